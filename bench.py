@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--classes B_per_gpu | --classes-total B] [--variant v2|v1]
                     [--precision fftx3|fft|f16x3|f16x2|f32] [--pyramid] [--gather all|scores|detections]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,9 +11,14 @@ One "step" = the whole head (correlation -> TransformNet -> resample/pool -> box
 feature map [1,1024,60,80] against the classes of the run.  Inputs are synthetic (post-ReLU Gaussian features, perturbed
 TransformNet) and resident in HBM before the timed region.
 
+A plain run sets up, warms up, times the K steps of the headline workload and prints its line; --full adds the
+secondary measurements named below, each a run of its own.  --dump-outputs DIR writes what the last timed step returned
+(loc / cls / corners maps, per level with --pyramid, or the detections) to DIR/<name>.npy; the inputs are seeded, so two
+builds given the same arguments can be compared output for output.
+
 Workloads
-  N = 1 (default)  BASELINE.json configs[1]: 64 classes, V2 head.  The same run also times, with the driver's clock
-                   running, the other single-GPU readings of BASELINE.json's configs ("sweep" in bench_details.json, the
+  N = 1 (default)  BASELINE.json configs[1]: 64 classes, V2 head.  With --full the same run also times the other
+                   single-GPU readings of BASELINE.json's configs ("sweep" in bench_details.json, the
                    headline figures inside `config` of the line): 256 classes V1 head (configs[3]), all 1024 classes on one
                    GPU (configs[2], N = 1) and the 7-level pyramid at 128 classes (the per-GPU share of configs[4]: levels
                    back to back - the runner's default - and on one HIP stream per level); each entry carries its own
@@ -24,6 +30,7 @@ Workloads
                    the timed region).  The lighter exchanges are timed right after and reported under "other_gathers":
                    "scores" (north_star: "all-gather ... of per-class score maps before NMS", 19 KB per class) and
                    "detections" (every rank decodes + NMS-es its own classes, only surviving boxes cross xGMI).
+                   These, the one-GPU reference of the same workload and the all-gather probe need --full.
                    --classes B keeps B classes per GPU instead (weak scaling).
 
 Arithmetic (``--precision``):
@@ -49,22 +56,23 @@ Arithmetic (``--precision``):
   fft32            strictly fp32 and fast: fp32-MFMA correlation and 5x5 layers (as f32), the 7x7 layer in the frequency domain
                    in fp32 (as fft) - no fp16 value anywhere;
   f32              v_mfma_f32_32x32x2_f32, exact fp32 (the reference's direct arithmetic).
-The primary line is measured in the selected mode; the other modes are timed right after and reported under
-"other_precisions" so all are always on record.
+The primary line is measured in the selected mode; with --full the other modes are timed right after and reported under
+"other_precisions".
 
 Output (rank 0).  stdout carries ONE compact JSON line (<= 6000 bytes, strict JSON; round 4's 22 KB line could not be parsed by
-the driver): the driver's contract fields, `config` (incl. the same-run figures of the strict-fp32 modes, 256 classes V1, 1024 classes
-on one GPU with the longest kernel's live traffic, and the 7-level pyramid), and
+the driver): the driver's contract fields, `config` (with --full incl. the same-run figures of the strict-fp32 modes, 256 classes V1,
+1024 classes on one GPU with the longest kernel's live traffic, and the 7-level pyramid), and
   roofline       - the LONGEST kernel of the step by live HIP-event time: ALGORITHMIC FLOPs (or bytes) per launch / its mean launch
                    duration, measured with HIP events recorded on the launch stream inside the timed steps, against the dense MFMA
                    peak of the instruction (or the 8 TB/s HBM peak); `traffic` / `hbm_gbps` / `mfma_pipe_busy` /
-                   `effective_clock_ghz` are LIVE at N = 1: the run spawns rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE, SQ / GRBM:
-                   one pass each) over a 3-step child run of the same workload and merges them
+                   `effective_clock_ghz` are LIVE at N = 1 with --full: the run spawns rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE,
+                   SQ / GRBM: one pass each) over a 3-step child run of the same workload and merges them (replayed from
+                   profiles/ without --full)
   roofline_other - {kernel: [frac of its bound, avg launch ms]} of the other kernels of the step
   stages_ms      - mean duration of every stage of the step (same events)
   cpu_baseline   - the oracle (torch-CPU restatement of the reference head, driven one class at a time like the reference's
-                   evaluation) timed on the host cores, rank 0 / N=1 only, on a bounded class sample
-  end_to_end     - secondary: backbone + head + decode/NMS per image (N=1 only)
+                   evaluation) timed on the host cores, rank 0 / N=1 only, on a bounded class sample (--full)
+  end_to_end     - secondary: backbone + head + decode/NMS per image (N=1 only, --full)
 The FULL record - every kernel's roofline object, the other arithmetic modes, the sweep entries with their own roofline objects, the
 raw live counters at 64 and 1024 classes, both end-to-end legs - goes to bench_details.json (repo root, and gpurun_out/ when present)
 and to stderr (one line prefixed "[bench_details] ").
@@ -126,6 +134,14 @@ def parse():
                     help="skip the rocprofv3 PMC passes (FETCH_SIZE / WRITE_SIZE / SQ) the N=1 run spawns over a short child run")
     ap.add_argument("--no-end-to-end", action="store_true",
                     help="skip the secondary end-to-end leg (backbone + class-head build + head + decode/NMS)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the secondary measurements, each a run of its own: the other arithmetic modes, the sweep, the "
+                         "CPU baseline, the end-to-end legs and the live PMC counters (N = 1); the one-GPU reference, the other "
+                         "exchanges and the all-gather probe (N > 1).  Without it the run times the headline workload only; "
+                         "the --no-* switches above select among these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed, seeded sample of each array when they exceed it)")
     return ap.parse_args()
 
 
@@ -476,14 +492,18 @@ class Workload(object):
         self.sync_all()
         if sharded is not None:
             sharded.wait_events = []       # (before, after) HIP events around every gather wait of the timed steps
+        last = None
         # ---- timed region: exactly K steps; stage events are recorded on the launch stream inside these steps
         t0 = time.perf_counter()
         for i in range(steps):
-            step(event_sets[i] if event_sets else None)
+            last = step(event_sets[i] if event_sets else None)
+            if i + 1 < steps:
+                last = None           # only the last step's outputs outlive their step (the allocator reuses the blocks as before)
         while pending:
-            pending.pop(0)()          # every gather of the timed steps completes inside the timed region
+            last = pending.pop(0)()   # every gather of the timed steps completes inside the timed region
         self.sync_all()
         dt = time.perf_counter() - t0
+        self.last_outputs = last       # what the last timed step returned (the sharded path: its gathered maps)
         if sharded is not None and sharded.wait_events:
             self.gather_wait_ms = sum(a.elapsed_time(b) for a, b in sharded.wait_events) / steps
         if sharded is not None:
@@ -763,6 +783,51 @@ class Workload(object):
                     self.classes_total, self.B_local, "7 scales 0.5-1.6" if self.pyramid else "single scale",
                     self.variant.upper(), self.P, int(self.inverse)))
 
+    def output_arrays(self, out):
+        """{name: tensor} of what one step of the timed path returns to its caller (``out``, kept by run()): the head's
+        loc / cls / corners maps (its third output is cls again), the same per pyramid level, or the gathered detections."""
+        if self.coder is not None:
+            named = {"boxes": out.bbox_xyxy}
+            for f in out.fields():
+                v = out.get_field(f)
+                named[f] = v.bbox_xyxy if hasattr(v, "bbox_xyxy") else v
+        elif self.runner is not None:
+            locs, clss, corners, _ = out
+            named = {}
+            for i in range(len(clss)):
+                named.update({"loc_level{}".format(i): locs[i], "cls_level{}".format(i): clss[i], "corners_level{}".format(i): corners[i]})
+        else:
+            loc, cls, _, corners = out
+            named = {"loc": loc, "cls": cls, "corners": corners}
+        return {k: v for k, v in named.items() if v is not None}
+
+
+DUMP_BUDGET = 64 << 20      # bytes of all arrays --dump-outputs writes
+
+
+def dump_outputs(named, directory, budget=DUMP_BUDGET, seed=0):
+    """Write every tensor of ``named`` to directory/<name>.npy in float32 (float64 for other dtypes), whole when all of them
+    fit in ``budget`` bytes.  Otherwise each array is cut down to the same fraction of its elements: a 1-D sample at sorted
+    flat indices drawn with numpy's default generator from ``seed`` - fixed by the seed and the array's size, so two runs
+    of the same arguments sample the same elements.  Returns {name: {"shape", "sampled"}}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {}
+    for name, t in named.items():
+        a = t.detach().cpu().numpy()
+        arrays[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+    total = sum(a.nbytes for a in arrays.values())
+    keep = 1.0 if total <= budget else (budget - 4096 * len(arrays)) / float(total)     # (room for the .npy headers)
+    written = {}
+    for name, a in arrays.items():
+        sampled = keep < 1.0
+        if sampled:
+            idx = np.unique(np.random.default_rng(seed).integers(0, a.size, size=int(a.size * keep)))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written[name] = {"shape": list(arrays[name].shape), "sampled": sampled}
+    return written
+
 
 def precision_deviation(w):
     """max |mode - f32| of the head outputs on the benchmarked tensors (this run, this workload)."""
@@ -948,7 +1013,7 @@ def run_bench(args, rank, local_rank, world, dev, use_dist):
     if classes_total < world:
         raise SystemExit("need at least one class per rank")
     one_gpu = None
-    if use_dist and not args.no_one_gpu_reference:
+    if args.full and use_dist and not args.no_one_gpu_reference:
         # The N = 1 point of THIS curve, in THIS run: rank 0 alone times all classes_total classes of the same
         # workload on its GPU - the others wait at the barrier - so that the line of an N > 1 run carries its own single-GPU
         # reference and speed-up (the default N = 1 command measures configs[1], 64 classes: another workload).
@@ -968,6 +1033,9 @@ def run_bench(args, rank, local_rank, world, dev, use_dist):
 
     dt, stage_ms = w.run(args.precision, args.steps, args.warmup)
     value = classes_total * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(w.output_arrays(w.last_outputs), args.dump_outputs)
+        print("[bench] outputs of the last timed step in {}: {}".format(args.dump_outputs, dumped), file=sys.stderr, flush=True)
     effective = args.precision          # below 7 image-class pairs the fft modes run the direct f16x3 kernel for the 7x7 layer
     if not args.pyramid and getattr(w.head, "last_precision", None):
         effective = w.head.last_precision
@@ -1007,7 +1075,7 @@ def run_bench(args, rank, local_rank, world, dev, use_dist):
     else:
         result["roofline"] = w.roofline(args.precision, stage_ms, dt / args.steps)
     result["head_tflops_algorithmic"] = round(w.whole_head_flops_per_class() * value / 1e12, 3)
-    if not args.no_other_precision:
+    if args.full and not args.no_other_precision:
         result["other_precisions"] = []
         for other in ("fft", "fftx3", "f16x3", "f16x2", "fft32", "f32"):
             if other == args.precision:
@@ -1039,8 +1107,9 @@ def run_bench(args, rank, local_rank, world, dev, use_dist):
             t = torch.tensor([w.gather_wait_ms], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             result["gather_wait_ms"] = round(float(t.item()), 4)
-        result["allgather_probe"] = allgather_probe(dev, world)
-    if use_dist and not args.no_other_gather:
+        if args.full:
+            result["allgather_probe"] = allgather_probe(dev, world)
+    if args.full and use_dist and not args.no_other_gather:
         result["other_gathers"] = []
         for g in ("all", "scores", "detections"):
             if g == args.gather:
@@ -1050,7 +1119,7 @@ def run_bench(args, rank, local_rank, world, dev, use_dist):
             dt2, _ = wg.run(args.precision, n2, 1)
             result["other_gathers"].append({"gather": g, "what": gather_desc[g], "value": round(classes_total * n2 / dt2, 2),
                                             "ms_per_step": round(dt2 / n2 * 1e3, 4), "steps": n2})
-    single = rank == 0 and world == 1 and not args.force_dist
+    single = args.full and rank == 0 and world == 1 and not args.force_dist      # the single-GPU legs of --full
     if single and not args.no_sweep and not args.pyramid:
         # the other single-GPU readings of BASELINE.json's configs, timed in this very run
         n = max(2, min(args.steps, 5))

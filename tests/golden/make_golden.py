@@ -224,6 +224,21 @@ EXTREME_CASES = [
 ]
 
 
+MAX_FILE_BYTES = 1 << 20      # no fixture file above 1 MiB
+
+
+def save_head_fixture(name, arrays):
+    """head_<name>.npz; while the archive exceeds MAX_FILE_BYTES its largest reference array moves beside it as
+    head_<name>.<key>.npy (tests/util.py:load_head_fixture reads both)."""
+    path = os.path.join(HERE, "head_{}.npz".format(name))
+    arrays = dict(arrays)
+    np.savez_compressed(path, **arrays)
+    while os.path.getsize(path) > MAX_FILE_BYTES:
+        key = max((k for k in arrays if k.startswith("ref_")), key=lambda k: arrays[k].nbytes)
+        np.save(os.path.join(HERE, "head_{}.{}.npy".format(name, key)), arrays.pop(key))
+        np.savez_compressed(path, **arrays)
+
+
 def make_extreme_fixtures():
     for name, P, inverse, C, H, W, sizes, (s_fm, s_cls, s_net), bias, std, kind in EXTREME_CASES:
         if kind == "relu":
@@ -247,7 +262,7 @@ def make_extreme_fixtures():
             arrays["class_fm_{}".format(b)] = c.numpy()
         for k in ("loc", "cls", "corners", "params"):      # corr / q15 are covered by the five base cases
             arrays["ref_" + k] = out[k].numpy()
-        np.savez_compressed(os.path.join(HERE, "head_{}.npz".format(name)), **arrays)
+        save_head_fixture(name, arrays)
 
 
 def run_reference_head(P, inverse, fm, class_fms, state):
@@ -286,7 +301,7 @@ def make_head_fixtures():
             arrays["class_fm_{}".format(b)] = c.numpy()
         for k, v in out.items():
             arrays["ref_" + k] = v.numpy()
-        np.savez_compressed(os.path.join(HERE, "head_{}.npz".format(name)), **arrays)
+        save_head_fixture(name, arrays)
 
 
 # ----------------------------------------------------------------------------- decode fixtures

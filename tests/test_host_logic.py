@@ -327,6 +327,32 @@ def test_bench_compact_line_of_a_multi_rank_record():
     assert d["config"]["classes_per_gpu"] == [128] * 8
 
 
+def test_bench_dump_outputs_whole_or_a_fixed_seeded_sample(tmp_path):
+    """``bench.py --dump-outputs``: every output whole (float32 kept, other dtypes as float64) while all fit the budget;
+    beyond it a sorted sample of each array's own elements, the same in every run, all files together within the budget."""
+    import os
+    import numpy as np
+    import bench
+    named = {"loc": torch.arange(4000, dtype=torch.float32).reshape(1, 10, 4, 100), "labels": torch.arange(50, dtype=torch.int64)}
+    info = bench.dump_outputs(named, str(tmp_path / "whole"))
+    assert info == {"loc": {"shape": [1, 10, 4, 100], "sampled": False}, "labels": {"shape": [50], "sampled": False}}
+    loc, labels = np.load(str(tmp_path / "whole" / "loc.npy")), np.load(str(tmp_path / "whole" / "labels.npy"))
+    assert loc.dtype == np.float32 and np.array_equal(loc, named["loc"].numpy())
+    assert labels.dtype == np.float64 and np.array_equal(labels, np.arange(50))
+    budget = 2 * 4096 + 8200          # half of the 16400 bytes once the header allowance is taken off
+    runs = []
+    for run in ("a", "b"):
+        info = bench.dump_outputs(named, str(tmp_path / run), budget=budget)
+        assert all(v["sampled"] for v in info.values()) and info["loc"]["shape"] == [1, 10, 4, 100]
+        d = str(tmp_path / run)
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= budget
+        runs.append({k: np.load(os.path.join(d, k + ".npy")) for k in named})
+    for k, n in (("loc", 4000), ("labels", 50)):
+        a = runs[0][k]
+        assert np.array_equal(a, runs[1][k]) and a.ndim == 1 and 0 < a.size <= n // 2
+        assert np.all(np.diff(a) > 0) and a.min() >= 0 and a.max() < n       # distinct elements of the array, in index order
+
+
 def test_fixture_pins_cover_every_head_fixture_and_fp32_equivalent_mode():
     """tests/golden/head_fixture_pins.json (measured on an MI355X, regenerated by the golden GPU test under
     $OS2D_WRITE_FIXTURE_PINS) holds [cls, loc, corners] error ratios for every head fixture in every fp32-equivalent mode, all of them

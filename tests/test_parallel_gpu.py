@@ -37,12 +37,15 @@ def test_class_sharded_head_over_rccl(world, device):
 
 
 @pytest.mark.parametrize("extra", [["--pyramid", "--classes-total", "16"], ["--classes-total", "16", "--gather", "scores"]])
-def test_bench_distributed_path_runs_on_one_rank(extra, device):
+def test_bench_distributed_path_runs_on_one_rank(extra, device, tmp_path):
     """``bench.py --force-dist`` = the N>1 timed path (RCCL process group, sharded head, gather, optional pyramid runner)
-    with one rank: the configuration that crashed in round 1 (pyramid + scores gather) must produce its JSON line."""
+    with one rank: the configuration that crashed in round 1 (pyramid + scores gather) must produce its JSON line, and
+    --dump-outputs writes what the last timed step gathered."""
     import json
+    import numpy as np
+    where = str(tmp_path / "outputs")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--force-dist", "--steps", "2", "--warmup", "1",
-           "--no-sweep", "--no-cpu-baseline", "--no-end-to-end", "--no-other-precision"] + extra
+           "--no-sweep", "--no-cpu-baseline", "--no-end-to-end", "--no-other-precision", "--full", "--dump-outputs", where] + extra
     env = dict(os.environ, MASTER_PORT=str(_free_port()))
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -57,3 +60,11 @@ def test_bench_distributed_path_runs_on_one_rank(extra, device):
     assert probe["bytes_per_rank"] == 32 << 20 and probe["ms"] > 0 and probe["algbw_gbps"] > 0
     if "--pyramid" not in extra:
         assert d["gather_wait_ms"] >= 0.0
+    names = sorted(os.listdir(where))
+    if "--pyramid" in extra:        # per level, locations flattened like Os2dModel.forward's
+        assert names == sorted("{}_level{}.npy".format(k, i) for k in ("loc", "cls", "corners") for i in range(7))
+        assert np.load(os.path.join(where, "loc_level6.npy")).shape == (1, 16, 4, 96 * 128)
+    else:                           # the score maps are all that the "scores" exchange gathers
+        assert names == ["cls.npy"]
+        cls = np.load(os.path.join(where, "cls.npy"))
+        assert cls.shape == (1, 16, 1, 60, 80) and cls.dtype == np.float32 and np.isfinite(cls).all()

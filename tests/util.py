@@ -26,6 +26,9 @@ def load_head_fixture(name):
     for k in d.files:
         if k.startswith("ref_"):
             fx[k] = torch.from_numpy(d[k])
+    # arrays kept beside the archive (head_<name>.ref_<key>.npy) so that no fixture file exceeds 1 MiB
+    for path in glob.glob(os.path.join(GOLDEN, "head_{}.ref_*.npy".format(name))):
+        fx[os.path.basename(path)[len("head_{}.".format(name)):-len(".npy")]] = torch.from_numpy(np.load(path))
     return fx
 
 

@@ -3,7 +3,7 @@
 #   gpurun --timeout 1500 -- 'bash tools/gpu_call.sh <tag> <step> [<step> ...]'
 # steps:  tests            the whole GPU suite (pytest -m gpu)
 #         tests:<expr>     pytest -m gpu -k <expr>
-#         bench            the driver's command (python bench.py --gpus 1 --steps 20 --warmup 5): line + details + stderr
+#         bench            the driver's command with every secondary measurement (python bench.py --gpus 1 --steps 20 --warmup 5 --full): line + details + stderr
 #         stages[:<variant>]  stage times of the 64- and the 1024-class step (product library or a variant)
 #         bench1024        python bench.py --classes 1024 (stage times of the 1024-class step only)
 #         prof             rocprofv3 --kernel-trace --stats + PMC passes of the 64-class step (tools/profile_bench.sh)
@@ -33,7 +33,7 @@ for STEP in "$@"; do
     tests:*)
       ( time timeout 1200 python -m pytest tests -m gpu -q -p no:cacheprovider -k "${STEP#tests:}" ) > $OUT/pytest_k.log 2>&1; echo "pytest -k rc=$?" | tee -a $OUT/pytest_k.log; tail -15 $OUT/pytest_k.log;;
     bench)
-      ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? line bytes=$(wc -c < $OUT/bench.json)"
+      ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full ) > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$? line bytes=$(wc -c < $OUT/bench.json)"
       cp -f gpurun_out/bench_details.json $OUT/bench_details.json 2>/dev/null; cat $OUT/bench.json;;
     levels|levels:*)
       V=""; [ "$STEP" != levels ] && V=${STEP#levels:}
