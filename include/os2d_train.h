@@ -1,0 +1,90 @@
+/* os2d_train.h -- C ABI of libos2d_train.so: the backward pass of the OS2D head (reference os2d/modeling/head.py:308-435 under
+ * autograd) for the MI355X (gfx950), strict fp32.
+ *
+ * The forward of a training step is the "f32" route of libos2d_hip.so, run stage by stage (os2d_fm_sumsq, os2d_corr,
+ * os2d_transform_conv x 3, os2d_sample_decode) so that its intermediates stay alive: corr [NB,225,HW], the relu + L2
+ * normalised correlation rnorm [NB,226,PLANE], h1 [NB,128,PLANE], h2 [NB,64,PLANE] (after BatchNorm and ReLU) and the
+ * transformation parameters params [NB,P,HW].  NB = A*B (image-major pairs), HW = H*W, PLANE = os2d_plane_floats(H,W) of
+ * os2d_hip.h: the zero-bordered plane layout of the TransformNet activations (cell (h,w) at BASE + h*(W+3) + w).
+ *
+ * Conventions as os2d_hip.h: device pointers owned by the caller, fp32, dense; asynchronous on `stream`; 0 on success,
+ * negative on error (-1 bad argument, -2 workspace too small, -3 unsupported shape, -4 HIP runtime error), described by
+ * os2d_train_last_error() on the calling thread.  Arguments are checked before anything is launched.
+ *
+ * Arithmetic: fp32 throughout.  The matrix-shaped work (the transposed convolutions, the weight gradients, the two
+ * correlation GEMMs) runs on v_mfma_f32_16x16x4_f32.  Weight gradients reduce over NB * PLANE positions in split-K partial
+ * sums that a second kernel adds in a fixed order: deterministic.  The resampling backward scatters into d corr with fp32
+ * atomicAdd: the order of those additions is not fixed (as in torch's own grid_sample backward).                         */
+#ifndef OS2D_TRAIN_H
+#define OS2D_TRAIN_H
+
+#include <stddef.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define OS2D_TRAIN_ABI_VERSION 1
+
+int os2d_train_abi_version(void);
+const char* os2d_train_last_error(void);
+
+/* ---- (a) resample + pool + box decode backward (head.py:371-435).  corr [NB,225,HW], params [NB,P,HW] as the forward used
+ * them; upstream gradients dcls [NB,HW], dcls_det [NB,HW], dloc [NB,4,HW] (each may be NULL = zero).  dcls + dcls_det are
+ * ADDED into dcorr [NB,225,HW] (atomicAdd; the caller zeroes it); dcls and dloc give dparams [NB,P,HW] (written).  The
+ * corners carry no gradient (head.py:423).  stride / rec_field as os2d_sample_decode.                                     */
+int os2d_train_decode_backward(const float* corr, const float* params, const float* dcls, const float* dcls_det, const float* dloc,
+                               int NB, int H, int W, int P, int inverse, int stride, int rec_field, float* dcorr, float* dparams,
+                               void* stream);
+
+/* ---- layer 3 (64 -> P, 5x5, no BatchNorm): dparams [NB,P,HW] -> dy [NB,P,PLANE] (zero-bordered plane layout) and
+ * dbias [P] = sum over pairs and positions (written).                                                                   */
+int os2d_train_params_backward(const float* dparams, int NB, int P, int H, int W, float* dy, float* dbias, void* stream);
+
+/* ---- frozen (eval-mode) BatchNorm + ReLU backward of layer 1 (128 channels) or 2 (64): dh [NB,Cout,PLANE] = gradient of
+ * the layer's output h [NB,Cout,PLANE]; gamma / beta / running_var of the BatchNorm, eps its epsilon.  Writes dy
+ * [NB,Cout,PLANE] = dh * (h > 0) * gamma / sqrt(var + eps) (the gradient of the convolution output; zero at pad cells) and
+ * dgamma, dbeta, dbias [Cout] (each may be NULL: not computed).  dgamma uses (h - beta) / gamma for the normalised
+ * pre-activation: a channel with gamma == 0 gets dgamma = 0.                                                             */
+int os2d_train_bn_relu_backward(int layer, const float* dh, const float* h, const float* gamma, const float* beta,
+                                const float* running_var, float eps, int NB, int H, int W, float* dy, float* dgamma, float* dbeta,
+                                float* dbias, void* stream);
+
+/* ---- convolution backward, layer 1 (225 -> 128, 7x7), 2 (128 -> 64, 5x5) or 3 (64 -> P, 5x5); w = the layer's raw weights
+ * [Cout,Cin,k,k] (not BatchNorm-folded), dy [NB,Cout,PLANE] from the two calls above.
+ *   data:   dx [NB,Cin,PLANE] (the transposed convolution; zero at pad cells).  workspace: os2d_train_conv_data_workspace_floats
+ *           floats (the flipped, transposed filters).
+ *   weight: dw [Cout,Cin,k,k] = sum over pairs and positions of dy x (written); x = the layer's input as the forward read it
+ *           (layer 1: rnorm [NB,226,PLANE]; 2: h1 [NB,128,PLANE]; 3: h2 [NB,64,PLANE]).  The reduction over NB * PLANE is cut
+ *           into as many split-K slices as fit `workspace_floats` (at most 64, at least one slice of Cout*Cin*k*k floats).   */
+size_t os2d_train_conv_data_workspace_floats(int layer, int P);
+int os2d_train_conv_backward_data(int layer, int P, const float* w, const float* dy, int NB, int H, int W, float* dx,
+                                  float* workspace, size_t workspace_floats, void* stream);
+size_t os2d_train_conv_weight_slice_floats(int layer, int P);
+int os2d_train_conv_backward_weight(int layer, int P, const float* x, const float* dy, int NB, int H, int W, float* dw,
+                                    float* workspace, size_t workspace_floats, void* stream);
+
+/* ---- relu + L2 over the 225 channels (eps 1e-6, head.py:650) backward: dxn [NB,225,PLANE] = gradient of the normalised
+ * tensor; ADDS the gradient of the raw correlation into dcorr [NB,225,HW].                                              */
+int os2d_train_norm225_backward(const float* corr, const float* dxn, int NB, int H, int W, float* dcorr, void* stream);
+
+/* ---- correlation + normalisation backward (head.py:339-350, 293): fm [A,C,H,W] raw image features, qp [B,C,256] the class
+ * operand of os2d_class_prepare_batch (normalised, x-major channels), dcorr [A*B,225,HW].
+ *   dfm [A,C,H,W]   gradient of the raw image features (image L2 over C, eps 1e-5), written; NULL = not computed;
+ *   dq  [B,C,225]   gradient of the normalised class maps, x-major channel order (m = x*15 + y), written; NULL = not computed.
+ * workspace: os2d_train_corr_workspace_floats(A,C,H,W) floats.                                                          */
+size_t os2d_train_corr_workspace_floats(int A, int C, int H, int W);
+int os2d_train_corr_backward(const float* fm, const float* qp, const float* dcorr, int A, int B, int C, int H, int W, float* dfm,
+                             float* dq, float* workspace, size_t workspace_floats, void* stream);
+
+/* ---- class map backward, the inverse of os2d_class_prepare_batch (head.py:241-268): q15 [B,C,225] the resized, NOT normalised
+ * maps (cell order i*15 + j; os2d_class_prepare_batch with normalize = 0), dq [B,C,225] from os2d_train_corr_backward.  L2 over
+ * C (eps 1e-5) backward, then bilinear-resize backward (align_corners = True, zero padding) into dsrcs[b] [C,h_b,w_b]
+ * (written), sizes = [B][2] (h, w) on the device.  workspace: B*C*225 floats.                                            */
+int os2d_train_class_backward(const float* q15, const float* dq, int B, int C, float* const* dsrcs, const int* sizes,
+                              float* workspace, size_t workspace_floats, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -2,6 +2,7 @@
 
     python -m os2d_amd.build                      # build if stale
     python -m os2d_amd.build --force
+    python -m os2d_amd.build --train              # only libos2d_train.so (the head's backward pass)
     python -m os2d_amd.build --variant TAG [--packed on|off|fft] [-DFLAG ...]
                                                   # diagnostic copy under tools/diag_libs/TAG/ (run with OS2D_HIP_LIB=...)
 """
@@ -32,6 +33,14 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc",
 PACKED_OFF = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 NO_PACKED_FP32 = set(SOURCES)             # which translation units are compiled without the packed instructions
 FLAGS += os.environ.get("OS2D_EXTRA_HIPCC_FLAGS", "").split()      # kernel experiments (-DOS2D_DIAG_...); part of the source hash
+
+# The backward pass of the head is a library of its own (include/os2d_train.h): libos2d_hip.so keeps exactly the sources and
+# kernels above.  Its units may include the forward's headers (csrc/*.h) to share the sampling and decode arithmetic.
+TRAIN_CSRC = os.path.join(HERE, "csrc_train")
+TRAIN_SOURCES = ["train.hip"]
+TRAIN_LIB_PATH = os.path.join(LIB_DIR, "libos2d_train.so")
+TRAIN_BUILD_DIR = os.path.join(TRAIN_CSRC, "build")
+TRAIN_FLAGS = FLAGS + PACKED_OFF
 
 
 def headers():
@@ -138,7 +147,59 @@ def build(force=False, verbose=True):
         with open(STAMP_PATH + ".tmp", "w") as f:
             f.write(digest + "\n")
         os.replace(STAMP_PATH + ".tmp", STAMP_PATH)
+    build_train(force=force, verbose=verbose)
     return LIB_PATH
+
+
+def train_headers():
+    return sorted(glob.glob(os.path.join(TRAIN_CSRC, "*.h"))) + headers() + [os.path.join(HERE, "..", "include", "os2d_train.h")]
+
+
+def train_source_hash():
+    h = hashlib.sha256((" ".join(TRAIN_FLAGS) + "\n").encode())
+    for path in [os.path.join(TRAIN_CSRC, s) for s in TRAIN_SOURCES] + train_headers():
+        h.update(os.path.basename(path).encode())
+        with open(path, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()
+
+
+def train_up_to_date():
+    stamp = TRAIN_LIB_PATH + ".srchash"
+    if not (os.path.exists(TRAIN_LIB_PATH) and os.path.exists(stamp)):
+        return False
+    with open(stamp) as f:
+        return f.read().strip() == train_source_hash()
+
+
+def build_train(force=False, verbose=True):
+    """Compile the backward-pass units for gfx950 and link libos2d_train.so.  Returns its path."""
+    if not force and train_up_to_date():
+        return TRAIN_LIB_PATH
+    hipcc = _hipcc()
+    os.makedirs(LIB_DIR, exist_ok=True)
+    os.makedirs(TRAIN_BUILD_DIR, exist_ok=True)
+    procs, objs = [], []
+    for s in TRAIN_SOURCES:
+        obj = os.path.join(TRAIN_BUILD_DIR, s.replace(".hip", ".o"))
+        objs.append(obj)
+        cmd = [hipcc] + TRAIN_FLAGS + ["-c", os.path.join(TRAIN_CSRC, s), "-o", obj]
+        if verbose:
+            print("[os2d_amd.build]", " ".join(cmd), flush=True)
+        procs.append((cmd, subprocess.Popen(cmd)))
+    _wait(procs)
+    digest = train_source_hash()
+    tmp = TRAIN_LIB_PATH + ".tmp.{}".format(os.getpid())
+    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", tmp] + objs
+    if verbose:
+        print("[os2d_amd.build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    os.replace(tmp, TRAIN_LIB_PATH)
+    stamp = TRAIN_LIB_PATH + ".srchash"
+    with open(stamp + ".tmp", "w") as f:
+        f.write(digest + "\n")
+    os.replace(stamp + ".tmp", stamp)
+    return TRAIN_LIB_PATH
 
 
 def build_variant(tag, packed=None, extra=(), verbose=False):
@@ -163,5 +224,7 @@ if __name__ == "__main__":
         tag = argv[i + 1]
         packed = argv[argv.index("--packed") + 1] if "--packed" in argv else None
         print(build_variant(tag, packed, [a for a in argv if a.startswith("-D")], verbose=True))
+    elif "--train" in argv:
+        print(build_train(force="--force" in argv))
     else:
         print(build(force="--force" in argv))

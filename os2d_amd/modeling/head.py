@@ -11,7 +11,13 @@ Same class names, constructor arguments, attribute names and state-dict keys as 
 
 All arithmetic of the path runs in the hand-written gfx950 kernels (os2d_amd/csrc); PyTorch only owns device
 memory, the stream and the parameter containers.  There is no CPU / eager fallback: CPU tensors raise.
-Training through the head (autograd) is out of scope and raises as well.
+
+Training: when grad mode is on and the image feature maps, the raw class maps given to ``create_os2d_head`` or a TransformNet
+parameter require grad, ``Os2dHead.forward`` runs the strict-fp32 "f32" route stage by stage, keeps its intermediates, and its
+backward pass runs in libos2d_train.so (os2d_amd/csrc_train, fp32 MFMA; see head_train.py).  Gradients reach the image and raw
+class maps and every TransformNet weight, bias and BatchNorm affine parameter; BatchNorm must be frozen (eval mode, the
+reference's training default); maps wider than MAX_W_DIRECT7 columns raise.  ``TransformationNet.forward`` on its own and the
+other precisions stay inference-only.
 """
 import collections
 import itertools
@@ -25,6 +31,7 @@ import torch.nn as nn
 from .. import _lib
 from ..structures.feature_map import FeatureMapSize
 from .box_coder import BoxGridGenerator
+from . import head_train
 
 TEMPLATE = 15
 QROWS = 256
@@ -719,9 +726,14 @@ class Os2dHeadCreator(nn.Module):
     def create_os2d_head(self, class_feature_maps):
         """class_feature_maps: list of [1,C,h_i,w_i] device tensors (reference head.py:261-268)."""
         q15, qp = _prepare_class_maps(class_feature_maps, normalise=True)
-        return Os2dHead(q15, self.aligner, self.box_grid_generator_image_level,
+        head = Os2dHead(q15, self.aligner, self.box_grid_generator_image_level,
                         self.box_grid_generator_feature_map_level, _prepared=qp,
                         _stride=self.feature_map_stride, _rec_field=self.feature_map_receptive_field)
+        # the raw maps, so that a training forward can return their gradient (head_train.py)
+        if isinstance(class_feature_maps, torch.Tensor):
+            class_feature_maps = [m.unsqueeze(0) for m in class_feature_maps]
+        head._raw_class_maps = list(class_feature_maps)
+        return head
 
 
 def _prepare_class_maps(class_feature_maps, normalise=True):
@@ -774,8 +786,9 @@ class Os2dHead(nn.Module):
     Differences from the reference, by design:
       * one ``forward`` handles all B classes in a single library call (the reference's evaluation loops B=1
         heads, os2d/engine/evaluate.py:323-331) - the per-class results are identical;
-      * eval mode only: ``output_recognition_transform_detached`` is the same tensor as ``output_recognition``
-        (as in the reference when no gradient is required, head.py:400-402).
+      * without autograd ``output_recognition_transform_detached`` is the same tensor as ``output_recognition`` (as in the
+        reference when no gradient is required, head.py:400-402); with autograd (head_train.py) it is a separate tensor of the
+        same values whose gradient does not reach the transformation.
     """
 
     def __init__(self, class_feature_maps, aligner, box_grid_generator_image_level,
@@ -792,6 +805,7 @@ class Os2dHead(nn.Module):
             # public constructor, as in the reference: maps are resized but not yet normalised (head.py:293)
             class_feature_maps, _prepared = _prepare_class_maps(class_feature_maps, normalise=True)
         self.class_feature_maps = class_feature_maps          # normalised, [B,C,15,15]
+        self._raw_class_maps = None                           # the maps create_os2d_head was given (gradients of training)
         self._qp = _prepared                                  # GEMM operand [B,C,256]
         self._qs = None                                       # its fp16 hi/lo split (f16x3 mode), built on first use
         self.class_batch_size = self.class_feature_maps.size(0)
@@ -886,8 +900,16 @@ class Os2dHead(nn.Module):
         feature_maps = _require_device_f32(feature_maps, "feature_maps")
         if feature_maps.dim() != 4:
             raise RuntimeError("feature_maps must be [A,C,H,W], got {}".format(tuple(feature_maps.shape)))
+        _resolve(precision or self.precision)          # a bad precision is refused on every route
+        if out is None and stage_events is None and head_train.needs_grad(self, feature_maps):
+            # training: the strict-fp32 route with a HIP backward pass (``precision`` / ``route_pairs`` do not apply)
+            if feature_maps.size(1) != self.class_feature_maps.size(1):
+                raise RuntimeError("Feature dimensionality of input={0} and class={1} feature maps has to equal".format(
+                    feature_maps.size(1), self.class_feature_maps.size(1)))
+            self.last_precision = "f32"
+            return head_train.head_forward_train(self, feature_maps)
         if torch.is_grad_enabled() and feature_maps.requires_grad:
-            raise RuntimeError("autograd through the HIP head is not implemented (training is out of scope): "
+            raise RuntimeError("autograd through the HIP head does not take preallocated outputs or stage events: "
                                "call under torch.no_grad()")
         A, C, H, W = feature_maps.shape
         B = self.class_batch_size

@@ -1,0 +1,204 @@
+"""Autograd through the HIP head: the training forward (the strict-fp32 "f32" route, stage by stage, intermediates kept) and
+the backward pass of libos2d_train.so (include/os2d_train.h), wrapped in one ``torch.autograd.Function``.
+
+``Os2dHead.forward`` comes here when grad mode is on and the image feature maps, the raw class maps the head was created from
+(``Os2dHeadCreator.create_os2d_head``) or a TransformNet parameter require grad.  Gradients reach
+  * the image feature maps (through the image L2 normalisation, eps 1e-5),
+  * the raw class maps (through the class L2 normalisation and the bilinear resize to 15 x 15),
+  * the TransformNet: conv.0 / conv.3 / linear weights and biases and the affine parameters of the frozen (eval-mode)
+    BatchNorms conv.1 / conv.4 (weight = gamma, bias = beta); the running statistics stay constants.
+As in the reference (head.py:396-402, 423): ``cls_det`` carries the same values as ``cls`` but its gradient reaches the
+correlation only, not the transformation; ``corners`` carries none.
+"""
+import ctypes
+
+import torch
+
+from .. import _lib
+from .. import _train_lib
+
+TEMPLATE = 15
+MAX_W_DIRECT7 = 209
+
+
+def _ptr(t):
+    return _lib.ptr(t)
+
+
+def _wgrad_splits(NB, PL):
+    """Split-K slices of a weight gradient: one per ~4096 positions of the NB * PLANE reduction, at most 64."""
+    return max(1, min(64, (NB * PL + 4095) // 4096))
+
+
+class _HeadFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, head, n_class, fm, *tensors):
+        raws, params = tensors[:n_class], tensors[n_class:]
+        lib = _lib.load()
+        A, C, H, W = fm.shape
+        B = head.class_batch_size
+        NB, HW = A * B, H * W
+        dev = fm.device
+        regressor = head.aligner.parameter_regressor
+        P = regressor.output_dim
+        inverse = 1 if head.aligner.use_inverse_geom_model else 0
+        w1, b1, w2, b2, w3, b3 = regressor.packed("f32")
+        PL = int(lib.os2d_plane_floats(H, W))
+        f32 = dict(dtype=torch.float32, device=dev)
+        sumsq = torch.empty(A * HW, **f32)
+        corr = torch.empty(NB, 225, HW, **f32)
+        rnorm = torch.empty(NB * 226 * PL, **f32)
+        h1 = torch.empty(NB * 128 * PL, **f32)
+        h2 = torch.empty(NB * 64 * PL, **f32)
+        prm = torch.empty(NB, P, HW, **f32)
+        loc = torch.empty(A, B, 4, H, W, **f32)
+        cls = torch.empty(A, B, 1, H, W, **f32)
+        corners = torch.empty(A, B, 8, H, W, **f32)
+        with torch.cuda.device(dev):
+            s = _lib.current_stream(dev)
+            _lib.check(lib.os2d_fm_sumsq(_ptr(fm), _ptr(sumsq), A, C, H, W, s), "os2d_fm_sumsq")
+            _lib.check(lib.os2d_corr(_ptr(fm), _ptr(head._qp), _ptr(sumsq), _ptr(corr), _ptr(rnorm), A, B, C, H, W, s), "os2d_corr")
+            for layer, src, wp, bp, dst in ((1, rnorm, w1, b1, h1), (2, h1, w2, b2, h2), (3, h2, w3, b3, prm)):
+                _lib.check(lib.os2d_transform_conv(layer, _ptr(src), _ptr(wp), _ptr(bp), _ptr(dst), NB, P, H, W, s),
+                           "os2d_transform_conv")
+            _lib.check(lib.os2d_sample_decode(_ptr(corr), _ptr(prm), NB, H, W, P, inverse, head._stride, head._rec_field,
+                                              _ptr(loc), _ptr(cls), _ptr(corners), s), "os2d_sample_decode")
+        q15raw = None
+        if any(ctx.needs_input_grad[3:3 + n_class]):
+            from .head import _prepare_class_maps
+            q15raw, _ = _prepare_class_maps(list(raws), normalise=False)
+        ctx.head, ctx.n_class, ctx.shape = head, n_class, (A, B, C, H, W, P, inverse, PL)
+        ctx.saved = dict(fm=fm, raws=raws, corr=corr, rnorm=rnorm, h1=h1, h2=h2, params=prm, q15raw=q15raw,
+                         weights=[p.detach().contiguous() for p in params])
+        ctx.mark_non_differentiable(corners)
+        return loc, cls, cls.clone(), corners
+
+    @staticmethod
+    def backward(ctx, dloc, dcls, dcls_det, _dcorners):
+        tl = _train_lib.load()
+        head, n_class = ctx.head, ctx.n_class
+        A, B, C, H, W, P, inverse, PL = ctx.shape
+        sv = ctx.saved
+        NB, HW = A * B, H * W
+        fm = sv["fm"]
+        dev = fm.device
+        need = ctx.needs_input_grad
+        need_fm, need_cls = need[2], any(need[3:3 + n_class])
+        need_p = need[3 + n_class:]
+        w1, b1, g1, be1, w2, b2, g2, be2, w3, b3 = sv["weights"]
+        regressor = head.aligner.parameter_regressor
+        bn1, bn2 = regressor.conv[1], regressor.conv[4]
+        f32 = dict(dtype=torch.float32, device=dev)
+
+        def grad_in(t):
+            return None if t is None else t.contiguous()
+        dloc, dcls, dcls_det = grad_in(dloc), grad_in(dcls), grad_in(dcls_det)
+        grads = [None] * 10
+        dfm, draws = None, [None] * n_class
+        with torch.cuda.device(dev):
+            s = _lib.current_stream(dev)
+            dcorr = torch.zeros(NB, 225, HW, **f32)
+            dparams = torch.empty(NB, P, HW, **f32)
+            _train_lib.check(tl.os2d_train_decode_backward(_ptr(sv["corr"]), _ptr(sv["params"]), _ptr(dcls), _ptr(dcls_det), _ptr(dloc),
+                                                           NB, H, W, P, inverse, head._stride, head._rec_field, _ptr(dcorr),
+                                                           _ptr(dparams), s), "os2d_train_decode_backward")
+            splits = _wgrad_splits(NB, PL)
+
+            def wgrad(layer, x, dy, like):
+                n = int(tl.os2d_train_conv_weight_slice_floats(layer, P))
+                ws = torch.empty(n * splits, **f32)
+                dw = torch.empty_like(like)
+                _train_lib.check(tl.os2d_train_conv_backward_weight(layer, P, _ptr(x), _ptr(dy), NB, H, W, _ptr(dw), _ptr(ws), ws.numel(), s),
+                                 "os2d_train_conv_backward_weight")
+                return dw
+
+            def dgrad(layer, w, dy, cin):
+                ws = torch.empty(int(tl.os2d_train_conv_data_workspace_floats(layer, P)), **f32)
+                dx = torch.empty(NB * cin * PL, **f32)
+                _train_lib.check(tl.os2d_train_conv_backward_data(layer, P, _ptr(w), _ptr(dy), NB, H, W, _ptr(dx), _ptr(ws), ws.numel(), s),
+                                 "os2d_train_conv_backward_data")
+                return dx
+
+            def bn_relu(layer, dh, h, bn, gamma, beta, cout, ig, ib, iw):
+                dy = torch.empty(NB * cout * PL, **f32)
+                dg = torch.empty(cout, **f32) if need_p[ig] else None
+                dbe = torch.empty(cout, **f32) if need_p[ib] else None
+                db = torch.empty(cout, **f32) if need_p[iw] else None
+                _train_lib.check(tl.os2d_train_bn_relu_backward(layer, _ptr(dh), _ptr(h), _ptr(gamma), _ptr(beta),
+                                                                _ptr(bn.running_var.detach().contiguous()), ctypes.c_float(float(bn.eps)),
+                                                                NB, H, W, _ptr(dy), _ptr(dg), _ptr(dbe), _ptr(db), s),
+                                 "os2d_train_bn_relu_backward")
+                grads[ig], grads[ib], grads[iw] = dg, dbe, db
+                return dy
+
+            # layer 3 (linear): parameters -> plane gradient, bias gradient
+            dy3 = torch.empty(NB * P * PL, **f32)
+            db3 = torch.empty(P, **f32) if need_p[9] else None
+            _train_lib.check(tl.os2d_train_params_backward(_ptr(dparams), NB, P, H, W, _ptr(dy3), _ptr(db3), s),
+                             "os2d_train_params_backward")
+            grads[9] = db3
+            if need_p[8]:
+                grads[8] = wgrad(3, sv["h2"], dy3, w3)
+            need_below = need_fm or need_cls or any(need_p[:8])
+            if need_below:
+                dh2 = dgrad(3, w3, dy3, 64)
+                dy2 = bn_relu(2, dh2, sv["h2"], bn2, g2, be2, 64, 6, 7, 5)
+                if need_p[4]:
+                    grads[4] = wgrad(2, sv["h1"], dy2, w2)
+                dh1 = dgrad(2, w2, dy2, 128)
+                dy1 = bn_relu(1, dh1, sv["h1"], bn1, g1, be1, 128, 2, 3, 1)
+                if need_p[0]:
+                    grads[0] = wgrad(1, sv["rnorm"], dy1, w1)
+                if need_fm or need_cls:
+                    dxn = dgrad(1, w1, dy1, 225)
+                    _train_lib.check(tl.os2d_train_norm225_backward(_ptr(sv["corr"]), _ptr(dxn), NB, H, W, _ptr(dcorr), s),
+                                     "os2d_train_norm225_backward")
+            if need_fm or need_cls:
+                ws = torch.empty(int(tl.os2d_train_corr_workspace_floats(A, C, H, W)), **f32)
+                dfm = torch.empty(A, C, H, W, **f32) if need_fm else None
+                dq = torch.empty(B, C, 225, **f32) if need_cls else None
+                _train_lib.check(tl.os2d_train_corr_backward(_ptr(fm), _ptr(head._qp), _ptr(dcorr), A, B, C, H, W, _ptr(dfm), _ptr(dq),
+                                                             _ptr(ws), ws.numel(), s), "os2d_train_corr_backward")
+                if need_cls:
+                    raws = sv["raws"]
+                    draws = [torch.empty(r.shape, **f32) for r in raws]
+                    ptrs = torch.tensor([d.data_ptr() for d in draws], dtype=torch.int64).to(dev)
+                    sizes = torch.tensor([[r.shape[-2], r.shape[-1]] for r in raws], dtype=torch.int32).to(dev)
+                    cws = torch.empty(B * C * 225, **f32)
+                    _train_lib.check(tl.os2d_train_class_backward(_ptr(sv["q15raw"]), _ptr(dq), B, C, _ptr(ptrs), _ptr(sizes), _ptr(cws),
+                                                                  cws.numel(), s), "os2d_train_class_backward")
+                    draws = [d if need[3 + i] else None for i, d in enumerate(draws)]
+        grads = [g if need_p[i] else None for i, g in enumerate(grads)]
+        return (None, None, dfm) + tuple(draws) + tuple(grads)
+
+
+def transform_parameters(regressor):
+    """The TransformNet tensors that receive gradients, in the Function's order (reference state-dict names)."""
+    c = regressor.conv
+    return [c[0].weight, c[0].bias, c[1].weight, c[1].bias, c[3].weight, c[3].bias, c[4].weight, c[4].bias,
+            regressor.linear.weight, regressor.linear.bias]
+
+
+def needs_grad(head, feature_maps):
+    """True when grad mode is on and something the head reads requires grad."""
+    if not torch.is_grad_enabled():
+        return False
+    raws = head._raw_class_maps or []
+    return (feature_maps.requires_grad or any(r.requires_grad for r in raws)
+            or any(p.requires_grad for p in transform_parameters(head.aligner.parameter_regressor)))
+
+
+def head_forward_train(head, feature_maps):
+    """(loc, cls, cls_det, corners) of ``Os2dHead.forward`` with autograd (see the module docstring)."""
+    A, C, H, W = feature_maps.shape
+    if W > MAX_W_DIRECT7:
+        raise RuntimeError("autograd through the HIP head needs feature maps at most {} columns wide (the direct 7x7 kernels of the "
+                           "training forward), got W={}: crop the training images".format(MAX_W_DIRECT7, W))
+    regressor = head.aligner.parameter_regressor
+    regressor.check_ready()
+    _train_lib.load()                       # a missing backward library is an error now, not at backward time
+    raws = list(head._raw_class_maps) if head._raw_class_maps is not None else []
+    for r in raws:
+        if r.device != feature_maps.device or r.dtype != torch.float32:
+            raise RuntimeError("raw class maps must be float32 on {}".format(feature_maps.device))
+    return _HeadFunction.apply(head, len(raws), feature_maps, *raws, *transform_parameters(regressor))

@@ -1,0 +1,90 @@
+"""Time the training step of the head at the reference training shape (A = 4 images, B = 15 classes, C = 1024, 38 x 38):
+the HIP training forward (the "f32" route with its intermediates kept) and the HIP backward pass (libos2d_train.so), against
+the same step done eagerly by torch: the oracle's ``head_forward`` under autograd on the same GPU.
+
+    python tools/time_head_backward.py [--reps N] [--no-eager] [--A 4 --B 15 --C 1024 --H 38 --W 38]
+
+Per-kernel times: run it under ``rocprofv3 --kernel-trace --stats -- python tools/time_head_backward.py --reps 1 --no-eager``.
+Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--A", type=int, default=4)
+    ap.add_argument("--B", type=int, default=15)
+    ap.add_argument("--C", type=int, default=1024)
+    ap.add_argument("--H", type=int, default=38)
+    ap.add_argument("--W", type=int, default=38)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--no-eager", action="store_true")
+    a = ap.parse_args()
+    from os2d_amd.modeling.head import build_os2d_head_creator
+    from os2d_amd.structures.feature_map import FeatureMapSize
+    from os2d_amd.utils import synthetic
+    from oracle import head_oracle as O
+
+    dev = torch.device("cuda:0")
+    state = synthetic.make_transform_net_state(6, seed=3)
+    creator = build_os2d_head_creator(False, False, True, FeatureMapSize(w=16, h=16), FeatureMapSize(w=16, h=16))
+    creator.aligner.parameter_regressor.load_state_dict(state)
+    creator.to(dev).eval()
+    fm = synthetic.make_feature_map(a.C, a.H, a.W, seed=5, A=a.A).to(dev).requires_grad_(True)
+    raws = [c.to(dev).requires_grad_(True) for c in synthetic.make_class_feature_maps(a.B, a.C, sizes=[(15, 15), (20, 24)], seed=9)]
+    g = torch.Generator().manual_seed(1)
+    gl = torch.randn(a.A, a.B, 4, a.H, a.W, generator=g).to(dev)
+    gc = torch.randn(a.A, a.B, 1, a.H, a.W, generator=g).to(dev)
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(a.reps):
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            e0.record()
+            out = fn(e1)
+            e2.record()
+            torch.cuda.synchronize()
+            ts.append((e0.elapsed_time(e1), e1.elapsed_time(e2)))
+            del out
+        ts.sort(key=lambda t: t[0] + t[1])
+        return ts[len(ts) // 2]
+
+    def hip_step(mid=None):
+        head = creator.create_os2d_head(raws)
+        loc, cls, cls_det, _ = head(fm)
+        if mid is not None:
+            mid.record()
+        ((loc * gl).sum() + (cls * gc).sum() + (cls_det * gc).sum()).backward()
+        return loc
+
+    fwd, bwd = timed(hip_step)
+    res = {"shape": [a.A, a.B, a.C, a.H, a.W], "hip_forward_ms": round(fwd, 3), "hip_backward_ms": round(bwd, 3)}
+    if not a.no_eager:
+        st = {k: v.to(dev).requires_grad_(k.endswith("weight") or k.endswith("bias")) for k, v in state.items()}
+
+        def eager_step(mid=None):
+            with torch.device(dev):          # the oracle builds its grids / masks with default-device factories
+                q = O.prepare_class_maps(raws)
+                loc, cls, cls_det, _ = O.head_forward(fm, q, st, True)
+            if mid is not None:
+                mid.record()
+            ((loc * gl).sum() + (cls * gc).sum() + (cls_det * gc).sum()).backward()
+            return loc
+        try:
+            efwd, ebwd = timed(eager_step)
+            res.update({"eager_forward_ms": round(efwd, 3), "eager_backward_ms": round(ebwd, 3)})
+        except RuntimeError as e:       # report, do not hide: the comparison point is missing
+            res["eager_error"] = str(e)[:300]
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
