@@ -1,5 +1,6 @@
 /* os2d_train.h -- C ABI of libos2d_train.so: the backward pass of the OS2D head (reference os2d/modeling/head.py:308-435 under
- * autograd) for the MI355X (gfx950), strict fp32.
+ * autograd) for the MI355X (gfx950), strict fp32, and - since ABI version 2 - the target assignment and the training
+ * objective (the last section of this file).
  *
  * The forward of a training step is the "f32" route of libos2d_hip.so, run stage by stage (os2d_fm_sumsq, os2d_corr,
  * os2d_transform_conv x 3, os2d_sample_decode) so that its intermediates stay alive: corr [NB,225,HW], the relu + L2
@@ -24,7 +25,7 @@
 extern "C" {
 #endif
 
-#define OS2D_TRAIN_ABI_VERSION 1
+#define OS2D_TRAIN_ABI_VERSION 2
 
 int os2d_train_abi_version(void);
 const char* os2d_train_last_error(void);
@@ -83,6 +84,58 @@ int os2d_train_corr_backward(const float* fm, const float* qp, const float* dcor
  * (written), sizes = [B][2] (h, w) on the device.  workspace: B*C*225 floats.                                            */
 int os2d_train_class_backward(const float* q15, const float* dq, int B, int C, float* const* dsrcs, const int* sizes,
                               float* workspace, size_t workspace_floats, void* stream);
+
+/* ==== Target assignment and the training objective (csrc_train/objective.hip; reference os2d/modeling/box_coder.py:234-389 and
+ * os2d/engine/objective.py:107-313).  A images, B labels, HW = H*W anchors per level, N = A*B*HW elements.  Class targets are
+ * int64 (1 positive, 0 negative, -1 ignored), as the reference returns them.  No call synchronises with the host; float sums
+ * are reduced in a fixed order (block partials, then one combining block), so two runs on the same input give the same bits. */
+
+/* ---- anchors to ground truth, one thread per (image, label, anchor).  Ground truth arrives packed: gt_boxes [n,4] xyxy,
+ * gt_labels [n] int32, gt_difficult [n] bytes, image_offsets [A+1] int32 (the boxes of image a are offsets[a] .. offsets[a+1]-1;
+ * num_boxes = n may be 0, then the three gt pointers may be NULL).  Anchors are the closed form of os2d_sample_decode: cell (y,x)
+ * centred at ((x+0.5)*stride, (y+0.5)*stride), size rec_field + 14*stride, row-major.  IoU as boxlist_iou in fp32; the best box is
+ * the first maximum; torchvision's Matcher(iou_high, iou_low) without low-quality matches (below low: -1, [low, high): -2, a
+ * matched difficult box: -2); class target = 1 + clamp(index, -2, 0).
+ *   mode 0 (encode):  cls_targets [A,B,HW] int64 and loc_targets [A,B,4,HW] = encode_boxes, weights (10,10,5,5), of the matched box
+ *                     against the anchor after clip_to_min_size(1); an unmatched anchor gets the value for the label's FIRST box;
+ *                     a label without a box in the image gets zeros.  loc_scores and the two IoU outputs are not used.
+ *   mode 1 (remap):   the anchor is replaced by the box decoded from loc_scores [A,B,4,HW] (BoxCoder.decode_single, dw / dh
+ *                     clamped at log(1000/16)); writes cls_targets (the remapped targets), ious_anchor (best IoU of the plain
+ *                     anchor) and ious_anchor_corrected (best IoU of the decoded box), each [A,B,HW].  loc_targets is not used. */
+int os2d_train_assign_targets(int mode, const float* gt_boxes, const int* gt_labels, const unsigned char* gt_difficult,
+                              const int* image_offsets, int num_boxes, const float* loc_scores, int A, int B, int H, int W, int stride,
+                              int rec_field, float iou_high, float iou_low, float* loc_targets, long long* cls_targets,
+                              float* ious_anchor, float* ious_anchor_corrected, void* stream);
+
+/* ---- objective forward.  class_loss 0 = ContrastiveLoss (squared half-margins, then hard-negative mining: the
+ * k = neg_to_pos_ratio * num_pos largest losses among the candidates - elements neither positive nor ignored - found by a radix
+ * select over the fp32 bit patterns, elements equal to the k-th taken in increasing flat index), 1 = RLL (linear half-margins,
+ * positives rescaled by num_pos / num_nontrivial_pos, negatives weighted by exp((l - max_l) * T), T = -log(rll_neg_weight_ratio) /
+ * max_l per label, normalised per label and by the number of labels with max_l > 1e-5; no mining: every candidate is used when
+ * neg_to_pos_ratio * num_pos > 0, none otherwise).  patch_mining_mode != 0 skips the RLL normalisation and the mining.
+ * loc_preds / loc_targets [A,B,4,HW], cls_preds [A,B,HW], cls_targets [A,B,HW] int64; cls_targets_remapped (NULL = none) replaces
+ * cls_targets for the class loss, not for the localisation loss; cls_preds_for_neg (NULL = none) replaces cls_preds at negatives.
+ * Outputs: losses [5] = loss, loc_smoothL1, cls, cls_pos, cls_neg; cls_loss [N] the per-element class loss; loc_loss [N] the
+ * per-element localisation loss (NULL = not written); flags [N] bytes (1 positive, 2 negative used, 4 regression positive,
+ * 8 candidate) and coef [N] (d class loss / d score before the count normalisation) for the backward.  The counts
+ * (a zero count divides as 1) stay in `workspace`, os2d_train_objective_workspace_floats floats, which the backward reads.   */
+size_t os2d_train_objective_workspace_floats(int A, int B, int HW);
+int os2d_train_objective_forward(int class_loss, int patch_mining_mode, const float* loc_preds, const float* loc_targets,
+                                 const float* cls_preds, const long long* cls_targets, const long long* cls_targets_remapped,
+                                 const float* cls_preds_for_neg, int A, int B, int HW, float margin, float margin_pos,
+                                 float class_loss_neg_weight, float localization_weight, float neg_to_pos_ratio,
+                                 double rll_neg_weight_ratio, float* losses, float* cls_loss, float* loc_loss, unsigned char* flags,
+                                 float* coef, float* workspace, size_t workspace_floats, void* stream);
+
+/* ---- objective backward, one kernel: grad_loss is the upstream gradient of losses[0] as a one-element device tensor; flags,
+ * coef and workspace as the forward left them.  Writes (each may be NULL = not computed) dloc_preds [A,B,4,HW] = clamp(diff,-1,1)
+ * * localization_weight / num_pos_for_regression at regression positives, dcls_preds [A,B,HW] and dcls_preds_for_neg [A,B,HW]:
+ * the class term goes to dcls_preds at positives and to dcls_preds_for_neg at the used negatives; without dcls_preds_for_neg
+ * both go to dcls_preds.  Zero elsewhere and where a clamp is inactive; the RLL weights and the counts are constants.       */
+int os2d_train_objective_backward(const float* grad_loss, const float* loc_preds, const float* loc_targets, const unsigned char* flags,
+                                  const float* coef, const float* workspace, int A, int B, int HW, float class_loss_neg_weight,
+                                  float localization_weight, float* dloc_preds, float* dcls_preds, float* dcls_preds_for_neg,
+                                  void* stream);
 
 #ifdef __cplusplus
 }

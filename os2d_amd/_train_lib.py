@@ -1,4 +1,5 @@
-"""ctypes binding of libos2d_train.so, the backward pass of the head (C ABI declared in include/os2d_train.h).
+"""ctypes binding of libos2d_train.so: the backward pass of the head, the target assignment and the training objective
+(C ABI declared in include/os2d_train.h).
 
 Same rules as ``_lib``: no fallback.  A missing or stale library is built in-tree (os2d_amd/build.py) and an export that is
 not there, or an ABI version that does not match, raises ``Os2dLibraryError``."""
@@ -9,12 +10,13 @@ from ._lib import Os2dLibraryError
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libos2d_train.so")
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 _p = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float
 _sz = ctypes.c_size_t
+_d = ctypes.c_double
 
 SIGNATURES = {
     "os2d_train_abi_version": (_i, []),
@@ -30,6 +32,11 @@ SIGNATURES = {
     "os2d_train_corr_workspace_floats": (_sz, [_i, _i, _i, _i]),
     "os2d_train_corr_backward": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "os2d_train_class_backward": (_i, [_p, _p, _i, _i, _p, _p, _p, _sz, _p]),
+    "os2d_train_assign_targets": (_i, [_i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p]),
+    "os2d_train_objective_workspace_floats": (_sz, [_i, _i, _i]),
+    "os2d_train_objective_forward": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _f, _d, _p, _p, _p, _p, _p,
+                                          _p, _sz, _p]),
+    "os2d_train_objective_backward": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _p, _p, _p, _p]),
 }
 
 _LIB = None

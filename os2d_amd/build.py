@@ -37,10 +37,13 @@ FLAGS += os.environ.get("OS2D_EXTRA_HIPCC_FLAGS", "").split()      # kernel expe
 # The backward pass of the head is a library of its own (include/os2d_train.h): libos2d_hip.so keeps exactly the sources and
 # kernels above.  Its units may include the forward's headers (csrc/*.h) to share the sampling and decode arithmetic.
 TRAIN_CSRC = os.path.join(HERE, "csrc_train")
-TRAIN_SOURCES = ["train.hip"]
+TRAIN_SOURCES = ["train.hip", "objective.hip"]
 TRAIN_LIB_PATH = os.path.join(LIB_DIR, "libos2d_train.so")
 TRAIN_BUILD_DIR = os.path.join(TRAIN_CSRC, "build")
 TRAIN_FLAGS = FLAGS + PACKED_OFF
+# objective.hip restates the reference's IoU and box encoding operation for operation: a fused multiply-add would round
+# differently from the CPU reference
+TRAIN_UNIT_FLAGS = {"objective.hip": ["-ffp-contract=off"]}
 
 
 def headers():
@@ -157,6 +160,8 @@ def train_headers():
 
 def train_source_hash():
     h = hashlib.sha256((" ".join(TRAIN_FLAGS) + "\n").encode())
+    for s in TRAIN_SOURCES:
+        h.update((s + ":" + " ".join(TRAIN_UNIT_FLAGS.get(s, [])) + "\n").encode())
     for path in [os.path.join(TRAIN_CSRC, s) for s in TRAIN_SOURCES] + train_headers():
         h.update(os.path.basename(path).encode())
         with open(path, "rb") as f:
@@ -183,7 +188,7 @@ def build_train(force=False, verbose=True):
     for s in TRAIN_SOURCES:
         obj = os.path.join(TRAIN_BUILD_DIR, s.replace(".hip", ".o"))
         objs.append(obj)
-        cmd = [hipcc] + TRAIN_FLAGS + ["-c", os.path.join(TRAIN_CSRC, s), "-o", obj]
+        cmd = [hipcc] + TRAIN_FLAGS + TRAIN_UNIT_FLAGS.get(s, []) + ["-c", os.path.join(TRAIN_CSRC, s), "-o", obj]
         if verbose:
             print("[os2d_amd.build]", " ".join(cmd), flush=True)
         procs.append((cmd, subprocess.Popen(cmd)))

@@ -14,6 +14,7 @@
 #include "../../include/os2d_train.h"
 #include "../csrc/os2d_common.h"
 #include "../csrc/sample_decode.h"
+#include "train_common.h"
 
 namespace {
 
@@ -599,6 +600,8 @@ __global__ __launch_bounds__(256) void class_resize_backward_kernel(const float*
 inline unsigned blocks(size_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
+
+void os2d_train_store_error(const char* text) { set_error("%s", text); }
 
 // ================================================================================================ C ABI
 extern "C" {

@@ -5,8 +5,11 @@
     Os2dBoxCoder.decode_pyramid                           reference box_coder.py:448-536   (os2d_detect_level for one level,
                                                                                             os2d_decode_boxes + os2d_nms otherwise)
 
-Only the inference half of the reference class is mirrored: target encoding / anchor matching / hard-negative
-remapping are training-only and out of scope.
+    Os2dBoxCoder.encode / encode_pyramid / encode_batch   reference box_coder.py:332-421   (os2d_train_assign_targets, mode 0)
+    Os2dBoxCoder.remap_anchor_targets                     reference box_coder.py:234-300   (os2d_train_assign_targets, mode 1)
+
+The target side runs as one launch per call over every (image, label, anchor); the BoxLists are packed into four arrays on
+the host once per batch.  Box transforms in the target code (hard-patch mining) are out of scope.
 """
 import collections
 import weakref
@@ -16,6 +19,7 @@ from functools import lru_cache
 import torch
 
 from .. import _lib
+from .. import _train_lib
 from ..structures.feature_map import FeatureMapSize
 from ..structures.bounding_box import BoxList, FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM
 
@@ -236,8 +240,22 @@ def feature_map_size_c4(img_size):
     return FeatureMapSize(w=f(img_size.w), h=f(img_size.h))
 
 
+class Matcher(object):
+    """torchvision's ``Matcher(high, low)`` without low-quality matches, as the kernels apply it: per column of an IoU matrix
+    [n_gt, n_det] the row of the first maximum, -1 where it is below ``low``, -2 where it is in [low, high)."""
+    BELOW_LOW_THRESHOLD, BETWEEN_THRESHOLDS = -1, -2
+
+    def __init__(self, high_threshold, low_threshold):
+        self.high_threshold, self.low_threshold = high_threshold, low_threshold
+
+    def __call__(self, ious):
+        best, index = ious.max(dim=0)
+        index = torch.where(best < self.high_threshold, torch.full_like(index, self.BETWEEN_THRESHOLDS), index)
+        return torch.where(best < self.low_threshold, torch.full_like(index, self.BELOW_LOW_THRESHOLD), index)
+
+
 class Os2dBoxCoder(object):
-    """Inference half of reference box_coder.py:169-536."""
+    """reference box_coder.py:169-536: decode + NMS for inference, encode / remap_anchor_targets for training."""
 
     def __init__(self, positive_iou_threshold=0.5, negative_iou_threshold=0.1,
                  remap_classification_targets_iou_pos=0.5, remap_classification_targets_iou_neg=0.1,
@@ -261,6 +279,8 @@ class Os2dBoxCoder(object):
             raise RuntimeError("anisotropic anchors are not supported")
         self._stride = int(g.box_stride.w)
         self._rec_field = int(g.box_size.w - self._stride * 14)
+        self.matcher = Matcher(self.positive_iou_threshold, self.negative_iou_threshold)
+        self.matcher_remap = Matcher(self.remap_classification_targets_iou_pos, self.remap_classification_targets_iou_neg)
 
     def _get_default_boxes(self, img_size):
         """reference box_coder.py:191-203 (CPU anchors as a BoxList; the kernels use the closed form)."""
@@ -652,3 +672,115 @@ class Os2dBoxCoder(object):
         if out_corners is not None:
             result.add_field("transform_corners", out_corners.view(-1, 8)[flat])
         return result
+
+    # ------------------------------------------------------------------------------------------------ training targets
+    @staticmethod
+    def _pack_boxes(batch_boxes, device):
+        """BoxLists (fields "labels", "difficult") -> gt_boxes [n,4] float32, gt_labels [n] int32, gt_difficult [n] uint8,
+        image_offsets [A+1] int32 on ``device``; assembled on the host, once per batch."""
+        boxes = [b.bbox_xyxy.detach().to("cpu", torch.float32).reshape(-1, 4) for b in batch_boxes]
+        labels = [b.get_field("labels").detach().to("cpu", torch.int32).reshape(-1) for b in batch_boxes]
+        difficult = [b.get_field("difficult").detach().to("cpu", torch.uint8).reshape(-1) if b.has_field("difficult")
+                     else torch.zeros(len(b), dtype=torch.uint8) for b in batch_boxes]
+        offsets = [0]
+        for b in boxes:
+            offsets.append(offsets[-1] + b.shape[0])
+        n = offsets[-1]
+        packed = (torch.cat(boxes).contiguous(), torch.cat(labels).contiguous(), torch.cat(difficult).contiguous(),
+                  torch.tensor(offsets, dtype=torch.int32))
+        return tuple(t.to(device, non_blocking=True) for t in packed) + (n,)
+
+    def _assign(self, mode, batch_boxes, fm, num_labels, device, loc_scores=None):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("target assignment runs on the HIP device only (no CPU fallback), got {}".format(device))
+        tl = _train_lib.load()
+        A, HW = len(batch_boxes), fm.h * fm.w
+        gt_boxes, gt_labels, gt_difficult, offsets, n = self._pack_boxes(batch_boxes, device)
+        cls_targets = torch.empty(A, num_labels, HW, dtype=torch.int64, device=device)
+        if mode == 0:
+            outs = (torch.empty(A, num_labels, 4, HW, dtype=torch.float32, device=device), None, None)
+            high, low = self.positive_iou_threshold, self.negative_iou_threshold
+        else:
+            outs = (None, torch.empty(A, num_labels, HW, dtype=torch.float32, device=device),
+                    torch.empty(A, num_labels, HW, dtype=torch.float32, device=device))
+            high, low = self.remap_classification_targets_iou_pos, self.remap_classification_targets_iou_neg
+        with torch.cuda.device(device):
+            _train_lib.check(tl.os2d_train_assign_targets(
+                mode, _lib.ptr(gt_boxes) if n else None, _lib.ptr(gt_labels) if n else None, _lib.ptr(gt_difficult) if n else None,
+                _lib.ptr(offsets), n, _lib.ptr(loc_scores), A, num_labels, fm.h, fm.w, self._stride, self._rec_field,
+                ctypes.c_float(high), ctypes.c_float(low), _lib.ptr(outs[0]), _lib.ptr(cls_targets), _lib.ptr(outs[1]),
+                _lib.ptr(outs[2]), _lib.current_stream(device)), "os2d_train_assign_targets")
+        return cls_targets, outs
+
+    def encode_batch(self, batch_boxes, img_size, num_labels, device):
+        """``encode`` of every image of a batch in ONE launch: -> loc_targets [A,num_labels,4,HW] float32, cls_targets
+        [A,num_labels,HW] int64 on ``device`` (what the reference's data loader stacks from per-image ``encode`` calls)."""
+        cls_targets, outs = self._assign(0, batch_boxes, self.get_feature_map_size(img_size), num_labels, device)
+        return outs[0], cls_targets
+
+    def encode(self, boxes, img_size, num_labels, default_box_transform=None):
+        """reference box_coder.py:332-389: -> loc_targets [num_labels,4,HW] float32, cls_targets [num_labels,HW] int64 (1
+        positive, 0 negative, -1 ignored), on the HIP device (that of ``boxes`` when it is there already)."""
+        if default_box_transform is not None:
+            raise NotImplementedError("default_box_transform is not supported (hard-patch mining is out of scope)")
+        dev = boxes.bbox_xyxy.device if boxes.bbox_xyxy.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        loc_targets, cls_targets = self.encode_batch([boxes], img_size, num_labels, dev)
+        return loc_targets[0], cls_targets[0]
+
+    def encode_pyramid(self, boxes, img_size_pyramid, num_labels, default_box_transform_pyramid=None):
+        """reference box_coder.py:391-421: ``encode`` per pyramid level -> (list of loc_targets, list of cls_targets)."""
+        if default_box_transform_pyramid is not None and any(t is not None for t in default_box_transform_pyramid):
+            raise NotImplementedError("default_box_transform_pyramid is not supported (hard-patch mining is out of scope)")
+        levels = [self.encode(boxes, img_size, num_labels) for img_size in img_size_pyramid]
+        return [l[0] for l in levels], [l[1] for l in levels]
+
+    def remap_anchor_targets(self, loc_scores, batch_img_size, class_image_sizes, batch_boxes, box_reverse_transform=None):
+        """reference box_coder.py:234-300: the targets after the model's localisation.  loc_scores [A,B,4,HW] on the HIP
+        device -> cls_targets_remapped [A,B,HW] int64, ious_anchor, ious_anchor_corrected [A,B,HW] float32.  One launch,
+        no host synchronisation.  The images of a batch share one size (they are one tensor)."""
+        if box_reverse_transform is not None:
+            raise NotImplementedError("box_reverse_transform is not supported (hard-patch mining is out of scope)")
+        if not (loc_scores.is_cuda and loc_scores.dtype == torch.float32):
+            raise RuntimeError("remap_anchor_targets runs on the HIP device only (no CPU fallback)")
+        A, B = loc_scores.shape[0], loc_scores.shape[1]
+        if len(batch_boxes) != A or len(batch_img_size) != A:
+            raise ValueError("batch_boxes / batch_img_size must have one entry per image ({})".format(A))
+        fm = self.get_feature_map_size(batch_img_size[0])
+        if any(self.get_feature_map_size(s) != fm for s in batch_img_size[1:]) or fm.h * fm.w != loc_scores.shape[3]:
+            raise ValueError("the images of a batch must share one feature map size that matches loc_scores")
+        cls_targets, outs = self._assign(1, batch_boxes, fm, B, loc_scores.device, loc_scores.detach().contiguous())
+        return cls_targets, outs[1], outs[2]
+
+    @staticmethod
+    def build_loc_targets(class_boxes, default_boxes):
+        """reference box_coder.py:302-317 on two BoxLists of equal length (clip_to_min_size(1), then encode_boxes with
+        weights (10, 10, 5, 5)): the reference's public helper.  ``encode`` does not come here - the kernel encodes against
+        the closed-form anchors."""
+        def clipped(b):
+            b = b.bbox_xyxy
+            x2 = torch.where(b[:, 0] + 1 > b[:, 2], b[:, 0] + 1, b[:, 2])
+            y2 = torch.where(b[:, 1] + 1 > b[:, 3], b[:, 1] + 1, b[:, 3])
+            return b[:, 0], b[:, 1], x2, y2
+        gx1, gy1, gx2, gy2 = clipped(class_boxes)
+        px1, py1, px2, py2 = clipped(default_boxes)
+        ew, eh, gw, gh = px2 - px1, py2 - py1, gx2 - gx1, gy2 - gy1
+        wx, wy, ww, wh = BOX_ENCODING_WEIGHTS
+        return torch.stack([wx * ((gx1 + 0.5 * gw) - (px1 + 0.5 * ew)) / ew, wy * ((gy1 + 0.5 * gh) - (py1 + 0.5 * eh)) / eh,
+                            ww * torch.log(gw / ew), wh * torch.log(gh / eh)], dim=1)
+
+    @staticmethod
+    def assign_anchors_to_boxes_threshold(detection_boxes, annotation_boxes, matcher):
+        """reference box_coder.py:212-232 for arbitrary detection boxes: -> (index [n_det] of the matched annotation box, -1
+        below the low threshold, -2 between the thresholds or matched to a difficult box; ious [n_gt, n_det]).  The
+        reference's public helper; the kernels match against the closed-form anchors and do not come here."""
+        a, d = annotation_boxes.bbox_xyxy, detection_boxes.bbox_xyxy
+        wh = (torch.min(a[:, None, 2:], d[None, :, 2:]) - torch.max(a[:, None, :2], d[None, :, :2])).clamp(min=0)
+        inter = wh[..., 0] * wh[..., 1]
+        area_a, area_d = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1]), (d[:, 2] - d[:, 0]) * (d[:, 3] - d[:, 1])
+        ious = inter / (area_a[:, None] + area_d[None, :] - inter)
+        index = matcher(ious)
+        difficult = annotation_boxes.get_field("difficult").to(torch.bool)
+        hit = index >= 0
+        index = torch.where(hit & difficult[index.clamp(min=0)], torch.full_like(index, -2), index)
+        return index, ious

@@ -120,7 +120,8 @@ class Os2dModel(nn.Module):
             forward(feature_maps=..., class_head=...)         (evaluation: pre-extracted features + prebuilt head)
         Returns (loc [A,B,4,HW], cls [A,B,HW], cls_detached [A,B,HW], FeatureMapSize, corners [A,B,8,HW])."""
         if train_mode:
-            raise RuntimeError("train_mode=True: training through the HIP head is out of scope (inference only)")
+            raise RuntimeError("train_mode=True: training through Os2dModel.forward is out of scope (inference only); "
+                               "os2d_amd.engine.train.forward_train is the training forward")
         # what is missing is computed from what was given; the messages are the reference's (callers match on them)
         need_features, need_head = feature_maps is None, class_head is None
         assert not need_features or images is not None, "If feature_maps is None than images cannot be None"
