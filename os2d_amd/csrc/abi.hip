@@ -4,6 +4,7 @@
 
 #include "../../include/os2d_hip.h"
 #include "os2d_common.h"
+#include "detect_common.h"
 #include <atomic>
 #include <mutex>
 #include <random>

@@ -17,7 +17,7 @@
 // is written to global memory inside the loop, so the serial chain of a class has no memory latency in it; the
 // survivors are written out by all threads at the end.
 // Outputs are compacted per class in decreasing-score order: out_boxes/out_scores/out_index[c][0 .. out_count[c]).
-#include "os2d_common.h"
+#include "detect_common.h"
 
 namespace {
 
@@ -61,9 +61,7 @@ __global__ __launch_bounds__(NTHR) void detect_level_kernel(const float* __restr
       const float s = sc[i];
       const bool empty = (b.w <= b.y) || (b.z <= b.x);
       if (s > score_thr && !empty) {
-        unsigned int u = (s == 0.f) ? 0u : __float_as_uint(s);  // -0 and +0 tie in a comparison sort
-        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);        // monotone map float -> uint (ascending)
-        key = ~u;                                              // ascending key = descending score
+        key = os2d_score_key(s);
         ++mine;
       }
     }
@@ -74,53 +72,8 @@ __global__ __launch_bounds__(NTHR) void detect_level_kernel(const float* __restr
   __syncthreads();
   const int n = n_valid;
 
-  // ---- 2. bitonic sort (ascending in (key, location)).  Stage k = 2^m needs the levels j = 2^(m-1) .. 1; they are
-  // taken NB <= 3 at a time: a thread owns the 2^NB elements whose indices differ in bits lo .. lo+NB-1.
-#define DET_SORT_CHUNK(NB)                                                                                        \
-  {                                                                                                               \
-    const int groups_ = NP2 >> (NB);                                                                              \
-    for (int g_ = tid; g_ < groups_; g_ += NTHR) {                                                                \
-      const int base_ = ((g_ >> lo) << (lo + (NB))) | (g_ & ((1 << lo) - 1));                                     \
-      const bool up_ = (base_ & k) == 0;                                                                          \
-      unsigned int kk_[1 << (NB)];                                                                                \
-      unsigned short ii_[1 << (NB)];                                                                              \
-      _Pragma("unroll") for (int e = 0; e < (1 << (NB)); ++e) {                                                   \
-        kk_[e] = skey[base_ | (e << lo)];                                                                         \
-        ii_[e] = sidx[base_ | (e << lo)];                                                                         \
-      }                                                                                                           \
-      _Pragma("unroll") for (int b = (NB)-1; b >= 0; --b) {                                                       \
-        _Pragma("unroll") for (int e = 0; e < (1 << (NB)); ++e) {                                                 \
-          if ((e >> b) & 1) continue;                                                                             \
-          const int f = e | (1 << b);                                                                             \
-          const bool gt_ = kk_[e] > kk_[f] || (kk_[e] == kk_[f] && ii_[e] > ii_[f]);                              \
-          if (gt_ == up_) {                                                                                       \
-            const unsigned int tk_ = kk_[e];                                                                      \
-            kk_[e] = kk_[f];                                                                                      \
-            kk_[f] = tk_;                                                                                         \
-            const unsigned short ti_ = ii_[e];                                                                    \
-            ii_[e] = ii_[f];                                                                                      \
-            ii_[f] = ti_;                                                                                         \
-          }                                                                                                       \
-        }                                                                                                         \
-      }                                                                                                           \
-      _Pragma("unroll") for (int e = 0; e < (1 << (NB)); ++e) {                                                   \
-        skey[base_ | (e << lo)] = kk_[e];                                                                         \
-        sidx[base_ | (e << lo)] = ii_[e];                                                                         \
-      }                                                                                                           \
-    }                                                                                                             \
-    __syncthreads();                                                                                              \
-  }
-  for (int m = 1; (1 << m) <= NP2; ++m) {
-    const int k = 1 << m;
-    for (int hi = m - 1; hi >= 0; hi -= 3) {  // levels hi .. max(hi-2, 0)
-      const int nb = min(3, hi + 1);
-      const int lo = hi - nb + 1;
-      if (nb == 3) DET_SORT_CHUNK(3)
-      else if (nb == 2) DET_SORT_CHUNK(2)
-      else DET_SORT_CHUNK(1)
-    }
-  }
-#undef DET_SORT_CHUNK
+  // ---- 2. bitonic sort (ascending in (key, location))
+  os2d_bitonic_sort<NTHR>(skey, sidx, NP2, tid);
 
   // ---- 3. boxes in sorted order, mapped to the output image (the level's chain of BoxList.resize / transpose / crop)
   for (int jx = tid; jx < n; jx += NTHR) {
@@ -155,19 +108,7 @@ __global__ __launch_bounds__(NTHR) void detect_level_kernel(const float* __restr
       unsigned int dead = valid ? 0u : 1u;
 #pragma unroll
       for (int w = 0; w < NWAVE; ++w) dead |= vote[w][lane];
-      u64 alive = ~__ballot(dead != 0u);
-      u64 kbits = 0ull;
-      while (alive) {
-        const int i = __builtin_ctzll(alive);  // best-scoring candidate still alive: kept
-        kbits |= 1ull << i;
-        float4 kb;
-        kb.x = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, me.x), i));
-        kb.y = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, me.y), i));
-        kb.z = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, me.z), i));
-        kb.w = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, me.w), i));
-        const bool hit = os2d_iou_gt(kb, os2d_box_area(kb), me, my_area, iou_thr);
-        alive &= ~(__ballot(hit) | ((2ull << i) - 1ull));  // drop lanes 0..i and everything the new box suppresses
-      }
+      const u64 kbits = os2d_nms_resolve(me, my_area, ~__ballot(dead != 0u), iou_thr);
       if ((kbits >> lane) & 1ull) {
         const int slot = nk + __popcll(kbits & ((1ull << lane) - 1ull));
         if (slot < kcap) kbox[slot] = me;
@@ -190,19 +131,13 @@ __global__ __launch_bounds__(NTHR) void detect_level_kernel(const float* __restr
   if (tid == 0) out_count[c] = nkept;
 }
 
-int next_pow2(int v) {
-  int p = 8;  // >= 8 keeps the LDS sub-arrays 16-byte aligned
-  while (p < v) p <<= 1;
-  return p;
-}
-
 }  // namespace
 
 // dynamic LDS of one class at this level (0 if the level is too large for the fused kernel)
 size_t os2d_detect_level_lds_bytes(int H, int W) {
   const long long HW = (long long)H * W;
   if (H < 1 || W < 1 || HW >= 65536) return 0;
-  const size_t np2 = (size_t)next_pow2((int)HW);
+  const size_t np2 = (size_t)os2d_next_pow2((int)HW);
   const size_t bytes = np2 * 6 + (((size_t)HW * 2 + 15) & ~(size_t)15) + (size_t)HW * 16;
   return bytes + 4608 <= 160 * 1024 ? bytes : 0;  // 4.5 KB: static arrays of the kernel
 }
@@ -223,7 +158,7 @@ int os2d_launch_detect_level(const float* loc, const float* cls, int B, int H, i
   }
   const float half_box = 0.5f * (float)(stride * (OS2D_T - 1) + rec_field);
   hipLaunchKernelGGL(detect_level_kernel, dim3(B), dim3(NTHR), lds, stream, loc, cls, H, W, (float)stride, half_box, img_w,
-                     img_h, ops, score_thr, iou_thr, next_pow2(H * W), reinterpret_cast<float4*>(out_boxes),
+                     img_h, ops, score_thr, iou_thr, os2d_next_pow2(H * W), reinterpret_cast<float4*>(out_boxes),
                      out_scores, out_index, out_count);
   e = hipGetLastError();
   if (e != hipSuccess) {

@@ -29,7 +29,7 @@
 // 483-487 merges rows with the same class id before NMS): a label's candidate list is its rows in row order, each row level
 // by level.  The kernels work on G labels x V slots: slot_rows[g * V + v] names the head row of view v of label g (-1: none),
 // candidate j of label g = (slot j / N, location j % N); everything after pyr_decode just sees G "classes" of V * N candidates.
-#include "os2d_common.h"
+#include "detect_common.h"
 #include "../../include/os2d_hip.h"
 
 namespace {
@@ -41,7 +41,7 @@ constexpr int MAX_LEVELS = OS2D_PYRAMID_MAX_LEVELS;
 constexpr int MAX_CHUNKS = 64;      // chunks per class and pass that the count tables hold
 constexpr int KCAP = 2048;          // kept boxes cached in LDS (32 KB); later ones are re-read through the id lists
 
-struct DefaultOpsTable {        // per level: the chain the anchors ("default_boxes") go through (os2d_common.h)
+struct DefaultOpsTable {        // per level: the chain the anchors ("default_boxes") go through (detect_common.h)
   Os2dDefaultBoxOps ops[OS2D_PYRAMID_MAX_LEVELS];
 };
 
@@ -54,12 +54,6 @@ struct LevelTable {
   Os2dBoxOps ops[MAX_LEVELS];    // level -> output image
   int L;
 };
-
-__device__ __forceinline__ unsigned int score_key(float s) {
-  unsigned int u = (s == 0.f) ? 0u : __float_as_uint(s);  // -0 and +0 tie in a comparison sort
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);        // monotone map float -> uint (ascending)
-  return ~u;                                             // ascending key = descending score
-}
 
 // ---- 1a. candidates: decode, clip, validity, map to the output image (one thread per candidate)
 __global__ __launch_bounds__(256) void pyr_decode_kernel(LevelTable T, int N, float stride, float half_box, float score_thr,
@@ -84,7 +78,7 @@ __global__ __launch_bounds__(256) void pyr_decode_kernel(LevelTable T, int N, fl
   bx = os2d_apply_box_ops(bx, T.ops[l]);
   boxes[(size_t)slot * N + g] = bx;
   scores[(size_t)slot * N + g] = s;
-  keys[(size_t)slot * N + g] = valid ? score_key(s) : 0xffffffffu;   // a valid key is never 0xffffffff (that would be score -NaN)
+  keys[(size_t)slot * N + g] = valid ? os2d_score_key(s) : 0xffffffffu;   // a valid key is never 0xffffffff (that would be score -NaN)
 }
 
 // ---- 1b. the valid candidates of a class, compacted in list order (ballot + prefix, NTHR candidates per round)
@@ -196,51 +190,7 @@ __global__ __launch_bounds__(NTHR) void pyr_chunk_nms_kernel(int pass, int N, in
   __syncthreads();
 
   // ---- bitonic sort, ascending in (key, position): decreasing score, ties in list order (a STABLE descending sort)
-#define PYR_SORT_CHUNK(NB)                                                                                        \
-  {                                                                                                               \
-    const int groups_ = NP2 >> (NB);                                                                              \
-    for (int g_ = tid; g_ < groups_; g_ += NTHR) {                                                                \
-      const int base_ = ((g_ >> lo) << (lo + (NB))) | (g_ & ((1 << lo) - 1));                                     \
-      const bool up_ = (base_ & k) == 0;                                                                          \
-      unsigned int kk_[1 << (NB)];                                                                                \
-      unsigned short ii_[1 << (NB)];                                                                              \
-      _Pragma("unroll") for (int e = 0; e < (1 << (NB)); ++e) {                                                   \
-        kk_[e] = skey[base_ | (e << lo)];                                                                         \
-        ii_[e] = spos[base_ | (e << lo)];                                                                         \
-      }                                                                                                           \
-      _Pragma("unroll") for (int bb = (NB)-1; bb >= 0; --bb) {                                                    \
-        _Pragma("unroll") for (int e = 0; e < (1 << (NB)); ++e) {                                                 \
-          if ((e >> bb) & 1) continue;                                                                            \
-          const int f = e | (1 << bb);                                                                            \
-          const bool gt_ = kk_[e] > kk_[f] || (kk_[e] == kk_[f] && ii_[e] > ii_[f]);                              \
-          if (gt_ == up_) {                                                                                       \
-            const unsigned int tk_ = kk_[e];                                                                      \
-            kk_[e] = kk_[f];                                                                                      \
-            kk_[f] = tk_;                                                                                         \
-            const unsigned short ti_ = ii_[e];                                                                    \
-            ii_[e] = ii_[f];                                                                                      \
-            ii_[f] = ti_;                                                                                         \
-          }                                                                                                       \
-        }                                                                                                         \
-      }                                                                                                           \
-      _Pragma("unroll") for (int e = 0; e < (1 << (NB)); ++e) {                                                   \
-        skey[base_ | (e << lo)] = kk_[e];                                                                         \
-        spos[base_ | (e << lo)] = ii_[e];                                                                         \
-      }                                                                                                           \
-    }                                                                                                             \
-    __syncthreads();                                                                                              \
-  }
-  for (int m = 1; (1 << m) <= NP2; ++m) {
-    const int k = 1 << m;
-    for (int hi = m - 1; hi >= 0; hi -= 3) {
-      const int nbits = min(3, hi + 1);
-      const int lo = hi - nbits + 1;
-      if (nbits == 3) PYR_SORT_CHUNK(3)
-      else if (nbits == 2) PYR_SORT_CHUNK(2)
-      else PYR_SORT_CHUNK(1)
-    }
-  }
-#undef PYR_SORT_CHUNK
+  os2d_bitonic_sort<NTHR>(skey, spos, NP2, tid);
 
   // ---- candidate ids in sorted order (global scratch: read back 64 at a time by the NMS loop)
   for (int i = tid; i < n; i += NTHR) srt[i] = list_at(in, cnt_in, M, j0 + spos[i]);
@@ -312,19 +262,7 @@ __global__ __launch_bounds__(NTHR) void pyr_chunk_nms_kernel(int pass, int N, in
           unsigned int dd = valid ? 0u : 1u;
 #pragma unroll
           for (int w = 0; w < NWAVE; ++w) dd |= vote[w][lane];
-          u64 alive = ~__ballot(dd != 0u);
-          u64 kbits = 0ull;
-          while (alive) {
-            const int i = __builtin_ctzll(alive);
-            kbits |= 1ull << i;
-            float4 kbx;
-            kbx.x = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cand.x), i));
-            kbx.y = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cand.y), i));
-            kbx.z = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cand.z), i));
-            kbx.w = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cand.w), i));
-            const bool hit = os2d_iou_gt(kbx, os2d_box_area(kbx), cand, cand_area, iou_thr);
-            alive &= ~(__ballot(hit) | ((2ull << i) - 1ull));
-          }
+          const u64 kbits = os2d_nms_resolve(cand, cand_area, ~__ballot(dd != 0u), iou_thr);
           if ((kbits >> lane) & 1ull) {
             const int slot = nk + __popcll(kbits & ((1ull << lane) - 1ull));
             if (slot < KCAP) kbox[slot] = cand;
@@ -402,25 +340,7 @@ __global__ __launch_bounds__(NTHR) void pyr_finalize_kernel(int passes, int N, i
       spos[i] = (unsigned short)i;
     }
     __syncthreads();
-    for (int k = 2; k <= NP2; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int i = tid; i < NP2; i += NTHR) {
-          const int p = i ^ j;
-          if (p > i) {
-            const bool up = (i & k) == 0;
-            const unsigned int ka = skey[i], kb2 = skey[p];
-            const unsigned short pa = spos[i], pb = spos[p];
-            const bool gt = ka > kb2 || (ka == kb2 && pa > pb);
-            if (gt == up) {
-              skey[i] = kb2;
-              skey[p] = ka;
-              spos[i] = pb;
-              spos[p] = pa;
-            }
-          }
-        }
-        __syncthreads();
-      }
+    os2d_bitonic_sort<NTHR>(skey, spos, NP2, tid);
   }
   for (int s = tid; s < total; s += NTHR) {
     const int g = list_at(ids, cnt_fin, M, need_sort ? (int)spos[s] : s);
@@ -450,12 +370,6 @@ __global__ __launch_bounds__(NTHR) void pyr_finalize_kernel(int passes, int N, i
     }
   }
   if (tid == 0) out_count[b] = total;
-}
-
-int next_pow2(int v) {
-  int p = 8;
-  while (p < v) p <<= 1;
-  return p;
 }
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -590,7 +504,7 @@ static int detect_pyramid_impl(const float* const* loc, const float* const* cls,
   if (rc) return rc;
   hipLaunchKernelGGL(pyr_compact_kernel, dim3(G), dim3(NTHR), 0, st, N, M, keys, ids[0], counts, final_pass);
   if ((rc = check("pyr_compact"))) return rc;
-  const int NP2 = next_pow2(min(M, N));
+  const int NP2 = os2d_next_pow2(min(M, N));
   const size_t lds = (size_t)NP2 * 6 + (((size_t)M * 2 + 15) & ~(size_t)15) + (size_t)KCAP * 16;
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(pyr_chunk_nms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e == hipSuccess)

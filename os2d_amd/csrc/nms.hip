@@ -11,7 +11,7 @@
 //            candidate overlapping it dies (one 64-lane IoU test per box kept in this step), and so on,
 //   phase 3  survivors are appended to the kept list.
 // Work ~ N * kept / 256 IoU tests per class instead of N^2 / 2, and nothing but the kept list (<= N boxes) is stored.
-#include "os2d_common.h"
+#include "detect_common.h"
 
 namespace {
 
@@ -63,19 +63,8 @@ __global__ __launch_bounds__(256) void nms_kernel(const float4* __restrict__ box
     // ---- phase 2: in-order resolve, wave 0
     if (wv == 0) {
       const bool pre_dead = (dead[0][lane] | dead[1][lane] | dead[2][lane] | dead[3][lane]) != 0 || !valid;
-      unsigned long long alive = ~__ballot(pre_dead);  // candidates not killed by the kept list
-      unsigned long long kbits = 0ull;
-      while (alive) {
-        const int i = __builtin_ctzll(alive);  // best-scoring candidate still alive: kept
-        kbits |= 1ull << i;
-        float4 kb;
-        kb.x = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, me.x), i));
-        kb.y = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, me.y), i));
-        kb.z = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, me.z), i));
-        kb.w = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, me.w), i));
-        const bool hit = os2d_iou_gt(kb, os2d_box_area(kb), me, my_area, thr);
-        alive &= ~(__ballot(hit) | ((2ull << i) - 1ull));  // drop lanes 0..i and everything the new box suppresses
-      }
+      const unsigned long long alive = ~__ballot(pre_dead);  // candidates not killed by the kept list
+      const unsigned long long kbits = os2d_nms_resolve(me, my_area, alive, thr);
       const bool k = (kbits >> lane) & 1ull;
       if (valid) kp[idx] = k ? 1 : 0;
       // ---- phase 3: append survivors in order

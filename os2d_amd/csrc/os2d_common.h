@@ -110,141 +110,6 @@ static inline __host__ __device__ bool os2d_interior(int n, int H, int W) {
   return r >= 0 && r < H * os2d_ws(W) && (r % os2d_ws(W)) < W;
 }
 
-// Box decode of ONE location (reference os2d/modeling/box_coder.py:319-330 = torchvision BoxCoder.decode_single with
-// weights (10,10,5,5) and the dw/dh clamp log(1000/16), then clip_boxes_to_image): shared by decode_boxes_kernel and
-// detect_level_kernel so both produce bit-identical boxes.  ``l`` points at loc[nb][0][n]; channel stride HW.
-__device__ __forceinline__ float4 os2d_decode_box(const float* __restrict__ l, int HW, int n, int W, float stride,
-                                                  float half_box, float img_w, float img_h) {
-  const int h = n / W, w = n - h * W;
-  const float ecx = stride * ((float)w + 0.5f), ecy = stride * ((float)h + 0.5f);
-  const float ax1 = ecx - half_box, ay1 = ecy - half_box;
-  const float aw = (ecx + half_box) - ax1, ah = (ecy + half_box) - ay1;
-  const float acx = ax1 + 0.5f * aw, acy = ay1 + 0.5f * ah;
-  const float clipv = 4.135166556742356f;  // log(1000/16): torchvision BoxCoder.bbox_xform_clip
-  const float dx = l[0] / 10.0f, dy = l[HW] / 10.0f;
-  const float dw = fminf(l[2 * (size_t)HW] / 5.0f, clipv), dh = fminf(l[3 * (size_t)HW] / 5.0f, clipv);
-  const float pcx = dx * aw + acx, pcy = dy * ah + acy;
-  const float pw = expf(dw) * aw, ph = expf(dh) * ah;
-  float4 o = make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph);
-  if (img_w > 0.f && img_h > 0.f) {  // clip_boxes_to_image; a non-positive size means "leave unclipped"
-    o.x = fminf(fmaxf(o.x, 0.f), img_w);
-    o.y = fminf(fmaxf(o.y, 0.f), img_h);
-    o.z = fminf(fmaxf(o.z, 0.f), img_w);
-    o.w = fminf(fmaxf(o.w, 0.f), img_h);
-  }
-  return o;
-}
-
-// Chain of axis-aligned box transforms that maps a level's boxes into the output image: what the reference's per-level
-// ``TransformList`` of closures amounts to (os2d/structures/transforms.py:12-27, built by os2d/data/dataloader.py:286-336 from
-// BoxList.resize / transpose / crop, os2d/structures/bounding_box.py:138-226), applied op by op with the reference's
-// roundings - every product / difference rounded on its own (no contraction into fused multiply-adds), so the fused decode
-// equals the generic chain (which calls the closures on a BoxList) bit for bit.  Kinds: OS2D_BOX_OP_* of include/os2d_hip.h.
-#define OS2D_BOX_MAX_OPS 6
-#define OS2D_BOX_MAX_DEFAULT_OPS 12
-template <int N>
-struct Os2dBoxOpsN {
-  int n;
-  unsigned char kind[N];
-  float ax[N], ay[N];
-};
-typedef Os2dBoxOpsN<OS2D_BOX_MAX_OPS> Os2dBoxOps;
-// the anchors ("default_boxes") go through a chain of their own: in the reference they ride along as a BoxList FIELD of the
-// boxes - BoxList.transpose / crop also transform such fields, resize does not (bounding_box.py:162,196-199,222-225) - and the
-// level's transform is then applied to the field once more (box_coder.py:515-516); the caller records that whole sequence
-typedef Os2dBoxOpsN<OS2D_BOX_MAX_DEFAULT_OPS> Os2dDefaultBoxOps;
-template <int N>
-__device__ __forceinline__ float4 os2d_apply_box_ops(float4 b, const Os2dBoxOpsN<N>& t) {
-#pragma clang fp contract(off)
-  for (int k = 0; k < t.n; ++k) {
-    const float ax = t.ax[k], ay = t.ay[k];
-    switch (t.kind[k]) {
-      case 1:   // SCALE: BoxList.resize
-        b.x = b.x * ax;
-        b.y = b.y * ay;
-        b.z = b.z * ax;
-        b.w = b.w * ay;
-        break;
-      case 2: { // HFLIP about the image width ax: (xmin, xmax) = (W - xmax, W - xmin)
-        const float lo = ax - b.z, hi = ax - b.x;
-        b.x = lo;
-        b.z = hi;
-        break;
-      }
-      case 3: { // VFLIP about the image height ay
-        const float lo = ay - b.w, hi = ay - b.y;
-        b.y = lo;
-        b.w = hi;
-        break;
-      }
-      case 4:   // SHIFT: BoxList.crop (x - left, y - top)
-        b.x = b.x - ax;
-        b.y = b.y - ay;
-        b.z = b.z - ax;
-        b.w = b.w - ay;
-        break;
-      default:
-        break;
-    }
-  }
-  return b;
-}
-template <int N>
-static inline Os2dBoxOpsN<N> os2d_box_ops_scale(float sx, float sy) {
-  Os2dBoxOpsN<N> t = {};
-  t.n = 1;
-  t.kind[0] = 1;
-  t.ax[0] = sx;
-  t.ay[0] = sy;
-  return t;
-}
-// ops from the ABI arrays (kinds [nops], args [nops][2]); false on a bad chain
-template <int N>
-static inline bool os2d_box_ops_from(const int* kinds, const float* args, int nops, Os2dBoxOpsN<N>* t) {
-  *t = Os2dBoxOpsN<N>{};
-  if (nops < 0 || nops > N || (nops > 0 && (!kinds || !args))) return false;
-  t->n = nops;
-  for (int k = 0; k < nops; ++k) {
-    if (kinds[k] < 1 || kinds[k] > 4) return false;
-    t->kind[k] = (unsigned char)kinds[k];
-    t->ax[k] = args[2 * k];
-    t->ay[k] = args[2 * k + 1];
-  }
-  return true;
-}
-
-// IoU(a, b) > thr with torchvision's arithmetic (inter / (area_a + area_b - inter) in fp32, reference
-// os2d/structures/bounding_box.py:367 -> torchvision.ops.nms).  The IEEE division (a dozen VALU instructions) is only
-// executed when some lane of the wave is within 1e-5 (relative) of the threshold - everywhere else comparing inter with
-// thr * union gives the same answer as the rounded quotient.  The vote makes the branch wave-uniform, so it is a real
-// branch and not an if-converted select.
-// Every product and sum below is rounded on its own, like the reference's tensor expressions: the compiler must NOT contract
-// them into fused multiply-adds (hipcc's default for device code is -ffp-contract=fast, and HIP's __fmul_rn / __fadd_rn are
-// plain operators that it fuses just the same: area_a + area_b - w * h became two v_fma_f32).  Whether it did depended on
-// unrelated code generation choices - the decisions at the threshold flipped when the library was first built without
-// packed-FP32 instructions (tests/test_decode_gpu.py::test_nms_decisions_at_the_iou_threshold).
-__device__ __forceinline__ float os2d_box_area(float4 b) {
-#pragma clang fp contract(off)
-  const float bw = b.z - b.x, bh = b.w - b.y;
-  return bw * bh;
-}
-
-__device__ __forceinline__ bool os2d_iou_gt(float4 a, float area_a, float4 b, float area_b, float thr) {
-#pragma clang fp contract(off)
-  const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f);
-  const float h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
-  const float inter = w * h;
-  const float sum = area_a + area_b;
-  const float uni = sum - inter;
-  const float tu = thr * uni;
-  bool res = inter > tu;
-  const bool near = !(uni > 0.f && fabsf(inter - tu) > 1e-5f * fabsf(tu));
-  if (__builtin_amdgcn_ballot_w64(near) != 0ull) {
-    if (near) res = inter / uni > thr;
-  }
-  return res;
-}
-
 // error plumbing (abi.hip)
 void os2d_set_error(const char* fmt, ...);
 
@@ -296,11 +161,6 @@ int os2d_launch_alignment_grids(const float* params, int NB, int H, int W, int P
 // nms.hip
 int os2d_launch_nms(const float* boxes, const int* counts, int NC, int N, float thr, unsigned char* keep, int* num_keep,
                     void* workspace, hipStream_t stream);
-// detect.hip
-size_t os2d_detect_level_lds_bytes(int H, int W);
-int os2d_launch_detect_level(const float* loc, const float* cls, int B, int H, int W, int stride, int rec_field,
-                             float img_w, float img_h, const Os2dBoxOps& ops, float score_thr, float iou_thr,
-                             float* out_boxes, float* out_scores, int* out_index, int* out_count, hipStream_t stream);
 // fft.hip
 int os2d_fft_plan(int H, int W, int* P, int* Q, int* nbins, int* tiles /* [6]: TY, TX, TH, TW, window rows, window columns */);
 int os2d_launch_fft_forward(const float* corr, const float* inv, float* X, const float* twQ, const float* twP, int NB, int C,

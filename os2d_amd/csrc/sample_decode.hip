@@ -15,6 +15,7 @@
 // fall in the same or adjacent cache lines of one correlation channel (the transforms vary smoothly), so
 // each of the 121x4 gathers is a near-coalesced L2 read of the 4.3 MB per-class correlation block.
 #include "os2d_common.h"
+#include "detect_common.h"
 #include "sample_decode.h"
 
 namespace {

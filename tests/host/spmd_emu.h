@@ -1,4 +1,5 @@
-// Host-side SPMD emulator for the work-group kernels of os2d_amd/csrc/dft_mfma.h: every work item of a work-group is an OS
+// Host-side SPMD emulator for the work-group kernels of os2d_amd/csrc/dft_mfma.h and the shared device functions of
+// os2d_amd/csrc/detect_common.h (tests/test_detect_host.py): every work item of a work-group is an OS
 // thread, LDS is a per-group buffer, the work-group barrier is a pthread barrier, and the wave-level instructions the kernels
 // use (v_mfma_f32_32x32x16_f16, cross-lane shuffles) are emulated by exchanging operands through a per-wave scratch area
 // between two wave barriers.  The kernel source is compiled UNCHANGED (clang++ as a host compiler: ext_vector_type and
@@ -105,6 +106,16 @@ inline unsigned long long ballot(bool p) {
   for (int k = 0; k < WAVE; ++k) m |= (unsigned long long)(w.i[k] != 0) << k;
   wave_barrier();
   return m;
+}
+
+// v_readlane_b32: the value lane `lane` holds (the same `lane` in every work item of the wave)
+inline int readlane(int v, int lane) {
+  WaveScratch& w = wave();
+  w.i[ctx.tid % WAVE] = v;
+  wave_barrier();
+  const int r = w.i[lane];
+  wave_barrier();
+  return r;
 }
 
 // run `body` as a grid of `grid` work-groups of `nthreads` work items with `lds_bytes` of LDS (groups one after the other)
