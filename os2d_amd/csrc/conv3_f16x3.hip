@@ -10,7 +10,7 @@
 // cells of one map: per channel group the input slab (256 + 2 x (2 rows + 2) halo cells, hi and lo) and the group's weights
 // (28 x 2 x 16 units) arrive by LDS-DMA into the other half of a double buffer while the current group is multiplied.
 // Every output element accumulates its products in ONE order whatever the batch size (one kernel shape for all).
-// Maps wider than OS2D_MAX_W_LINEAR5 run in column strips (SP > 0: the strip-plane geometry of conv_f16x3.hip).
+// Maps wider than OS2D_MAX_W_LINEAR5 run in column strips (SP > 0: the strip-plane geometry of tile_common.h).
 //
 // FUSE (round 6): the layer's P outputs of a location are all the alignment epilogue needs for that location
 // (sample_decode.h: theta, resample + pool, box, corners, loc) - so the head's launch does that epilogue right here: the accumulators
@@ -18,14 +18,10 @@
 // os2d_sample_decode_location for its cell.  The parameters never touch HBM, one launch and one dependent-launch gap (~11 us per
 // step at 64 classes) less, and the gather-bound epilogue of one work-group overlaps the load-bound matrix phase of its neighbours
 // on the CU.  The standalone kernels remain for the per-stage entry points (os2d_transform_conv_f16x3, os2d_sample_decode).
-#include "os2d_common.h"
+#include "tile_common.h"
 #include "sample_decode.h"
 
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int C3_THR = 256;
 constexpr int C3_NT = 256;          // plane cells per work-group (64 per wave = 4 blocks of 16)
@@ -60,24 +56,21 @@ __global__ __launch_bounds__(C3_THR, C3_BUFS == 1 ? (FUSE ? OS2D_C3_FUSE_GROUPS 
     const u32x4* in, const u32x4* wp, const float* __restrict__ bp, float* __restrict__ out, int P, int H, int W, int PLANE, int TILES, int NB,
     int SP /*0: linear; else row pitch of a strip-plane*/, int TPS /*tiles per strip*/, C3Fuse fz) {
   extern __shared__ __attribute__((aligned(16))) u32x4 smem16[];
-  const int Ws = W + OS2D_PAD, BASE = os2d_base(W), DATA = H * Ws;
+  const int Ws = W + OS2D_PAD, BASE = os2d_base(W);
   const int PW = SP ? SP : Ws;                     // row pitch of the cells in the LDS slab
   const int HALO = 2 * PW + 2, SLAB = C3_NT + 2 * HALO;
   const int SLABP = (2 * SLAB + 63) & ~63;         // slab area rounded up to whole DMA instructions (64 units)
   const int STAGE = SLABP + C3_WUNITS;             // units of one double-buffer half: slab hi | slab lo | pad | weights
   const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, kq = lane >> 4;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int per = gridDim.x >> 3;
-  const int logical = (blockIdx.x & 7) * per + (blockIdx.x >> 3);   // XCD-aware order, see conv_f16x3.hip
+  const int logical = os2d_xcd_logical(blockIdx.x, gridDim.x);      // (plane, tile)
   if (logical >= TILES * NB) return;
   const int tile = logical % TILES, nb = logical / TILES;
   const int strip = SP ? tile / TPS : 0;
-  const int c0mR = SP ? strip * (SP - 4) - 2 : 0;  // map column of strip-plane column 0
+  const int c0mR = SP ? os2d_strip_origin(strip, SP, 2) : 0;
   const int n0 = SP ? (tile - strip * TPS) * C3_NT : BASE + tile * C3_NT;
   const u32x4* inb = in + (size_t)nb * C3_G * 2 * PLANE;
 
-  typedef const void __attribute__((address_space(1))) * gptr_t;
-  typedef void __attribute__((address_space(3))) * lptr_t;
   // one group's operands -> LDS half (G & 1): slab cells n0 - HALO .. n0 + NT + HALO of the hi and the lo plane (clamped to
   // the plane: what lies outside is border = zero, and the last cell of a plane is a zero cell), then the 896 weight units
   const int nslab = (2 * SLAB + 63) / 64;           // wave instructions for the slab (both parts back to back)
@@ -89,18 +82,17 @@ __global__ __launch_bounds__(C3_THR, C3_BUFS == 1 ? (FUSE ? OS2D_C3_FUSE_GROUPS 
       const int part_ = u_ >= SLAB ? 1 : 0;                                                                       \
       int c_ = n0 - HALO + (u_ - part_ * SLAB);                                                                   \
       if (SP) {                                          /* strip-plane index -> map cell, 0 (a zero cell) outside */ \
-        const int h_ = c_ / SP, cc_ = c0mR + (c_ - h_ * SP);                                                      \
-        c_ = (c_ >= 0 && u_ < 2 * SLAB && h_ < H && cc_ >= 0 && cc_ < W) ? BASE + h_ * Ws + cc_ : 0;              \
+        c_ = u_ < 2 * SLAB ? os2d_strip_cell(c_, SP, c0mR, H, W, Ws, BASE) : 0;                                   \
       } else {                                                                                                    \
         c_ = min(max(c_, 0), PLANE - 1);                                                                          \
       }                                                                                                           \
       const u32x4* src_ = inb + ((size_t)(GRP)*2 + part_) * PLANE + c_;                                           \
-      __builtin_amdgcn_global_load_lds((gptr_t)src_, (lptr_t)(dst_ + i_ * 64), 16, 0, 0);                         \
+      os2d_lds_dma16(src_, dst_ + i_ * 64);                                                                       \
     }                                                                                                             \
     for (int i_ = wv; i_ < C3_WUNITS / 64; i_ += C3_THR / 64) {                                                   \
       const int u_ = i_ * 64 + lane;                     /* (tap, part, row < 8) */                               \
       const u32x4* src_ = wp + (size_t)(GRP)*C3_WG + (u_ / C3_ROWS) * 32 + (u_ % C3_ROWS);                        \
-      __builtin_amdgcn_global_load_lds((gptr_t)src_, (lptr_t)(dst_ + SLABP + i_ * 64), 16, 0, 0);                  \
+      os2d_lds_dma16(src_, dst_ + SLABP + i_ * 64);                                                               \
     }                                                                                                             \
   }
 
@@ -168,21 +160,9 @@ __global__ __launch_bounds__(C3_THR, C3_BUFS == 1 ? (FUSE ? OS2D_C3_FUSE_GROUPS 
         }
     }
     __syncthreads();
-    const int n = n0 + tid;
-    int hr, wc;
-    bool ok;
-    if (SP) {
-      hr = n / SP;
-      const int j = n - hr * SP;
-      wc = c0mR + j;
-      ok = !(j < 2 || j >= SP - 2 || hr >= H || wc >= W);
-    } else {
-      const int r = n - BASE;
-      hr = r / Ws;
-      wc = r - hr * Ws;
-      ok = !(n >= PLANE || r >= DATA || wc >= W);
-    }
-    if (!ok) return;
+    int hr, wc, cell;
+    bool valid;
+    if (!os2d_tile_cell(SP != 0, n0 + tid, SP, 2, c0mR, H, W, Ws, BASE, PLANE, &hr, &wc, &cell, &valid) || !valid) return;
     const int HW = H * W, nl = hr * W + wc;
     const int img = nb / fz.Bc;
     const size_t ob = (size_t)img * fz.Btot + fz.b0 + (nb - img * fz.Bc);
@@ -198,19 +178,9 @@ __global__ __launch_bounds__(C3_THR, C3_BUFS == 1 ? (FUSE ? OS2D_C3_FUSE_GROUPS 
   }
 #pragma unroll
   for (int cb = 0; cb < 4; ++cb) {
-    const int n = n0 + wv * 64 + cb * 16 + l15;
-    int hr, wc;
-    if (SP) {
-      hr = n / SP;
-      const int j = n - hr * SP;
-      wc = c0mR + j;
-      if (j < 2 || j >= SP - 2 || hr >= H || wc >= W) continue;
-    } else {
-      const int r = n - BASE;
-      hr = r / Ws;
-      wc = r - hr * Ws;
-      if (n >= PLANE || r >= DATA || wc >= W) continue;
-    }
+    int hr, wc, cell;
+    bool valid;
+    if (!os2d_tile_cell(SP != 0, n0 + wv * 64 + cb * 16 + l15, SP, 2, c0mR, H, W, Ws, BASE, PLANE, &hr, &wc, &cell, &valid) || !valid) continue;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int m = 4 * kq + k;
@@ -228,8 +198,8 @@ namespace {
 int launch_conv3(bool fuse, const C3Fuse& fz, const void* in, const void* wp, const float* bp, void* out, int NB, int P, int H, int W,
                  hipStream_t stream) {
   const int Ws = os2d_ws(W), PLANE = os2d_plane(H, W);
-  int NS = 1, SP = 0;
-  if (W > OS2D_MAX_W_LINEAR5) os2d_conv_strips(W, 2, &NS, &SP);
+  int SP, TPS;
+  const int tiles = os2d_conv_tiles(W > OS2D_MAX_W_LINEAR5, H, W, 2, C3_NT, &SP, &TPS);
   const int SLAB = C3_NT + 2 * (2 * (SP ? SP : Ws) + 2);
   const size_t lds = (size_t)C3_BUFS * (((2 * SLAB + 63) & ~63) + C3_WUNITS) * 16;
   if (lds > 160 * 1024) {
@@ -237,27 +207,13 @@ int launch_conv3(bool fuse, const C3Fuse& fz, const void* in, const void* wp, co
     return -3;
   }
   auto kern = fuse ? conv3_f16x3_kernel<true> : conv3_f16x3_kernel<false>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    os2d_set_error("hipFuncSetAttribute(conv3 f16x3): %s", hipGetErrorString(e));
-    return -4;
-  }
-  const int TPS = SP ? (H * SP + C3_NT - 1) / C3_NT : 0;
-  const int tiles = SP ? NS * TPS : (H * Ws + C3_NT - 1) / C3_NT;
-  const long long groups = (long long)tiles * NB;
-  if (groups + 7 > 0x7fffffffLL) {
-    os2d_set_error("conv3 f16x3: too many work-groups (%lld)", groups);
-    return -3;
-  }
-  dim3 grid((unsigned)((groups + 7) / 8 * 8));
-  hipLaunchKernelGGL(kern, grid, dim3(C3_THR), lds, stream, static_cast<const u32x4*>(in), static_cast<const u32x4*>(wp), bp,
+  int rc = os2d_set_dynamic_lds(kern, lds, "conv3 f16x3");
+  if (rc) return rc;
+  unsigned grid;
+  if ((rc = os2d_xcd_grid((long long)tiles * NB, "conv3 f16x3", &grid))) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(C3_THR), lds, stream, static_cast<const u32x4*>(in), static_cast<const u32x4*>(wp), bp,
                      static_cast<float*>(out), P, H, W, PLANE, tiles, NB, SP, TPS, fz);
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("conv3 f16x3 launch: %s", hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
+  return os2d_launched("conv3 f16x3");
 }
 }  // namespace
 

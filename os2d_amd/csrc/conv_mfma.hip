@@ -19,20 +19,14 @@
 // The B slab only changes with the channel pair, so it is prefetched with the last row-stage of the previous pair.
 // conv1 needs 2*(7 KB + 6 KB) = 27 KB of LDS per group, so occupancy is set by registers (2 waves / SIMD).
 // Arithmetic is exact fp32 (the MFMA is a k-ordered fmaf chain).
-#include "os2d_common.h"
+#include "tile_common.h"
 
 namespace {
 
 constexpr int NBPF = 3;  // max float4 per thread for the B-slab prefetch (SLAB <= 1536 floats)
 
-// STRIP: maps wider than the linear slab takes (SLAB <= 1536 floats) are cut into column strips - the strip-plane geometry of
-// conv_f16x3.hip (os2d_strip_cell): scalar slab loads through the index translation, the matrix loop unchanged with the strip
-// pitch SP for the row pitch.
-__device__ __forceinline__ int conv_strip_cell(int np, int SP, int c0mR, int H, int W, int Ws, int BASE) {
-  const int h = np / SP, c = c0mR + (np - h * SP);
-  return (np >= 0 && h < H && c >= 0 && c < W) ? BASE + h * Ws + c : 0;
-}
-
+// STRIP: maps wider than the linear slab takes (SLAB <= 1536 floats) are cut into the column strips of tile_common.h: scalar slab
+// loads through os2d_strip_cell, the matrix loop unchanged with the strip pitch SPITCH for the row pitch.
 template <int KS, int RS, int MT, int WM, int WN, int NT, bool RELU, bool COMPACT, bool STRIP = false>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const float* __restrict__ in,   // [NB][CinP][PLANE]
                                                            const float* __restrict__ wp,   // [CinP/2][KS*KS][2][MT]
@@ -61,16 +55,14 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const float* __restri
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
   const int wm = wid / WN, wn = wid % WN;
-  // XCD-aware work mapping (see conv_f16x3.hip): XCD x = work-groups L with L % 8 == x gets a contiguous range of the
-  // logical order (plane, tile), so the tiles of one plane - whose input slabs overlap by 2/3 - share one L2
-  const int per = gridDim.x >> 3;
-  const int logical = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+  // logical order (tile_common.h): (plane, tile) - the tiles of one plane, whose input slabs overlap by 2/3, share one L2
+  const int logical = os2d_xcd_logical(blockIdx.x, gridDim.x);
   if (logical >= TILES * NB) return;
   const int tile = logical % TILES;
   const int nb = logical / TILES;
   const int PW = STRIP ? SPITCH : Ws;                            // row pitch of the cells in the LDS slab
   const int strip = STRIP ? tile / TPS : 0;
-  const int c0mR = STRIP ? strip * (SPITCH - 2 * R) - R : 0;     // map column of strip-plane column 0
+  const int c0mR = STRIP ? os2d_strip_origin(strip, SPITCH, R) : 0;
   const int n0 = STRIP ? (tile - strip * TPS) * NT : BASE + tile * NT;
 
   f32x16 acc[MI][NI];
@@ -106,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const float* __restri
         int g_ = n0 - HALO + ((i_ - h2_ * q4) << 2);                                                               \
         if (STRIP) {                                                                                               \
           const float* src_b_ = inb + (size_t)(2 * cp_ + h2_) * PLANE;                                             \
-          _Pragma("unroll") for (int e = 0; e < 4; ++e) pfB[k][e] = src_b_[conv_strip_cell(g_ + e, SPITCH, c0mR, H, W, Ws, BASE)]; \
+          _Pragma("unroll") for (int e = 0; e < 4; ++e) pfB[k][e] = src_b_[os2d_strip_cell(g_ + e, SPITCH, c0mR, H, W, Ws, BASE)]; \
         } else {                                                                                                   \
           g_ = (g_ >= 0 && g_ < PLANE) ? g_ : 0;                                                                   \
           pfB[k] = *reinterpret_cast<const f32x4*>(inb + (size_t)(2 * cp_ + h2_) * PLANE + g_);                    \
@@ -132,7 +124,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const float* __restri
           if (STRIP) {                                                                                             \
             f32x4 v_ = pfB[k];                                                                                     \
             _Pragma("unroll") for (int e = 0; e < 4; ++e)                                                          \
-              if (conv_strip_cell(g_ + e, SPITCH, c0mR, H, W, Ws, BASE) == 0) v_[e] = 0.f;                         \
+              if (os2d_strip_cell(g_ + e, SPITCH, c0mR, H, W, Ws, BASE) == 0) v_[e] = 0.f;                         \
             dstB_[i_] = v_;                                                                                        \
           } else {                                                                                                 \
             dstB_[i_] = (g_ >= 0 && g_ < PLANE) ? pfB[k] : z_;                                                     \
@@ -180,20 +172,10 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const float* __restri
   // ---- epilogue: bias (+ReLU); pad cells of a plane-layout output are written as exact zeros
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) {
-    int n = n0 + wn * NW + ni * 32 + l31;
-    int hr, wc;
-    if (STRIP) {       // strip-plane index -> map cell; only the strip's own output columns (incl. the map's pad columns) are stored
-      hr = n / SPITCH;
-      const int j = n - hr * SPITCH;
-      wc = c0mR + j;
-      if (j < R || j >= SPITCH - R || hr >= H || wc >= Ws) continue;
-      n = BASE + hr * Ws + wc;
-    } else {
-      const int r = n - BASE;
-      hr = r / Ws;
-      wc = r - hr * Ws;
-    }
-    const bool valid = hr < H && wc < W;
+    int hr, wc, n;
+    bool valid;
+    const bool own = os2d_tile_cell(STRIP, n0 + wn * NW + ni * 32 + l31, SPITCH, R, c0mR, H, W, Ws, BASE, PLANE, &hr, &wc, &n, &valid);
+    if (STRIP && !own) continue;          // (linear: every data cell is inside the plane, the plane-layout store tests the rest)
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
@@ -229,8 +211,8 @@ int launch(const float* in, const float* wp, const float* bp, float* out, int NB
   constexpr int NT = 256;
   constexpr int R = KS / 2;
   const int Ws = os2d_ws(W), PLANE = os2d_plane(H, W);
-  int NS = 1, SPITCH = 0;
-  os2d_conv_strips(W, R, &NS, &SPITCH);
+  int SPITCH, TPS;
+  const int tiles = os2d_conv_tiles(STRIP, H, W, R, NT, &SPITCH, &TPS);
   const int HALO = os2d_round_up(R * (STRIP ? SPITCH : Ws) + R, 4);
   const int SLAB = NT + 2 * HALO;
   if (2 * (SLAB / 4) > NBPF * 256) {
@@ -239,23 +221,12 @@ int launch(const float* in, const float* wp, const float* bp, float* out, int NB
   }
   const size_t lds = (size_t)(2 * RS * KS * 2 * MT + 4 * SLAB) * sizeof(float);
   auto kern = conv_mfma_kernel<KS, RS, MT, WM, WN, NT, RELU, COMPACT, STRIP>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds);
-  if (e != hipSuccess) {
-    os2d_set_error("hipFuncSetAttribute(conv): %s", hipGetErrorString(e));
-    return -4;
-  }
-  const int TPS = STRIP ? (H * SPITCH + NT - 1) / NT : 0;
-  const int tiles = STRIP ? NS * TPS : (H * Ws + NT - 1) / NT;
-  const long long groups = (long long)tiles * NB;
-  dim3 grid((unsigned)((groups + 7) / 8 * 8));  // multiple of 8: every XCD gets the same number of logical slots
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, in, wp, bp, out, CinP, CoutStore, H, W, PLANE, HALO, tiles, NB, SPITCH, TPS);
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("conv launch: %s", hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
+  int rc = os2d_set_dynamic_lds(kern, lds, "conv");
+  if (rc) return rc;
+  unsigned grid;
+  if ((rc = os2d_xcd_grid((long long)tiles * NB, "conv", &grid))) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, in, wp, bp, out, CinP, CoutStore, H, W, PLANE, HALO, tiles, NB, SPITCH, TPS);
+  return os2d_launched("conv");
 }
 
 }  // namespace

@@ -26,14 +26,11 @@
 // below that the dropped bits are < 2^-44 absolute) and accumulates integers: lanes, waves and work-groups combine with 64-bit
 // integer atomics, which commute and associate.  corr_norm_finalize_kernel turns the sums into 1 / (sqrt(s) + 1e-6) and
 // clears them for the next call.
-#include "os2d_common.h"
+#include "tile_common.h"
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 #define U32X4_ZERO (u32x4{0u, 0u, 0u, 0u})
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 constexpr int GC = 4;                    // 8-channel groups per K chunk (32 channels)
 constexpr int STACK_STRIDE = 228;        // stacked rows per class (225 rounded up to a multiple of 4)
@@ -110,7 +107,6 @@ __device__ __forceinline__ void corr_tile(const u32x4* fs,  // [A][CGP][2][HW]  
   // form cost ~14 instructions and an M0 dependency stall each).  Both operands are padded with zero channel groups to a
   // whole number of chunks (split_fm / split_qp), columns past H*W read the last valid column instead: their products
   // land in accumulator columns that are never stored.
-  typedef void __attribute__((address_space(3))) * lptr_t;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave index as a scalar
   // STACK: this thread always stages the same stacked row (its units are 256 apart): row p of class bfirst + d, clamped to the
   // last class (rows 225 .. 255 of every class are zero in the operand: the 3 padding rows of the stride need nothing else)
@@ -406,7 +402,6 @@ __device__ __forceinline__ void corr_tile(const u32x4* fs,  // [A][CGP][2][HW]  
         }
         // lower half-wave: channels 0-3, upper: channels 4-7 of the unit.  The lower lane sends its lo half and receives the
         // partner's hi half; the upper lane sends its hi half and receives the partner's lo half.
-        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
         const u32x2 send = hw ? __builtin_bit_cast(u32x2, h4) : __builtin_bit_cast(u32x2, l4);
         u32x2 recv;
         recv[0] = (unsigned)__shfl_xor((int)send[0], 32);
@@ -530,15 +525,6 @@ __global__ __launch_bounds__(256) void corr_norm_finalize_kernel(unsigned long l
 
 constexpr int SCALE_LOG2 = 12;  // operands are L2-normalised (|x| <= 1): hi <= 4096, lo >= 2^-11 * 2^12 * x stays normal
 
-int check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("%s launch: %s", what, hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
-}
-
 }  // namespace
 
 int os2d_corr_groups(int C) { return os2d_round_up((C + 7) / 8, GC); }
@@ -548,13 +534,13 @@ int os2d_launch_split_fm(const float* fm, const float* sumsq, void* fs, int A, i
   hipLaunchKernelGGL(split_fm_kernel, dim3((HW + 255) / 256, os2d_round_up((C + 7) / 8, GC), A), dim3(256), 0, stream, fm, sumsq,
                      reinterpret_cast<u32x4*>(fs), C, HW, ldexpf(1.0f, SCALE_LOG2), static_cast<unsigned long long*>(clear),
                      clear ? clear_words : (size_t)0, status);
-  return check("split_fm");
+  return os2d_launched("split_fm");
 }
 
 int os2d_launch_split_qp(const float* qp, void* qs, int B, int C, hipStream_t stream) {
   hipLaunchKernelGGL(split_qp_kernel, dim3(os2d_round_up((C + 7) / 8, GC), B), dim3(256), 0, stream, qp, reinterpret_cast<u32x4*>(qs), C,
                      ldexpf(1.0f, SCALE_LOG2));
-  return check("split_qp");
+  return os2d_launched("split_qp");
 }
 
 namespace {
@@ -592,12 +578,7 @@ int launch_corr(const void* fs, const void* qs, float* corr, void* rshb, float* 
                 int B, int C, int H, int W, hipStream_t stream) {
   const int HW = H * W;
   const size_t lds = (size_t)(2 * GC * 2 * TM + 2 * GC * 2 * (128 * NIM)) * 16;  // 128 KB (NIM = 2) / 96 KB dynamic (+ 4 KB static)
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(corr_f16x3_kernel<STACK, NIM>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    os2d_set_error("hipFuncSetAttribute(corr f16x3): %s", hipGetErrorString(e));
-    return -4;
-  }
+  if (int rc = os2d_set_dynamic_lds(corr_f16x3_kernel<STACK, NIM>, lds, "corr f16x3")) return rc;
   const int RT = STACK ? (B * STACK_STRIDE + TM - 1) / TM : B;       // row tiles: stacked classes | one per class
   const long long tiles_total = (long long)((HW + 128 * NIM - 1) / (128 * NIM)) * RT * A;
   const CorrGrid g = corr_grid(tiles_total, NIM == 2 && !(flags & 2));
@@ -605,11 +586,11 @@ int launch_corr(const void* fs, const void* qs, float* corr, void* rshb, float* 
   hipLaunchKernelGGL((corr_f16x3_kernel<STACK, NIM>), grid, dim3(512), lds, stream, reinterpret_cast<const u32x4*>(fs),
                      reinterpret_cast<const u32x4*>(qs), corr, reinterpret_cast<char*>(rshb), invn, sumfx, A, B,
                      os2d_round_up((C + 7) / 8, GC), H, W, os2d_plane(H, W), ldexpf(1.0f, -2 * SCALE_LOG2), g.tpx, g.rsplit);
-  int rc = check("corr_f16x3");
+  int rc = os2d_launched("corr_f16x3");
   if (rc || !STACK || (flags & 1)) return rc;
   const size_t n = (size_t)A * B * HW;
   hipLaunchKernelGGL(corr_norm_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, sumfx, invn, n);
-  return check("corr_norm_finalize");
+  return os2d_launched("corr_norm_finalize");
 }
 
 }  // namespace

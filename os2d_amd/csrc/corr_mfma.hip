@@ -15,7 +15,7 @@
 // written to the other buffer after them, one barrier per chunk).  Outputs:
 //   corr  [A*B][225][H*W]      raw correlation (input of the resampling kernel)
 //   rpad  [A*B][226][PLANE]    relu+L2-normalised, in the zero-bordered plane layout the conv kernels read
-#include "os2d_common.h"
+#include "tile_common.h"
 
 namespace {
 
@@ -193,7 +193,6 @@ __global__ __launch_bounds__(256, 2) void corr_mfma_kernel(const float* __restri
     } else {
       // split-half blocked output for conv_f16x3.hip: [nb][29 groups][hi|lo][PLANE] units of 8 halves.  Registers
       // 4q..4q+3 of a lane are rows m0..m0+3 = channels 4*hi..4*hi+3 of group m0/8: one 8-byte store each for hi, lo.
-      typedef _Float16 half4 __attribute__((ext_vector_type(4)));
       char* base = reinterpret_cast<char*>(rpad);
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi)
@@ -235,10 +234,5 @@ int os2d_launch_corr(const float* fm, const float* qp, const float* sumsq, float
   else if (shb) CORR_GO(false, true);
   else CORR_GO(false, false);
 #undef CORR_GO
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("corr launch: %s", hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
+  return os2d_launched("corr");
 }

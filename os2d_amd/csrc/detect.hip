@@ -18,6 +18,7 @@
 // survivors are written out by all threads at the end.
 // Outputs are compacted per class in decreasing-score order: out_boxes/out_scores/out_index[c][0 .. out_count[c]).
 #include "detect_common.h"
+#include "tile_common.h"
 
 namespace {
 
@@ -150,20 +151,10 @@ int os2d_launch_detect_level(const float* loc, const float* cls, int B, int H, i
     os2d_set_error("os2d_detect_level: level %dx%d does not fit the fused kernel's LDS (use decode_boxes + nms)", H, W);
     return -3;
   }
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(detect_level_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    os2d_set_error("hipFuncSetAttribute(detect_level): %s", hipGetErrorString(e));
-    return -4;
-  }
+  if (int rc = os2d_set_dynamic_lds(detect_level_kernel, lds, "detect_level")) return rc;
   const float half_box = 0.5f * (float)(stride * (OS2D_T - 1) + rec_field);
   hipLaunchKernelGGL(detect_level_kernel, dim3(B), dim3(NTHR), lds, stream, loc, cls, H, W, (float)stride, half_box, img_w,
                      img_h, ops, score_thr, iou_thr, os2d_next_pow2(H * W), reinterpret_cast<float4*>(out_boxes),
                      out_scores, out_index, out_count);
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("detect_level launch: %s", hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
+  return os2d_launched("detect_level");
 }

@@ -30,6 +30,7 @@
 // by level.  The kernels work on G labels x V slots: slot_rows[g * V + v] names the head row of view v of label g (-1: none),
 // candidate j of label g = (slot j / N, location j % N); everything after pyr_decode just sees G "classes" of V * N candidates.
 #include "detect_common.h"
+#include "tile_common.h"
 #include "../../include/os2d_hip.h"
 
 namespace {
@@ -397,15 +398,6 @@ Carve carve(int B, int N, int passes) {
   return c;
 }
 
-int check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("%s launch: %s", what, hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -500,32 +492,26 @@ static int detect_pyramid_impl(const float* const* loc, const float* const* cls,
   }
   hipLaunchKernelGGL(pyr_decode_kernel, dim3((N1 + 255) / 256, G * V), dim3(256), 0, st, T, N1, (float)stride, half_box,
                      score_threshold, boxes, scores, keys, slot_rows);
-  int rc = check("pyr_decode");
+  int rc = os2d_launched("pyr_decode");
   if (rc) return rc;
   hipLaunchKernelGGL(pyr_compact_kernel, dim3(G), dim3(NTHR), 0, st, N, M, keys, ids[0], counts, final_pass);
-  if ((rc = check("pyr_compact"))) return rc;
+  if ((rc = os2d_launched("pyr_compact"))) return rc;
   const int NP2 = os2d_next_pow2(min(M, N));
   const size_t lds = (size_t)NP2 * 6 + (((size_t)M * 2 + 15) & ~(size_t)15) + (size_t)KCAP * 16;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(pyr_chunk_nms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(pyr_finalize_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)((size_t)16384 * 6));
-  if (e != hipSuccess) {
-    os2d_set_error("hipFuncSetAttribute(detect_pyramid): %s", hipGetErrorString(e));
-    return -4;
-  }
+  if ((rc = os2d_set_dynamic_lds(pyr_chunk_nms_kernel, lds, "detect_pyramid"))) return rc;
+  if ((rc = os2d_set_dynamic_lds(pyr_finalize_kernel, (size_t)16384 * 6, "detect_pyramid"))) return rc;
   const int chunks0 = (N + M - 1) / M;
   for (int p = 0; p < passes; ++p) {
     // pass 0 may need every chunk; a later pass works on the survivors: at most as many chunks as the pass before
     hipLaunchKernelGGL(pyr_chunk_nms_kernel, dim3(chunks0, G), dim3(NTHR), lds, st, p, N, M, NP2, iou_threshold, boxes, keys,
                        ids[p & 1], ids[(p + 1) & 1], sorted, counts, final_pass);
-    if ((rc = check("pyr_chunk_nms"))) return rc;
+    if ((rc = os2d_launched("pyr_chunk_nms"))) return rc;
   }
   hipLaunchKernelGGL(pyr_finalize_kernel, dim3(G), dim3(NTHR), (size_t)16384 * 6, st, passes, N, M, 16384, boxes, scores, keys,
                      ids[0], ids[1], counts, final_pass, reinterpret_cast<float4*>(out_boxes), out_scores, out_index, out_count,
                      unfinished, T, (float)stride, half_box, reinterpret_cast<float4*>(out_default), out_corners, N1, V,
                      slot_rows, D);
-  return check("pyr_finalize");
+  return os2d_launched("pyr_finalize");
 }
 
 // level -> output image as plain per-axis scales (BoxList.resize): the one-op chains of the original entry points

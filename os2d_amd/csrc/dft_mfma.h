@@ -75,13 +75,10 @@
 #define DFT_STAMP_END(BASE)
 #endif
 
+#include "tile_common.h"
+
 namespace os2d_dft {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16v __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2v __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));      // 4 floats at any float address (one dwordx4 load)
 
 constexpr int DFT_THR = 512, DFT_WAVES = 8;
@@ -294,26 +291,25 @@ DFT_DEV int dft_div(int x, unsigned magic) { return magic ? (int)(((unsigned lon
 // fp16 hi + lo of four values: two 8-byte halves-of-a-unit.  Vector conversions: gfx950 has v_cvt_pk_f16_f32 (two values per
 // instruction, round to nearest even like the scalar form) - 12 instructions per call instead of ~20 with scalar conversions
 // and integer packing; the split conversions are a third of the VALU work of the W / R / WY / WT phases.
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-DFT_DEV void dft_split4(float a, float b, float c, float d, u32x2v* hi, u32x2v* lo) {
-  const f32x4v x = {a, b, c, d};
-  const half4v h = __builtin_convertvector(x, half4v);
-  *hi = __builtin_bit_cast(u32x2v, h);
+DFT_DEV void dft_split4(float a, float b, float c, float d, u32x2* hi, u32x2* lo) {
+  const f32x4 x = {a, b, c, d};
+  const half4 h = __builtin_convertvector(x, half4);
+  *hi = __builtin_bit_cast(u32x2, h);
 #ifdef DFT_SPLIT_LO_PAIR      /* device build: one mixed-precision instruction per lo half (os2d_split_lo_pair), same bits */
-  u32x2v l;
+  u32x2 l;
   l[0] = DFT_SPLIT_LO_PAIR(a, b, (*hi)[0]);
   l[1] = DFT_SPLIT_LO_PAIR(c, d, (*hi)[1]);
   *lo = l;
 #else
-  const half4v l = __builtin_convertvector(x - __builtin_convertvector(h, f32x4v), half4v);
-  *lo = __builtin_bit_cast(u32x2v, l);
+  const half4 l = __builtin_convertvector(x - __builtin_convertvector(h, f32x4), half4);
+  *lo = __builtin_bit_cast(u32x2, l);
 #endif
 }
 
-DFT_DEV half8 dft_frag(const u32x4v* p) { return __builtin_bit_cast(half8, *p); }
+DFT_DEV half8 dft_frag(const u32x4* p) { return __builtin_bit_cast(half8, *p); }
 
 // one split product step: acc += A_hi B_lo + A_lo B_hi + A_hi B_hi (fp32 accumulation; the dropped lo x lo term is 2^-22 relative)
-DFT_DEV f32x16v dft_mma3(half8 ah, half8 al, half8 bh, half8 bl, f32x16v acc) {
+DFT_DEV f32x16 dft_mma3(half8 ah, half8 al, half8 bh, half8 bl, f32x16 acc) {
   acc = DFT_MFMA(ah, bl, acc);
   acc = DFT_MFMA(al, bh, acc);
   acc = DFT_MFMA(ah, bh, acc);
@@ -333,7 +329,7 @@ DFT_DEV f32x16v dft_mma3(half8 ah, half8 al, half8 bh, half8 bl, f32x16v acc) {
 // (The next iteration's global loads spread over the k-steps of this product instead of one burst next to it: measured slower,
 // tools/patches/dft_mfma_variants.patch.)
 template <int NT, int KS>
-DFT_DEV void dft_product_rega(f32x16v* acc, const half8* ah, const half8* al, int ksn, const u32x4v* B, int bstride, int nt0,
+DFT_DEV void dft_product_rega(f32x16* acc, const half8* ah, const half8* al, int ksn, const u32x4* B, int bstride, int nt0,
                               int ntstep, int l31, int hw) {
   constexpr int KR = KS ? KS : DFT_KREG;
   half8 bh[2][NT], bl[2][NT];
@@ -361,7 +357,7 @@ DFT_DEV void dft_product_rega(f32x16v* acc, const half8* ah, const half8* al, in
 }
 
 template <int KS>
-DFT_DEV void dft_product_rega_any(f32x16v* acc, int ntiles, const half8* ah, const half8* al, int ksn, const u32x4v* B, int bstride,
+DFT_DEV void dft_product_rega_any(f32x16* acc, int ntiles, const half8* ah, const half8* al, int ksn, const u32x4* B, int bstride,
                                   int nt0, int ntstep, int l31, int hw) {
   if (ntiles == 3) dft_product_rega<3, KS>(acc, ah, al, ksn, B, bstride, nt0, ntstep, l31, hw);
   else if (ntiles == 2) dft_product_rega<2, KS>(acc, ah, al, ksn, B, bstride, nt0, ntstep, l31, hw);
@@ -373,7 +369,7 @@ DFT_DEV void dft_product_rega_any(f32x16v* acc, int ntiles, const half8* ah, con
 // above: two fragment sets, the k loop unrolled by two so that the sets keep their registers, the reads of k-step ks + 1 in front
 // of the matrix instructions of k-step ks (an index beyond the last k-step is clamped: one harmless re-read).
 template <int NT, bool SHARE, int NW, int PIPE_MODE>
-DFT_DEV void dft_product_lds(f32x16v* acc, int ks0, int ks1, const u32x4v* A, int astride, const u32x4v* B, int bstride, int t0, int mtn,
+DFT_DEV void dft_product_lds(f32x16* acc, int ks0, int ks1, const u32x4* A, int astride, const u32x4* B, int bstride, int t0, int mtn,
                              int l31, int hw) {
   constexpr int NA = SHARE ? 1 : NT;
   int tm[NT], tn[NT];
@@ -429,7 +425,7 @@ DFT_DEV void dft_product_lds(f32x16v* acc, int ks0, int ks1, const u32x4v* A, in
 }
 
 template <int NW, int PIPE_MODE>
-DFT_DEV void dft_product_lds_any(f32x16v* acc, int ntiles, int ks0, int ks1, const u32x4v* A, int astride, const u32x4v* B, int bstride,
+DFT_DEV void dft_product_lds_any(f32x16* acc, int ntiles, int ks0, int ks1, const u32x4* A, int astride, const u32x4* B, int bstride,
                                  int t0, int mtn, int l31, int hw) {
   const bool share = mtn == NW;
   if (ntiles == 3) {
@@ -449,7 +445,7 @@ DFT_DEV void dft_product_lds_any(f32x16v* acc, int ntiles, int ks0, int ks1, con
 //   Fp2 [k = (ri * Pp + h) / 8][hi|lo][m = 2 u + ro]  value = ro == 0 ? (ri == 0 ? cos : sin) : (ri == 0 ? -sin : cos) of 2 pi u h / P
 //   E2  [k = (ri * Pp + u) / 8][hi|lo][m = 2 h + ro]  value = ro == 0 ? (ri == 0 ? cos : -sin) : (ri == 0 ? sin : cos)
 //   Gq  [k = (2 v + ri) / 8][hi|lo][n = w]            value = a_v * E_Q[v w].{re, im}, a_0 = a_{Q/2} = 1, else 2   * 2^13
-DFT_DEV void dft_matrix_unit(int which, int unit, int P, int Q, const double* twP, const double* twQ, u32x4v* out) {
+DFT_DEV void dft_matrix_unit(int which, int unit, int P, int Q, const double* twP, const double* twQ, u32x4* out) {
   const int V = Q / 2 + 1, Pp = dft_round_up(P, 8);
   int cols, kidx, hl, col;
   double vals[8];
@@ -499,7 +495,7 @@ DFT_DEV void dft_matrix_unit(int which, int unit, int P, int Q, const double* tw
     }
     w[t] = (unsigned)b[0] | ((unsigned)b[1] << 16);
   }
-  u32x4v o;
+  u32x4 o;
   o[0] = w[0];
   o[1] = w[1];
   o[2] = w[2];
@@ -514,7 +510,7 @@ template <bool TILED, bool FAST, int G, int NW, int KS2 = 0>
 DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
                               const float* invn,      // [NB][H * W]
                               float* X,               // [NBT / 64][NBINS / 4][64][Cpad][4][2] (dft_spectra_pair0)
-                              const u32x4v* FqT, const u32x4v* Fp2, const DftPlan& pl, int C, int Cpad, int NBT, int iters) {
+                              const u32x4* FqT, const u32x4* Fp2, const DftPlan& pl, int C, int Cpad, int NBT, int iters) {
   constexpr int THR = NW * 64;
   constexpr bool ALDS = G == 8;    // the row operand of step 2 lives in LDS
   unsigned char* smem = DFT_LDS;
@@ -523,12 +519,12 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
   const int P = pl.P, V = pl.V, Pp = pl.Pp, Wk = pl.Wk, N1 = pl.N1, Mx = pl.Mx, N2 = pl.N2, LH = pl.LH, LW = pl.LW, W = pl.W, H = pl.H;
   const int MxS = Mx + 1, N2S = N2 + 1;
   const int CG = (C + G - 1) / G, HW = H * W;
-  u32x4v* ldsF = reinterpret_cast<u32x4v*>(smem);                                   // FqT [Wk / 8][2][N1]
-  u32x4v* ldsU = reinterpret_cast<u32x4v*>(smem + pl.lds_const);                    // x | R2 | X staging
+  u32x4* ldsF = reinterpret_cast<u32x4*>(smem);                                   // FqT [Wk / 8][2][N1]
+  u32x4* ldsU = reinterpret_cast<u32x4*>(smem + pl.lds_const);                    // x | R2 | X staging
   unsigned char* ldsUb = smem + pl.lds_const;
   const int nF = (Wk / 8) * 2 * N1;
   for (int i = tid; i < nF; i += THR) ldsF[i] = FqT[i];
-  u32x4v* ldsP = ldsF + nF;                                                         // ALDS: Fp2 [2 Pp / 8][2][M2]
+  u32x4* ldsP = ldsF + nF;                                                         // ALDS: Fp2 [2 Pp / 8][2][M2]
   if (ALDS)
     for (int i = tid; i < (2 * Pp / 8) * 2 * pl.M2; i += THR) ldsP[i] = Fp2[i];
 
@@ -565,7 +561,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
   // all G images; raw values only (any arithmetic here would make the compiler wait for each load where it is issued)
   constexpr int NSLOT = ALDS ? 2 : 3 * 512 / THR;              // ceil(Pp * Wk / 4 / THR) <= 64 * 24 / THR (G = 8: <= 48 * 16 / 512)
   const int npos = Pp * (Wk / 4);
-  f32x4v pc[NSLOT][G], pn[NSLOT];
+  f32x4 pc[NSLOT][G], pn[NSLOT];
 #define DFT_FWD_ITER(IT)                                                                                     \
   const int pr_ = dft_div((IT), pl.inv_cg), cg_ = (IT)-pr_ * CG;                                             \
   const int nb_ = TILED ? dft_div(pr_, pl.inv_t) : pr_, tile_ = TILED ? pr_ - nb_ * pl.T : 0;               \
@@ -586,10 +582,10 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
       if (FAST) {                                                                                            \
         const bool ok = i_ < npos && r_ < LH && 4 * c4_ < LW;                                                \
         const int off = ok ? y_ * W + x_ : 0;                                                                \
-        pn[s] = *reinterpret_cast<const f32x4v*>(invn + (size_t)nb_ * HW + off);                             \
+        pn[s] = *reinterpret_cast<const f32x4*>(invn + (size_t)nb_ * HW + off);                             \
         _Pragma("unroll") for (int g = 0; g < G; ++g) {                                                  \
           const int c = c0_ + g < C ? c0_ + g : C - 1;                                                       \
-          pc[s][g] = *reinterpret_cast<const f32x4v*>(corr + ((size_t)nb_ * C + c) * HW + off);              \
+          pc[s][g] = *reinterpret_cast<const f32x4*>(corr + ((size_t)nb_ * C + c) * HW + off);              \
         }                                                                                                    \
       } else {                                                                                               \
         /* rows of any width / tiles: the slot's 4 columns as ONE 16-byte load with 4-byte alignment (global loads need no   \
@@ -625,7 +621,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
   // (round 4, tried: converting the prefetched window to fp16 pairs IN REGISTERS before the store loop, as the inverse kernel now
   // does with its maxima - the W phase fell from 1.6 to 1.0 us but the conversion cost 0.9 us where it went and the stores 0.3 us
   // more: 14.7 against 14.3 us per iteration, profiles/r04/dft_phases_v4_convert_before_stores.txt.  Not kept.)
-  // XCD-aware order (work-group L runs on XCD L % 8): every XCD takes a contiguous range of iterations, so work-groups whose
+  // XCD-aware order (tile_common.h; written out: os2d_xcd_logical is unsigned arithmetic, the hooks are int): every XCD takes a contiguous range of iterations, so work-groups whose
   // outputs share cache lines / 16-byte units (neighbouring channel groups) run on ONE XCD at about the same time
   const int first = (DFT_GRID & 7) == 0 ? (DFT_BID & 7) * (DFT_GRID >> 3) + (DFT_BID >> 3) : DFT_BID;
   if (first < iters) DFT_FWD_PREFETCH(first, tid)
@@ -657,28 +653,28 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
           }
 #pragma unroll
           for (int g = 0; g < G; ++g) {
-            u32x2v hi = {0u, 0u}, lo = {0u, 0u};
+            u32x2 hi = {0u, 0u}, lo = {0u, 0u};
             if (c0_ + g < C)         // (uniform: only the last channel group of a pair has channels beyond C)
               dft_split4(fmaxf(pc[s][g][0], 0.f) * nsc[0], fmaxf(pc[s][g][1], 0.f) * nsc[1], fmaxf(pc[s][g][2], 0.f) * nsc[2],
                          fmaxf(pc[s][g][3], 0.f) * nsc[3], &hi, &lo);
             const int m = g * Pp + r_;
             unsigned char* dst = ldsUb + ((size_t)((c4_ >> 1) * 2) * MxS + m) * 16 + (c4_ & 1) * 8;
-            *reinterpret_cast<u32x2v*>(dst) = hi;
-            *reinterpret_cast<u32x2v*>(dst + (size_t)MxS * 16) = lo;
+            *reinterpret_cast<u32x2*>(dst) = hi;
+            *reinterpret_cast<u32x2*>(dst + (size_t)MxS * 16) = lo;
           }
         }
       }
       // rows G * Pp .. Mx of the last row tile (only when G * Pp is not a multiple of 32): zeros
       for (int i = tid; i < (Mx - G * Pp) * (Wk / 8) * 2; i += THR) {
         const int m = G * Pp + i % (Mx - G * Pp), kh = i / (Mx - G * Pp);
-        ldsU[(size_t)kh * MxS + m] = u32x4v{0u, 0u, 0u, 0u};
+        ldsU[(size_t)kh * MxS + m] = u32x4{0u, 0u, 0u, 0u};
       }
     }
     DFT_BARRIER();
     DFT_STAMP(0)
 
     // ---- step 1: R^T = x . FqT; this wave's tiles t = wv + 8 j of the mt1n x nt1n grid
-    f32x16v acc[3];
+    f32x16 acc[3];
     int tm[3], tn[3];
     int nt1w = 0;
 #pragma unroll
@@ -708,13 +704,13 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
         const int mb = tm[j] * 32 + 8 * q;
         const int img = dft_div(mb, pl.inv_pp), h0 = mb - img * Pp + 4 * hw;
         if (v < V && img < G) {
-          u32x2v hi, lo;
+          u32x2 hi, lo;
           const float sc = 1.0f / 2097152.0f;      // 2^-21 = 2^8 / (2^15 * 2^14)
           dft_split4(acc[j][4 * q] * sc, acc[j][4 * q + 1] * sc, acc[j][4 * q + 2] * sc, acc[j][4 * q + 3] * sc, &hi, &lo);
           const int kg = ri * (Pp / 8) + (h0 >> 3);
           unsigned char* dst = ldsUb + ((size_t)(kg * 2) * N2S + img * V + v) * 16 + (h0 & 4) * 2;
-          *reinterpret_cast<u32x2v*>(dst) = hi;
-          *reinterpret_cast<u32x2v*>(dst + (size_t)N2S * 16) = lo;
+          *reinterpret_cast<u32x2*>(dst) = hi;
+          *reinterpret_cast<u32x2*>(dst + (size_t)N2S * 16) = lo;
         }
       }
     }
@@ -723,7 +719,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
 
     // ---- step 2: X = Fp2 . R2 (Fp2 fragments in registers); this wave's column tiles (wv >> 2) + 2 j of row tile wv & 3
     // (ALDS: tiles t = wv + NW j of the mt2n x nt2n grid, row tile fastest - as dft_product_lds counts them)
-    f32x16v xc[3];
+    f32x16 xc[3];
     int un[3], um[3];      // column / row tile of accumulator j, -1: none
     int nt2w = 0;
 #pragma unroll
@@ -773,12 +769,12 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
         const int u0 = (um[j] * 32 + 8 * q + 4 * hw) >> 1;
         if (img < G && u0 < P) {
           const float sc = 1.0f / 4194304.0f;      // 2^-22 = 1 / (2^8 * 2^14)
-          f32x4v o;
+          f32x4 o;
           o[0] = xc[j][4 * q] * sc;
           o[1] = xc[j][4 * q + 1] * sc;
           o[2] = xc[j][4 * q + 2] * sc;
           o[3] = xc[j][4 * q + 3] * sc;
-          *reinterpret_cast<f32x4v*>(ldsUb + (size_t)v * XS + (u0 >> 2) * (G * 32) + img * 32 + (u0 & 3) * 8) = o;
+          *reinterpret_cast<f32x4*>(ldsUb + (size_t)v * XS + (u0 >> 2) * (G * 32) + img * 32 + (u0 & 3) * 8) = o;
         }
       }
     }
@@ -793,12 +789,12 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
       for (int i = tl; i < npieces; i += THR) {
         const int v = dft_div(i, pl.inv_pq), rem = i - v * per_v;
         const int uq = rem / (2 * G), jj = rem - uq * (2 * G);
-        const f32x4v val = *reinterpret_cast<const f32x4v*>(ldsUb + (size_t)v * XS + uq * (G * 32) + jj * 16);
-        DFT_STREAM_STORE(reinterpret_cast<f32x4v*>(dstbase + (size_t)(v * (P / 4) + uq) * qstride + jj * 4), val);
+        const f32x4 val = *reinterpret_cast<const f32x4*>(ldsUb + (size_t)v * XS + uq * (G * 32) + jj * 16);
+        DFT_STREAM_STORE(reinterpret_cast<f32x4*>(dstbase + (size_t)(v * (P / 4) + uq) * qstride + jj * 4), val);
       }
       const int qpad0 = (P * V) / 4, qpad1 = pl.NBINS / 4;
       for (int i = tl; i < (qpad1 - qpad0) * 2 * G; i += THR)
-        *reinterpret_cast<f32x4v*>(dstbase + (size_t)(qpad0 + i / (2 * G)) * qstride + (i % (2 * G)) * 4) = f32x4v{0.f, 0.f, 0.f, 0.f};
+        *reinterpret_cast<f32x4*>(dstbase + (size_t)(qpad0 + i / (2 * G)) * qstride + (i % (2 * G)) * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     DFT_BARRIER();      // the staging buffer is free: the next window may be written
     DFT_STAMP(5)
@@ -817,7 +813,7 @@ template <bool TILED, int KSA = 0, int G = DFT_G>
 DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64][Cout][4][2] (dft_spectra_pair0)
                               const float* bp,       // [3][MTP]: bias | - | 2^out_exp
                               int MTP, unsigned char* out,   // SHB [NB][Cout / 8][2][PLANE] x 16 B
-                              const u32x4v* E2, const u32x4v* Gq, const DftPlan& pl, int Cout, int NBT, int PLANE, int Ws,
+                              const u32x4* E2, const u32x4* Gq, const DftPlan& pl, int Cout, int NBT, int PLANE, int Ws,
                               int BASE, int iters, DFT_FLAG bad_flag, int zero_borders) {
   unsigned char* smem = DFT_LDS;
   const int tid = DFT_TID, lane = tid & 63, l31 = lane & 31, hw = lane >> 5;
@@ -827,8 +823,8 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
   const int OG = Cout / G;
   constexpr bool ALDS = G == 8;      // the row operand of step A lives in LDS
   constexpr int LG = G == 8 ? 3 : 2; // log2 G
-  u32x4v* ldsG = reinterpret_cast<u32x4v*>(smem);                                   // Gq [KB / 8][2][NBo]
-  u32x4v* ldsU = reinterpret_cast<u32x4v*>(smem + pl.lds_const);                    // Y2 | Tt
+  u32x4* ldsG = reinterpret_cast<u32x4*>(smem);                                   // Gq [KB / 8][2][NBo]
+  u32x4* ldsU = reinterpret_cast<u32x4*>(smem + pl.lds_const);                    // Y2 | Tt
   unsigned char* ldsUb = smem + pl.lds_const;
   float* smaxw = reinterpret_cast<float*>(smem + pl.lds_const + pl.lds_union);      // [8 waves][G]: |Y| maxima
   const int nG = (KB / 8) * 2 * NBo, NQ = dft_round_up(pl.Q, 32);     // the Gq array has round_up(Q, 32) columns, NBo of them are needed
@@ -837,7 +833,7 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
     ldsG[i] = Gq[(size_t)kh * NQ + n];
   }
   const int MAfull = dft_round_up(2 * P, 32);                    // row count of the E2 array
-  u32x4v* ldsE = ldsG + nG;                                      // ALDS: E2 [2 Pp / 8][2][MAfull]
+  u32x4* ldsE = ldsG + nG;                                      // ALDS: E2 [2 Pp / 8][2][MAfull]
   if (ALDS)
     for (int i = tid; i < (2 * Pp / 8) * 2 * MAfull; i += DFT_THR) ldsE[i] = E2[i];
 
@@ -863,7 +859,7 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
   // ---- register prefetch: item = (img, v, octet of u) -> the two quads of bins u0 .. u0 + 7 of column v: 2 x 32 bytes
   constexpr int NITEM = 3;                                      // ceil(G * V * Pp / 8 / 512) <= 4 * 48 * 8 / 512 (G = 8: 8 * 32 * 6 / 512)
   const int uoct = Pp / 8, nitem = G * V * uoct;
-  f32x4v py[NITEM][4];
+  f32x4 py[NITEM][4];
 #define DFT_INV_PREFETCH(IT, TID) DFT_INV_PREFETCH_ITEMS(IT, TID, 0, NITEM)
 #define DFT_INV_PREFETCH_ITEMS(IT, TID, S0, S1)                                             \
   {                                                                                         \
@@ -879,10 +875,10 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
       const bool ptwo_ = 8 * puo_ + 4 < P;                                                  \
       const float* p0_ = src_ + (size_t)q0_ * qstride + pimg_ * 8;                          \
       const float* p1_ = src_ + (size_t)(ptwo_ ? q0_ + 1 : q0_) * qstride + pimg_ * 8;      \
-      py[s][0] = *reinterpret_cast<const f32x4v*>(p0_);                                     \
-      py[s][1] = *reinterpret_cast<const f32x4v*>(p0_ + 4);                                 \
-      py[s][2] = *reinterpret_cast<const f32x4v*>(p1_);                                     \
-      py[s][3] = *reinterpret_cast<const f32x4v*>(p1_ + 4);                                 \
+      py[s][0] = *reinterpret_cast<const f32x4*>(p0_);                                     \
+      py[s][1] = *reinterpret_cast<const f32x4*>(p0_ + 4);                                 \
+      py[s][2] = *reinterpret_cast<const f32x4*>(p1_);                                     \
+      py[s][3] = *reinterpret_cast<const f32x4*>(p1_ + 4);                                 \
     }                                                                                       \
   }
 #define DFT_INV_ITEM(E)                                                                     \
@@ -974,8 +970,8 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
           re[2 * k + 1] = ok ? py[s][k][2] * simg : 0.f;
           im[2 * k + 1] = ok ? py[s][k][3] * simg : 0.f;
         }
-        u32x2v h0, l0, h1, l1;
-        u32x4v t;
+        u32x2 h0, l0, h1, l1;
+        u32x4 t;
         const size_t n = (size_t)img * V + v;
         dft_split4(re[0], re[1], re[2], re[3], &h0, &l0);
         dft_split4(re[4], re[5], re[6], re[7], &h1, &l1);
@@ -996,7 +992,7 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
 
     // ---- step A: T = E2 . Y2 (E2 fragments in registers)
     // (ALDS: tiles t = wv + 8 j of the mtAn x ntAn grid, row tile fastest - as dft_product_lds counts them)
-    f32x16v ta[3];
+    f32x16 ta[3];
     int an[3], am[3];      // column / row tile of accumulator j, -1: none
     int ntaw = 0;
 #pragma unroll
@@ -1041,7 +1037,7 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int h0 = (am[j] * 32 + 8 * q + 4 * hw) >> 1;
-          u32x2v hi, lo;
+          u32x2 hi, lo;
           dft_split4(ta[j][4 * q] * sc, ta[j][4 * q + 1] * sc, ta[j][4 * q + 2] * sc, ta[j][4 * q + 3] * sc, &hi, &lo);
           unsigned char* d0 = ldsUb + ((size_t)((v >> 2) * 2) * MBS + (size_t)h0 * G + img) * 16 + (v & 3) * 4;
           *reinterpret_cast<unsigned*>(d0) = hi[0];
@@ -1061,7 +1057,7 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
     DFT_STAMP(3)
 
     // ---- step B: y = Tt . Gq; this wave's tiles t = wv + 8 j of the mtBn x ntBn grid
-    f32x16v yc[3];
+    f32x16 yc[3];
     int bm[3], bn[3];
     int ntbw = 0;
 #pragma unroll
@@ -1105,11 +1101,11 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
             cell = BASE + hr * Ws + W + (jj - hr * (Ws - W));
           } else cell = tail0 + (k - BASE - rows);
           if (G == 8) {
-            *reinterpret_cast<u32x4v*>(hi_unit + (size_t)cell * 16) = u32x4v{0u, 0u, 0u, 0u};
-            *reinterpret_cast<u32x4v*>(lo_unit + (size_t)cell * 16) = u32x4v{0u, 0u, 0u, 0u};
+            *reinterpret_cast<u32x4*>(hi_unit + (size_t)cell * 16) = u32x4{0u, 0u, 0u, 0u};
+            *reinterpret_cast<u32x4*>(lo_unit + (size_t)cell * 16) = u32x4{0u, 0u, 0u, 0u};
           } else {
-            *reinterpret_cast<u32x2v*>(hi_unit + (size_t)cell * 16) = u32x2v{0u, 0u};
-            *reinterpret_cast<u32x2v*>(lo_unit + (size_t)cell * 16) = u32x2v{0u, 0u};
+            *reinterpret_cast<u32x2*>(hi_unit + (size_t)cell * 16) = u32x2{0u, 0u};
+            *reinterpret_cast<u32x2*>(lo_unit + (size_t)cell * 16) = u32x2{0u, 0u};
           }
         }
       }
@@ -1132,21 +1128,21 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
               // out of the fp16 range, or NaN: the pre-activation is tested too, fmaxf(NaN, 0) = 0 hid a NaN spectrum
               if (inside && (!(fabsf(t[g]) <= 65504.f) || pre != pre)) bad = true;
             }
-            u32x2v hi, lo;
+            u32x2 hi, lo;
             dft_split4(t[0], t[1], t[2], t[3], &hi, &lo);
             const size_t off = ((size_t)BASE + (size_t)h * Ws + w) * 16;
             if (G == 8) {
               // the lower lane sends its lo half and receives the partner's hi half (-> the complete hi unit), the upper lane sends its
               // hi half and receives the partner's lo half (-> the complete lo unit); every lane of the wave takes part
-              const u32x2v send = hw ? hi : lo, keep = hw ? lo : hi;
-              u32x2v recv;
+              const u32x2 send = hw ? hi : lo, keep = hw ? lo : hi;
+              u32x2 recv;
               recv[0] = DFT_SHFL_XOR_U32(send[0], 32);
               recv[1] = DFT_SHFL_XOR_U32(send[1], 32);
-              const u32x4v unit = hw ? u32x4v{recv[0], recv[1], keep[0], keep[1]} : u32x4v{keep[0], keep[1], recv[0], recv[1]};
-              if (inside) *reinterpret_cast<u32x4v*>((hw ? lo_unit : hi_unit) + off) = unit;
+              const u32x4 unit = hw ? u32x4{recv[0], recv[1], keep[0], keep[1]} : u32x4{keep[0], keep[1], recv[0], recv[1]};
+              if (inside) *reinterpret_cast<u32x4*>((hw ? lo_unit : hi_unit) + off) = unit;
             } else {
-              *reinterpret_cast<u32x2v*>(hi_unit + off) = hi;
-              *reinterpret_cast<u32x2v*>(lo_unit + off) = lo;
+              *reinterpret_cast<u32x2*>(hi_unit + off) = hi;
+              *reinterpret_cast<u32x2*>(lo_unit + off) = lo;
             }
           }
         }

@@ -1,7 +1,7 @@
 // Device build of dft_mfma.h (the transforms of the frequency-domain 7x7 layer as matrix products on v_mfma_f32_32x32x16_f16,
 // precision "fftx3"): hardware hooks, kernel entry points, the constant-matrix builder and the launchers.  The kernel bodies
 // live in the header so that tests/host/dft_mfma_check.cpp can run the same source on the CPU (tests/host/spmd_emu.h).
-#include "os2d_common.h"
+#include "tile_common.h"
 #include <map>
 #include <mutex>
 #include <utility>
@@ -60,22 +60,22 @@ using namespace os2d_dft;
 // size behind uniform guards ($OS2D_DFT_SIZES=exact)
 template <bool TILED, bool FAST, int G, int NW, int KS>
 __global__ __launch_bounds__(NW * 64, 8 / NW) void dft_forward_kernel(const float* __restrict__ corr, const float* __restrict__ invn,
-                                                                      float* __restrict__ X, const u32x4v* __restrict__ FqT,
-                                                                      const u32x4v* __restrict__ Fp2, DftPlan pl, int C, int Cpad, int NBT,
+                                                                      float* __restrict__ X, const u32x4* __restrict__ FqT,
+                                                                      const u32x4* __restrict__ Fp2, DftPlan pl, int C, int Cpad, int NBT,
                                                                       int iters) {
   dft_forward_body<TILED, FAST, G, NW, KS>(corr, invn, X, FqT, Fp2, pl, C, Cpad, NBT, iters);
 }
 
 template <bool TILED, int KS, int G>
 __global__ __launch_bounds__(DFT_THR, 1) void dft_inverse_kernel(const float* __restrict__ Y, const float* __restrict__ bp, int MTP,
-                                                                 unsigned char* __restrict__ out, const u32x4v* __restrict__ E2,
-                                                                 const u32x4v* __restrict__ Gq, DftPlan pl, int Cout, int NBT, int PLANE,
+                                                                 unsigned char* __restrict__ out, const u32x4* __restrict__ E2,
+                                                                 const u32x4* __restrict__ Gq, DftPlan pl, int Cout, int NBT, int PLANE,
                                                                  int Ws, int BASE, int iters, Os2dRangeFlag status, int zero_borders) {
   dft_inverse_body<TILED, KS, G>(Y, bp, MTP, out, E2, Gq, pl, Cout, NBT, PLANE, Ws, BASE, iters, status, zero_borders);
 }
 
-typedef void (*dft_forward_fn)(const float*, const float*, float*, const u32x4v*, const u32x4v*, DftPlan, int, int, int, int);
-typedef void (*dft_inverse_fn)(const float*, const float*, int, unsigned char*, const u32x4v*, const u32x4v*, DftPlan, int, int, int, int, int,
+typedef void (*dft_forward_fn)(const float*, const float*, float*, const u32x4*, const u32x4*, DftPlan, int, int, int, int);
+typedef void (*dft_inverse_fn)(const float*, const float*, int, unsigned char*, const u32x4*, const u32x4*, DftPlan, int, int, int, int, int,
                                int, Os2dRangeFlag, int);
 template <int G, int NW, int KS>
 dft_forward_fn dft_forward_variant(const DftPlan& pl) {
@@ -112,22 +112,13 @@ dft_inverse_fn dft_inverse_pick(const DftPlan& pl) {
 
 // FqT | Fp2 | E2 | Gq of a (P, Q) transform, one thread per 16-byte unit
 __global__ __launch_bounds__(256) void dft_matrices_kernel(const double* __restrict__ twP, const double* __restrict__ twQ, int P, int Q,
-                                                           u32x4v* __restrict__ out) {
+                                                           u32x4* __restrict__ out) {
   const int n0 = dft_units_fqt(P, Q), n1 = n0 + dft_units_fp2(P, Q), n2 = n1 + dft_units_e2(P, Q), n3 = n2 + dft_units_gq(P, Q);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n3) return;
   const int which = i < n0 ? 0 : i < n1 ? 1 : i < n2 ? 2 : 3;
   const int base = which == 0 ? 0 : which == 1 ? n0 : which == 2 ? n1 : n2;
   dft_matrix_unit(which, i - base, P, Q, twP, twQ, out + i);
-}
-
-int dft_check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("%s launch: %s", what, hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
 }
 
 // The planner tries up to 48 x 48 tilings x 6 canonical sizes and a head call needs the plan of its map four times (workspace
@@ -164,7 +155,7 @@ bool dft_plan_cached(int H, int W, DftPlan* out, bool g8 = true) {
 
 int dft_grid(int iters, int per_cu = 1) {
   int g = iters < 256 * per_cu ? iters : 256 * per_cu;      // work-groups resident on the chip at once (126 - 137 KB of LDS each, or 2 x 80)
-  return (g + 7) / 8 * 8;                       // multiple of 8: XCD-aware iteration order
+  return os2d_round_up(g, 8);                   // multiple of 8: XCD-aware iteration order
 }
 
 }  // namespace
@@ -197,8 +188,8 @@ int os2d_launch_dft_matrices(const double* twP64, const double* twQ64, int P, in
     return -3;
   }
   const int n = (int)dft_matrices_units(P, Q);
-  hipLaunchKernelGGL(dft_matrices_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, twP64, twQ64, P, Q, static_cast<u32x4v*>(out));
-  return dft_check("dft_matrices");
+  hipLaunchKernelGGL(dft_matrices_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, twP64, twQ64, P, Q, static_cast<u32x4*>(out));
+  return os2d_launched("dft_matrices");
 }
 
 int os2d_launch_dft_forward(const float* corr, const float* inv, float* X, const void* matrices, int NB, int C, int Cpad, int H, int W,
@@ -216,17 +207,13 @@ int os2d_launch_dft_forward(const float* corr, const float* inv, float* X, const
   }
   const int CG = (C + G - 1) / G, NBT = NB * pl.T, iters = NBT * CG;
   pl.inv_cg = dft_magic((unsigned)CG);
-  const u32x4v* FqT = static_cast<const u32x4v*>(matrices);
-  const u32x4v* Fp2 = FqT + dft_units_fqt(pl.P, pl.Q);
+  const u32x4* FqT = static_cast<const u32x4*>(matrices);
+  const u32x4* Fp2 = FqT + dft_units_fqt(pl.P, pl.Q);
   auto kern = G == 8 ? dft_forward_pick<8, 8>(pl) : dft_forward_pick<4, 8>(pl);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_total);
-  if (e != hipSuccess) {
-    os2d_set_error("hipFuncSetAttribute(dft_forward): %s", hipGetErrorString(e));
-    return -4;
-  }
+  if (int rc = os2d_set_dynamic_lds(kern, pl.lds_total, "dft_forward")) return rc;
   hipLaunchKernelGGL(kern, dim3(dft_grid(iters)), dim3(DFT_THR), pl.lds_total, stream, corr, inv, X, FqT, Fp2, pl,
                      C, Cpad, NBT, iters);
-  return dft_check("dft_forward");
+  return os2d_launched("dft_forward");
 }
 
 // zero_borders != 0: the kernel also writes the zero border cells of the planes it fills (no os2d_launch_border_zero_shb_planes)
@@ -243,17 +230,13 @@ int os2d_launch_dft_inverse(const float* Y, const float* bp, int MTP, void* out,
   }
   const int OG = Cout / pl.G, NBT = NB * pl.T, iters = NBT * OG;
   pl.inv_og = dft_magic((unsigned)OG);
-  const u32x4v* E2 = static_cast<const u32x4v*>(matrices) + dft_units_fqt(pl.P, pl.Q) + dft_units_fp2(pl.P, pl.Q);
-  const u32x4v* Gq = E2 + dft_units_e2(pl.P, pl.Q);
+  const u32x4* E2 = static_cast<const u32x4*>(matrices) + dft_units_fqt(pl.P, pl.Q) + dft_units_fp2(pl.P, pl.Q);
+  const u32x4* Gq = E2 + dft_units_e2(pl.P, pl.Q);
   auto kern = dft_inverse_pick(pl);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds_total);
-  if (e != hipSuccess) {
-    os2d_set_error("hipFuncSetAttribute(dft_inverse): %s", hipGetErrorString(e));
-    return -4;
-  }
+  if (int rc = os2d_set_dynamic_lds(kern, pl.lds_total, "dft_inverse")) return rc;
   hipLaunchKernelGGL(kern, dim3(dft_grid(iters)), dim3(DFT_THR), pl.lds_total, stream, Y, bp, MTP, static_cast<unsigned char*>(out), E2, Gq,
                      pl, Cout, NBT, os2d_plane(H, W), os2d_ws(W), os2d_base(W), iters, status, zero_borders);
-  return dft_check("dft_inverse");
+  return os2d_launched("dft_inverse");
 }
 
 // diagnostic builds only (phase stamps, see above): copy the 16 phase counters to the host and optionally reset them

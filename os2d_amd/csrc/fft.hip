@@ -21,7 +21,7 @@
 // offset (3, 3) of the inverse transform and no wrap-around reaches them.  A tile is just one more "image" for all three
 // kernels: X is [C][NB * T][NBINS], Y is [NB * T][Cout][NBINS], pair' = nb * T + tile; the weight spectra depend on (P, Q)
 // only, so every map that tiles to the same transform size shares them.
-#include "os2d_common.h"
+#include "tile_common.h"
 #include <map>
 #include <mutex>
 #include <utility>
@@ -29,8 +29,6 @@
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 constexpr int FFT_THR = 512;
 constexpr int MAXPASS = 8;
@@ -348,12 +346,11 @@ __global__ __launch_bounds__(FFT_THR, FFT_EPT <= 10 ? 4 : 2) void fft_inverse_ke
   // GRP == 2 keeps the first channel of a pair as ONE register per cell (hi | lo << 16) and recombines at the second
   unsigned hreg[NACC][NR] = {}, lreg[GRP == 4 ? NACC : 1][NR] = {};
   const int ngroups = images / GRP, cells = TILED ? pl.TH * pl.TW : H * W;
-  // XCD-aware order (work-group L runs on XCD L % 8, one L2 per XCD): every XCD takes a contiguous range of channel
+  // XCD-aware order (tile_common.h): every XCD takes a contiguous range of channel
   // groups, so the 8 / GRP work-groups that fill the 16-byte units of one (class, 8-channel group) with their 4- / 8-byte
   // pieces run on ONE XCD at about the same time and the pieces merge in its L2 (with the round-robin order each piece
   // left a different L2 as a masked 32-byte write: 632 MB written for 183 MB of activations)
-  const int per_xcd = gridDim.x >> 3;                      // the launcher rounds the grid to a multiple of 8
-  const int first = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+  const int first = os2d_xcd_logical(blockIdx.x, gridDim.x);
   if (first < ngroups) FFT_PREFETCH_Y(first * GRP, tid)
   for (int it = first * GRP; it < images; it = ((it + 1) % GRP) ? it + 1 : (it / GRP + (int)gridDim.x) * GRP) {
     const int img = it;
@@ -646,15 +643,6 @@ bool make_plan_search(int H, int W, FftPlan* pl, size_t* lds) {
   return true;
 }
 
-int check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("%s launch: %s", what, hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
-}
-
 }  // namespace
 
 // P, Q and the padded number of bins (multiple of 8) of the transform of an H x W map (of ONE tile of it when the map is
@@ -688,18 +676,14 @@ int os2d_launch_fft_forward(const float* corr, const float* inv, float* X, const
   const int ept = (((pl.LH + 1) / 2) * pl.Q + FFT_THR - 1) / FFT_THR;
   auto kern = pl.T > 1 ? (ept <= 6 ? fft_forward_kernel<6, true> : ept <= 10 ? fft_forward_kernel<10, true> : fft_forward_kernel<14, true>)
                        : (ept <= 6 ? fft_forward_kernel<6, false> : ept <= 10 ? fft_forward_kernel<10, false> : fft_forward_kernel<14, false>);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    os2d_set_error("hipFuncSetAttribute(fft_forward): %s", hipGetErrorString(e));
-    return -4;
-  }
+  if (int rc = os2d_set_dynamic_lds(kern, lds, "fft_forward")) return rc;
   const int images = NB * C * pl.T;
   const int per_cu = (int)((160 * 1024) / lds) < 1 ? 1 : (int)((160 * 1024) / lds);
   const int grid = images < 256 * per_cu * 4 ? images : 256 * per_cu * 4;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(FFT_THR), lds, stream, corr, inv, reinterpret_cast<f32x2*>(X),
                      reinterpret_cast<const f32x2*>(twQ), reinterpret_cast<const f32x2*>(twP), pl, C, H, W,
                      os2d_round_up(pl.P * pl.V, 8), images);
-  return check("fft_forward");
+  return os2d_launched("fft_forward");
 }
 
 int os2d_launch_fft_inverse(const float* Y, const float* bp, int MTP, void* out, const float* twQ, const float* twP, int NB,
@@ -725,17 +709,13 @@ int os2d_launch_fft_inverse(const float* Y, const float* bp, int MTP, void* out,
                           : fft_inverse_kernel<14, 0, 1, T_>))
   auto kern = pl.T > 1 ? OS2D_INV_KERN(true) : OS2D_INV_KERN(false);
 #undef OS2D_INV_KERN
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    os2d_set_error("hipFuncSetAttribute(fft_inverse): %s", hipGetErrorString(e));
-    return -4;
-  }
+  if (int rc = os2d_set_dynamic_lds(kern, lds, "fft_inverse")) return rc;
   const int images = NB * pl.T * Cout, groups = grouped ? images / GRP : images;
   const int per_cu = (int)((160 * 1024) / lds) < 1 ? 1 : (int)((160 * 1024) / lds);
-  const int grid = ((groups < 256 * per_cu * 4 ? groups : 256 * per_cu * 4) + 7) / 8 * 8;   // multiple of 8 (XCD-aware order)
+  const int grid = os2d_round_up(groups < 256 * per_cu * 4 ? groups : 256 * per_cu * 4, 8);   // multiple of 8 (XCD-aware order)
   hipLaunchKernelGGL(kern, dim3(grid), dim3(FFT_THR), lds, stream, reinterpret_cast<const f32x2*>(Y), bp, MTP,
                      static_cast<char*>(out), reinterpret_cast<const f32x2*>(twQ), reinterpret_cast<const f32x2*>(twP), pl,
                      Cout, H, W, os2d_round_up(pl.P * pl.V, 8), os2d_plane(H, W), images,
                      (unsigned)(((1ull << 32) + pl.V - 1) / pl.V), status, layout ? 1 : 0, out_fp32 ? 1 : 0);
-  return check("fft_inverse");
+  return os2d_launched("fft_inverse");
 }

@@ -12,6 +12,7 @@
 //   phase 3  survivors are appended to the kept list.
 // Work ~ N * kept / 256 IoU tests per class instead of N^2 / 2, and nothing but the kept list (<= N boxes) is stored.
 #include "detect_common.h"
+#include "tile_common.h"
 
 namespace {
 
@@ -88,10 +89,5 @@ int os2d_launch_nms(const float* boxes, const int* counts, int NC, int N, float 
                     void* workspace, hipStream_t stream) {
   hipLaunchKernelGGL(nms_kernel, dim3(NC), dim3(256), 0, stream, reinterpret_cast<const float4*>(boxes), counts, N, thr,
                      keep, num_keep, reinterpret_cast<float4*>(workspace));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("nms launch: %s", hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
+  return os2d_launched("nms");
 }

@@ -4,7 +4,7 @@
 //   class_prepare  class feature map -> 15x15 bilinear resize + L2 normalisation + GEMM packing
 //                  (head.py:241-259, :293; the per-class constants an Os2dHead holds)
 //   pack_conv      fold eval-mode BatchNorm into a convolution and repack it for conv_mfma.hip
-#include "os2d_common.h"
+#include "tile_common.h"
 
 namespace {
 
@@ -205,7 +205,6 @@ __global__ __launch_bounds__(256) void class_normalize_batch_kernel(int C, int n
 // by border_zero_shb before.
 __global__ __launch_bounds__(256) void corr_normalize_shb_kernel(const float* __restrict__ corr, uint4* __restrict__ rshb,
                                                                  int H, int W, int PLANE) {
-  typedef _Float16 half8 __attribute__((ext_vector_type(8)));
   const int HW = H * W, Ws = os2d_ws(W);
   const int n = blockIdx.x * 256 + threadIdx.x;
   const int nb = blockIdx.y;
@@ -354,33 +353,24 @@ __global__ __launch_bounds__(256) void border_zero_shb_kernel(uint4* __restrict_
   }
 }
 
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("%s launch: %s", what, hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
-}
-
 }  // namespace
 
 int os2d_launch_fm_sumsq(const float* fm, float* sumsq, int A, int C, int HW, hipStream_t stream) {
   hipLaunchKernelGGL(fm_sumsq_kernel, dim3((HW + SUMSQ_POS - 1) / SUMSQ_POS, A), dim3(SUMSQ_LANES * SUMSQ_POS), 0, stream,
                      fm, sumsq, C, HW);
-  return check_launch("fm_sumsq");
+  return os2d_launched("fm_sumsq");
 }
 
 int os2d_launch_border_zero(float* rpad, int planes_total, int H, int W, hipStream_t stream) {
   hipLaunchKernelGGL(border_zero_kernel, dim3(planes_total), dim3(256), 0, stream, rpad, H, W, os2d_plane(H, W));
-  return check_launch("border_zero");
+  return os2d_launched("border_zero");
 }
 
 int os2d_launch_border_zero_shb_planes_norms(void* buf, int planes, int H, int W, void* sumfx, float* invn, size_t n, hipStream_t stream) {
   const size_t extra = sumfx ? (n + 255) / 256 : 0;
   hipLaunchKernelGGL(border_zero_shb_kernel, dim3((unsigned)(planes + extra)), dim3(256), 0, stream, reinterpret_cast<uint4*>(buf), H, W,
                      os2d_plane(H, W), planes, static_cast<unsigned long long*>(sumfx), invn, sumfx ? n : (size_t)0);
-  return check_launch("border_zero_shb");
+  return os2d_launched("border_zero_shb");
 }
 
 int os2d_launch_border_zero_shb(void* rnorm, int NB, int H, int W, hipStream_t stream) {
@@ -397,7 +387,7 @@ int os2d_launch_pack_conv_f16(const float* w, const float* b, const float* bn_w,
                               hipStream_t stream) {
   hipLaunchKernelGGL(pack_conv_f16_kernel, dim3(1024), dim3(256), 0, stream, w, b, bn_w, bn_b, bn_mean, bn_var, bn_eps,
                      Cout, Cin, KS, MT, steps_padded, wexp, in_exp, out_exp, reinterpret_cast<_Float16*>(wp), bp);
-  return check_launch("pack_conv_f16");
+  return os2d_launched("pack_conv_f16");
 }
 
 int os2d_launch_corr_normalize(const float* corr, float* rpad, int NB, int H, int W, hipStream_t stream) {
@@ -405,12 +395,12 @@ int os2d_launch_corr_normalize(const float* corr, float* rpad, int NB, int H, in
   if (rc) return rc;
   hipLaunchKernelGGL(corr_normalize_kernel, dim3((H * W + 255) / 256, NB), dim3(256), 0, stream, corr, rpad, H, W,
                      os2d_plane(H, W));
-  return check_launch("corr_normalize");
+  return os2d_launched("corr_normalize");
 }
 
 int os2d_launch_class_prepare(const float* src, int C, int h, int w, int normalize, float* q15, float* qp, hipStream_t stream) {
   hipLaunchKernelGGL(class_prepare_kernel, dim3(OS2D_K), dim3(256), 0, stream, src, C, h, w, normalize, q15, qp);
-  return check_launch("class_prepare");
+  return os2d_launched("class_prepare");
 }
 
 int os2d_class_prepare_partial_floats(int B, int C) { return B * ((C + CPB - 1) / CPB) * OS2D_K; }
@@ -419,10 +409,10 @@ int os2d_launch_class_prepare_batch(const float* const* srcs, const int* sizes, 
                                     float* qp, float* partial, hipStream_t stream) {
   const int nblocks = (C + CPB - 1) / CPB;
   hipLaunchKernelGGL(class_resize_batch_kernel, dim3(nblocks, B), dim3(256), 0, stream, srcs, sizes, C, q15, qp, partial);
-  int rc = check_launch("class_resize_batch");
+  int rc = os2d_launched("class_resize_batch");
   if (rc || !normalize) return rc;
   hipLaunchKernelGGL(class_normalize_batch_kernel, dim3(nblocks, B), dim3(256), 0, stream, C, nblocks, q15, qp, partial);
-  return check_launch("class_normalize_batch");
+  return os2d_launched("class_normalize_batch");
 }
 
 int os2d_launch_corr_normalize_shb(const float* corr, void* rshb, int NB, int H, int W, hipStream_t stream) {
@@ -430,7 +420,7 @@ int os2d_launch_corr_normalize_shb(const float* corr, void* rshb, int NB, int H,
   if (rc) return rc;
   hipLaunchKernelGGL(corr_normalize_shb_kernel, dim3((H * W + 255) / 256, NB), dim3(256), 0, stream, corr,
                      reinterpret_cast<uint4*>(rshb), H, W, os2d_plane(H, W));
-  return check_launch("corr_normalize_shb");
+  return os2d_launched("corr_normalize_shb");
 }
 
 int os2d_launch_pack_conv(const float* w, const float* b, const float* bn_w, const float* bn_b, const float* bn_mean,
@@ -438,5 +428,5 @@ int os2d_launch_pack_conv(const float* w, const float* b, const float* bn_w, con
                           hipStream_t stream) {
   hipLaunchKernelGGL(pack_conv_kernel, dim3(512), dim3(256), 0, stream, w, b, bn_w, bn_b, bn_mean, bn_var, bn_eps,
                      Cout, Cin, KS, MT, wp, bp);
-  return check_launch("pack_conv");
+  return os2d_launched("pack_conv");
 }

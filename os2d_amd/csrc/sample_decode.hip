@@ -14,7 +14,7 @@
 // One thread per location, consecutive lanes = consecutive w: the 4 bilinear taps of neighbouring lanes
 // fall in the same or adjacent cache lines of one correlation channel (the transforms vary smoothly), so
 // each of the 121x4 gathers is a near-coalesced L2 read of the 4.3 MB per-class correlation block.
-#include "os2d_common.h"
+#include "tile_common.h"
 #include "detect_common.h"
 #include "sample_decode.h"
 
@@ -103,12 +103,7 @@ int os2d_launch_sample_decode(const float* corr, const float* params, int NB, in
   dim3 grid((H * W + 255) / 256, NB);
   hipLaunchKernelGGL(sample_decode_kernel, grid, dim3(256), 0, stream, corr, params, H, W, P, inverse, (float)stride,
                      half_box, Bc, Btot, b0, loc, cls, corners, flags, NB / Bc, epoch, host_status);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("sample_decode launch: %s", hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
+  return os2d_launched("sample_decode");
 }
 
 int os2d_launch_decode_boxes(const float* loc, int NB, int H, int W, int stride, int rec_field, float img_w,
@@ -117,22 +112,12 @@ int os2d_launch_decode_boxes(const float* loc, int NB, int H, int W, int stride,
   dim3 grid((H * W + 255) / 256, NB);
   hipLaunchKernelGGL(decode_boxes_kernel, grid, dim3(256), 0, stream, loc, H, W, (float)stride, half_box, img_w,
                      img_h, boxes);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("decode_boxes launch: %s", hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
+  return os2d_launched("decode_boxes");
 }
 
 int os2d_launch_alignment_grids(const float* params, int NB, int H, int W, int P, int inverse, float* theta,
                                 float* grids, hipStream_t stream) {
   dim3 grid((H * W + 255) / 256, NB);
   hipLaunchKernelGGL(alignment_grids_kernel, grid, dim3(256), 0, stream, params, H * W, P, inverse, theta, grids);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("alignment_grids launch: %s", hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
+  return os2d_launched("alignment_grids");
 }

@@ -16,7 +16,7 @@
 //   OS2D_PRECISION_FFTX3  [bins/8][2 halves of 64 out-ch][ceil(C/8) k-steps][8 bins][2 channel groups][hi|lo][64] units of
 //                         8 halves = (Kr, Ki) of 4 channels, followed by 128 floats 2^-wexp[o]   (spectral_f16.hip)
 //   OS2D_PRECISION_FFT    [bins/8][2][C][8 bins][64] complex64                                    (spectral.hip)
-#include "os2d_common.h"
+#include "tile_common.h"
 
 namespace {
 
@@ -127,15 +127,6 @@ __global__ __launch_bounds__(SP_THR) void spectra_pack_kernel(const double* __re
   }
 }
 
-int sp_check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("%s launch: %s", what, hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
-}
-
 }  // namespace
 
 // wfold: DEVICE double [Cout <= 128][C][7][7]; twP64 / twQ64: DEVICE double [P][2] / [Q][2] = (cos, sin) of -2 pi m / n;
@@ -160,14 +151,14 @@ int os2d_launch_spectra_pack(const double* wfold, const double* twP64, const dou
     }
     hipLaunchKernelGGL(spectra_pack_kernel<0>, grid, dim3(SP_THR), lds, stream, wfold, twP64, twQ64, C, Cout, P, Q, NBINS, per, amax,
                        nullptr, nullptr, u_fastest);
-    int rc = sp_check("spectra_pack (row maxima)");
+    int rc = os2d_launched("spectra_pack (row maxima)");
     if (rc) return rc;
     float* wscale = reinterpret_cast<float*>(static_cast<char*>(out) + (size_t)(NBINS / 8) * 2 * KSTEPS * 8 * 256 * 16);
     hipLaunchKernelGGL(spectra_pack_kernel<1>, grid, dim3(SP_THR), lds, stream, wfold, twP64, twQ64, C, Cout, P, Q, NBINS, per, amax,
                        out, wscale, u_fastest);
-    return sp_check("spectra_pack (split)");
+    return os2d_launched("spectra_pack (split)");
   }
   hipLaunchKernelGGL(spectra_pack_kernel<2>, grid, dim3(SP_THR), lds, stream, wfold, twP64, twQ64, C, Cout, P, Q, NBINS, per, nullptr,
                      out, nullptr, u_fastest);
-  return sp_check("spectra_pack (complex64)");
+  return os2d_launched("spectra_pack (complex64)");
 }

@@ -14,12 +14,10 @@
 // double-buffered LDS: the weights (packed [bin group][o half][c][bin][o], 36 KB per chunk, contiguous) arrive by LDS-DMA,
 // the spectra (natural layout [class][c][bin]: 64-byte pieces) through registers with the transposition to [c][bin][class]
 // on the way, so every fragment read is a conflict-free ds_read_b64 of 64 consecutive complex numbers.
-#include "os2d_common.h"
+#include "tile_common.h"
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SG_BINS = 8;     // bins per group of the packed weight layout
 constexpr int SG_CC = 9;       // channels per K chunk (225 = 25 * 9)
@@ -53,12 +51,11 @@ __global__ __launch_bounds__(SG_THR, 2) void spectral_gemm_kernel(const f32x2* w
   f32x2* ldsX = reinterpret_cast<f32x2*>(smem + 2 * SG_WUNITS * 16);                 // [2][CC][8][64]
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hw = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // XCD-aware order (work-group L runs on XCD L % 8; each XCD has its own L2): every XCD takes a contiguous range of
+  // XCD-aware order (tile_common.h): every XCD takes a contiguous range of
   // logical indices = (bin group, class tile, o half, part of the bin group), last fastest.  The work-groups that share
   // cache lines run on one XCD at about the same time: the parts / halves of a bin group share the input spectra, the
   // class tiles of a bin group share the weight spectra (which therefore leave HBM once, not once per class tile)
-  const int per = gridDim.x >> 3;
-  const int lidx = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+  const int lidx = os2d_xcd_logical(blockIdx.x, gridDim.x);
   constexpr int SUB = NBLK == 2 ? 1 : 4;                 // work-groups per unit
   if (lidx >= nunits * SUB) return;
   const int logical = unit0 + lidx / SUB, sub = lidx % SUB;
@@ -80,8 +77,6 @@ __global__ __launch_bounds__(SG_THR, 2) void spectral_gemm_kernel(const f32x2* w
         yi[a][b][r] = 0.f;
       }
 
-  typedef const void __attribute__((address_space(1))) * gptr_t;
-  typedef void __attribute__((address_space(3))) * lptr_t;
   const char* wbase = reinterpret_cast<const char*>(wspec) + (((size_t)(g * 2 + half) * C) * SG_BINS + bh * SG_WB) * SG_OH * 8;
   u32x4 pfx[SG_XPF];
 
@@ -93,9 +88,8 @@ __global__ __launch_bounds__(SG_THR, 2) void spectral_gemm_kernel(const f32x2* w
     const char* src_ = wbase + (size_t)c0_ * SG_BINS * SG_OH * 8;                                                 \
     for (int u_ = wv * 64; u_ < units_; u_ += SG_THR) {                                                           \
       const int cl_ = u_ / (SG_WB * 32), r_ = u_ % (SG_WB * 32);                                                  \
-      __builtin_amdgcn_global_load_lds((gptr_t)(src_ + ((size_t)cl_ * SG_BINS * 32 + r_ + lane) * 16),            \
-                                       (lptr_t)(reinterpret_cast<char*>(ldsW) + (((T)&1) * SG_WUNITS + u_) * 16), \
-                                       16, 0, 0);                                                                 \
+      os2d_lds_dma16(src_ + ((size_t)cl_ * SG_BINS * 32 + r_ + lane) * 16,                                        \
+                     reinterpret_cast<char*>(ldsW) + (((T)&1) * SG_WUNITS + u_) * 16);                            \
     }                                                                                                             \
   }
   // spectra of chunk t: unit u = (c, class, bin pair); out-of-range classes / channels read a valid address and are
@@ -212,13 +206,9 @@ int os2d_launch_spectral_gemm(const float* wspec, const float* X, float* Y, int 
   }
   const int G = NBINS / SG_BINS, nbt = (NB + SG_NB - 1) / SG_NB;
   const size_t lds = (size_t)(2 * SG_WUNITS + 2 * SG_XUNITS) * 16;
-  for (const void* k : {reinterpret_cast<const void*>(spectral_gemm_kernel<2>), reinterpret_cast<const void*>(spectral_gemm_kernel<1>)}) {
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      os2d_set_error("hipFuncSetAttribute(spectral_gemm): %s", hipGetErrorString(e));
-      return -4;
-    }
-  }
+  int rc = os2d_set_dynamic_lds(spectral_gemm_kernel<2>, lds, "spectral_gemm");
+  if (!rc) rc = os2d_set_dynamic_lds(spectral_gemm_kernel<1>, lds, "spectral_gemm");
+  if (rc) return rc;
   // units = (class tile, bin group, o half, part of the bin group); 8 / WB units fill a CU.  Whole rounds of the resident
   // work-groups go to the full-tile kernel; what is left (2 % of the work at 64 classes, which would cost a whole extra
   // round) is cut into 32 x 32 quarters so that the tail takes a quarter of a round.
@@ -230,20 +220,16 @@ int os2d_launch_spectral_gemm(const float* wspec, const float* X, float* Y, int 
   const f32x2* w = reinterpret_cast<const f32x2*>(wspec);
   const f32x2* x = reinterpret_cast<const f32x2*>(X);
   f32x2* y = reinterpret_cast<f32x2*>(Y);
+  unsigned grid;
   if (main_units > 0) {
-    dim3 grid((unsigned)((main_units + 7) / 8 * 8));
-    hipLaunchKernelGGL(spectral_gemm_kernel<2>, grid, dim3(SG_THR), lds, stream, w, x, y, NB, C, Cout, NBINS, G, 0, (int)main_units);
+    if ((rc = os2d_xcd_grid(main_units, "spectral_gemm", &grid))) return rc;
+    hipLaunchKernelGGL(spectral_gemm_kernel<2>, dim3(grid), dim3(SG_THR), lds, stream, w, x, y, NB, C, Cout, NBINS, G, 0, (int)main_units);
   }
   if (units > main_units) {
     const long long tail = units - main_units;
-    dim3 grid((unsigned)((tail * 4 + 7) / 8 * 8));
-    hipLaunchKernelGGL(spectral_gemm_kernel<1>, grid, dim3(SG_THR), lds, stream, w, x, y, NB, C, Cout, NBINS, G, (int)main_units,
+    if ((rc = os2d_xcd_grid(tail * 4, "spectral_gemm", &grid))) return rc;
+    hipLaunchKernelGGL(spectral_gemm_kernel<1>, dim3(grid), dim3(SG_THR), lds, stream, w, x, y, NB, C, Cout, NBINS, G, (int)main_units,
                        (int)tail);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("spectral_gemm launch: %s", hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
+  return os2d_launched("spectral_gemm");
 }

@@ -30,15 +30,10 @@
 //     X [c][pair][bin]: in quads this kernel's loads were 0.03 ms cheaper per 64 pairs, but the forward transform's stores
 //     (688 pieces of 32 bytes per image, 460 KB apart) 0.04 ms dearer (profiles/r03_spectral_layouts.txt).
 // XCD-aware order: the pair tiles of a bin group (which share the weight spectra) run on one XCD at about the same time.
-#include "os2d_common.h"
+#include "tile_common.h"
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 constexpr int SH_THR = 512;
 constexpr int SH_WB = 4;        // bins per work-group
@@ -70,8 +65,7 @@ __global__ __launch_bounds__(SH_THR, 1) void spectral_gemm_f16_kernel(const u32x
   u32x4* ldsX = ldsW + SH_WRING * SH_WSTAGE;                    // [2][SH_STAGE]
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hw = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int per = gridDim.x >> 3;
-  const int lidx = (blockIdx.x & 7) * per + (blockIdx.x >> 3);   // XCD-aware order
+  const int lidx = os2d_xcd_logical(blockIdx.x, gridDim.x);
   if (lidx >= nunits) return;
   constexpr int NBH = SH_BINS / SH_WB;
   const int bh = lidx % NBH, lg = lidx / NBH;
@@ -313,21 +307,13 @@ int os2d_launch_spectral_gemm_f16(const void* w16, const float* X, float* Y, int
     return -1;
   }
   auto kern = x_quads ? spectral_gemm_f16_kernel<true> : spectral_gemm_f16_kernel<false>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    os2d_set_error("hipFuncSetAttribute(spectral_gemm_f16): %s", hipGetErrorString(e));
-    return -4;
-  }
+  if (int rc = os2d_set_dynamic_lds(kern, lds, "spectral_gemm_f16")) return rc;
   const long long units = (long long)G * nbt * (SH_BINS / SH_WB);
   const size_t KS = (size_t)(C + SH_KC - 1) / SH_KC;
   const float* wscale = reinterpret_cast<const float*>(static_cast<const char*>(w16) + (size_t)G * 2 * KS * SH_BINS * 256 * 16);
-  dim3 grid((unsigned)((units + 7) / 8 * 8));
-  hipLaunchKernelGGL(kern, grid, dim3(SH_THR), lds, stream, static_cast<const u32x4*>(w16), wscale,
+  unsigned grid;
+  if (int rc = os2d_xcd_grid(units, "spectral_gemm_f16", &grid)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(SH_THR), lds, stream, static_cast<const u32x4*>(w16), wscale,
                      reinterpret_cast<const f32x2*>(X), reinterpret_cast<f32x2*>(Y), NB, C, Cpad, Cout, NBINS, G, xscale, (int)units);
-  e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("spectral_gemm_f16 launch: %s", hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
+  return os2d_launched("spectral_gemm_f16");
 }

@@ -35,17 +35,6 @@ void set_error(const char* fmt, ...) {
   os2d_train_store_error(buf);
 }
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: %s", what, hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
-}
-
 // flags byte of one element
 constexpr unsigned char F_POS = 1;      // positive of the class loss (remapped targets when given)
 constexpr unsigned char F_NEG = 2;      // negative that enters the class loss (after mining)

@@ -27,17 +27,6 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: %s", what, hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
-}
-
 struct Layer {
   int cout, cin, ks;
 };

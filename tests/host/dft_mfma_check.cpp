@@ -64,13 +64,13 @@ static int check_case(int H, int W, int C, int NB, int grid) {
   std::printf("case %dx%d C=%d NB=%d: P=%d Q=%d bins=%d tiles=%dx%d (%dx%d) window %dx%d lds=%d fast=%d\n", H, W, C, NB, P, Q, pl.NBINS,
               pl.TY, pl.TX, pl.TH, pl.TW, pl.LH, pl.LW, pl.lds_total, pl.fast);
   const std::vector<double> tp = table(P), tq = table(Q);
-  std::vector<u32x4v> mats(dft_matrices_units(P, Q));
+  std::vector<u32x4> mats(dft_matrices_units(P, Q));
   const int nf = dft_units_fqt(P, Q), n2 = dft_units_fp2(P, Q), ne = dft_units_e2(P, Q), ng = dft_units_gq(P, Q);
   for (int i = 0; i < nf; ++i) dft_matrix_unit(0, i, P, Q, tp.data(), tq.data(), &mats[i]);
   for (int i = 0; i < n2; ++i) dft_matrix_unit(1, i, P, Q, tp.data(), tq.data(), &mats[nf + i]);
   for (int i = 0; i < ne; ++i) dft_matrix_unit(2, i, P, Q, tp.data(), tq.data(), &mats[nf + n2 + i]);
   for (int i = 0; i < ng; ++i) dft_matrix_unit(3, i, P, Q, tp.data(), tq.data(), &mats[nf + n2 + ne + i]);
-  const u32x4v *FqT = mats.data(), *Fp2 = FqT + nf, *E2 = Fp2 + n2, *Gq = E2 + ne;
+  const u32x4 *FqT = mats.data(), *Fp2 = FqT + nf, *E2 = Fp2 + n2, *Gq = E2 + ne;
 
   // ---------------- forward
   unsigned seed = 12345u + H * 131 + W;
