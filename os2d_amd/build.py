@@ -3,6 +3,7 @@
     python -m os2d_amd.build                      # build if stale
     python -m os2d_amd.build --force
     python -m os2d_amd.build --train              # only libos2d_train.so (the head's backward pass)
+    python -m os2d_amd.build --eval               # only libos2d_eval.so (the VOC detection metric)
     python -m os2d_amd.build --variant TAG [--packed on|off|fft] [-DFLAG ...]
                                                   # diagnostic copy under tools/diag_libs/TAG/ (run with OS2D_HIP_LIB=...)
 """
@@ -44,6 +45,16 @@ TRAIN_FLAGS = FLAGS + PACKED_OFF
 # objective.hip restates the reference's IoU and box encoding operation for operation: a fused multiply-add would round
 # differently from the CPU reference
 TRAIN_UNIT_FLAGS = {"objective.hip": ["-ffp-contract=off"]}
+
+# The VOC evaluation (include/os2d_eval.h) is a third library: the kernel list of libos2d_hip.so and the ABI of
+# libos2d_train.so stay what they are.  Its units may include csrc/detect_common.h for the score sort key.
+EVAL_CSRC = os.path.join(HERE, "csrc_eval")
+EVAL_SOURCES = ["match.hip", "sort.hip", "metric.hip"]
+EVAL_LIB_PATH = os.path.join(LIB_DIR, "libos2d_eval.so")
+EVAL_BUILD_DIR = os.path.join(EVAL_CSRC, "build")
+# the IoU of the match step must have the bits of the reference's CPU arithmetic, and the area under the curve is a sum of
+# separately rounded products: no fused multiply-adds in any unit
+EVAL_FLAGS = FLAGS + PACKED_OFF + ["-ffp-contract=off"]
 
 
 def headers():
@@ -151,6 +162,7 @@ def build(force=False, verbose=True):
             f.write(digest + "\n")
         os.replace(STAMP_PATH + ".tmp", STAMP_PATH)
     build_train(force=force, verbose=verbose)
+    build_eval(force=force, verbose=verbose)
     return LIB_PATH
 
 
@@ -207,6 +219,57 @@ def build_train(force=False, verbose=True):
     return TRAIN_LIB_PATH
 
 
+def eval_headers():
+    return sorted(glob.glob(os.path.join(EVAL_CSRC, "*.h"))) + headers() + [os.path.join(HERE, "..", "include", "os2d_eval.h")]
+
+
+def eval_source_hash():
+    h = hashlib.sha256((" ".join(EVAL_FLAGS) + "\n").encode())
+    for path in [os.path.join(EVAL_CSRC, s) for s in EVAL_SOURCES] + eval_headers():
+        h.update(os.path.basename(path).encode())
+        with open(path, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()
+
+
+def eval_up_to_date():
+    stamp = EVAL_LIB_PATH + ".srchash"
+    if not (os.path.exists(EVAL_LIB_PATH) and os.path.exists(stamp)):
+        return False
+    with open(stamp) as f:
+        return f.read().strip() == eval_source_hash()
+
+
+def build_eval(force=False, verbose=True):
+    """Compile the evaluation units for gfx950 and link libos2d_eval.so.  Returns its path."""
+    if not force and eval_up_to_date():
+        return EVAL_LIB_PATH
+    hipcc = _hipcc()
+    os.makedirs(LIB_DIR, exist_ok=True)
+    os.makedirs(EVAL_BUILD_DIR, exist_ok=True)
+    procs, objs = [], []
+    for s in EVAL_SOURCES:
+        obj = os.path.join(EVAL_BUILD_DIR, s.replace(".hip", ".o"))
+        objs.append(obj)
+        cmd = [hipcc] + EVAL_FLAGS + ["-c", os.path.join(EVAL_CSRC, s), "-o", obj]
+        if verbose:
+            print("[os2d_amd.build]", " ".join(cmd), flush=True)
+        procs.append((cmd, subprocess.Popen(cmd)))
+    _wait(procs)
+    digest = eval_source_hash()
+    tmp = EVAL_LIB_PATH + ".tmp.{}".format(os.getpid())
+    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", tmp] + objs
+    if verbose:
+        print("[os2d_amd.build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    os.replace(tmp, EVAL_LIB_PATH)
+    stamp = EVAL_LIB_PATH + ".srchash"
+    with open(stamp + ".tmp", "w") as f:
+        f.write(digest + "\n")
+    os.replace(stamp + ".tmp", stamp)
+    return EVAL_LIB_PATH
+
+
 def build_variant(tag, packed=None, extra=(), verbose=False):
     """A DIAGNOSTIC copy of the library (other flags, -DOS2D_DIAG_... switches) under tools/diag_libs/<tag>/; the product
     library is untouched.  Built HERE (hipcc cross-compiles) so that a GPU call spends its minutes measuring:
@@ -231,5 +294,7 @@ if __name__ == "__main__":
         print(build_variant(tag, packed, [a for a in argv if a.startswith("-D")], verbose=True))
     elif "--train" in argv:
         print(build_train(force="--force" in argv))
+    elif "--eval" in argv:
+        print(build_eval(force="--force" in argv))
     else:
         print(build(force="--force" in argv))

@@ -1,6 +1,7 @@
 """The caller of the hot path, rebuilt for the class-batched HIP head: what the reference's
 ``make_iterator_extract_scores_from_images_batched`` (os2d/engine/evaluate.py:177-371) and the decode step of
-``evaluate`` (:99-117) do for one image, minus datasets / dataloaders / mAP (out of scope).
+``evaluate`` (:99-117) do for one image, and the metric at the end of ``evaluate`` (:151-171), minus datasets /
+dataloaders / loss meters (out of scope).
 
     class_image_views  reference evaluate.py:241-269  class-image augmentation (rotation90 / horflip / both): every
                        view becomes one more row of the class-batched head, NMS merges the views of a class
@@ -10,7 +11,11 @@
     detect             reference evaluate.py:99-117   + Os2dBoxCoder.decode_pyramid (decode, clip, NMS, merge levels)
     detect_images      reference evaluate.py:278-371  the per-image loop, with the next image's host-to-device copy
                        prefetched on a side stream
+    evaluate           reference evaluate.py:151-171  detect_images + the VOC metric on the device (engine/voc_eval.py):
+                       mAP, weighted mAP, recall and joint-classes AP per IoU threshold
 """
+import time
+
 from collections import OrderedDict
 
 import torch
@@ -18,6 +23,7 @@ import torch
 from ..modeling.box_coder import ResizeBoxes
 from ..structures.feature_map import FeatureMapSize
 from .pyramid import PyramidHeadRunner
+from .voc_eval import VocEvaluator
 
 
 CLASS_IMAGE_AUGMENTATIONS = ("", "rotation90", "horflip", "horflip_rotation90")
@@ -134,3 +140,36 @@ def detect_images(net, box_coder, image_pyramids, class_head, class_ids, orig_si
         orig = orig_sizes[index] if orig_sizes is not None else None
         yield detect(net, box_coder, levels, class_head, class_ids, orig_size=orig, **detect_kwargs)
         index += 1
+
+
+def evaluate(net, box_coder, image_pyramids, gt_boxes, class_head, class_ids, orig_sizes=None, mAP_iou_thresholds=(0.5,),
+             **detect_kwargs):
+    """Detections of every image (``detect_images``) followed by the VOC metric, as the end of the reference's ``evaluate``
+    (evaluate.py:151-171).  ``gt_boxes``: one ``BoxList`` per image with field "labels" (and optionally "difficult"), on the
+    host or the device.  The detections never leave the device: each image's ``BoxList`` goes into a ``VocEvaluator``, the
+    sort is shared by all thresholds, and the scalars of all thresholds come back in one transfer at the end.  Returns a dict
+    of floats: ``mAP@t``, ``mAPw@t``, ``recall@t``, ``AP_joint_classes@t`` per threshold (t as ``{:0.2f}``) and ``eval_time``
+    in seconds."""
+    t_start = time.time()
+    gt_boxes = list(gt_boxes)
+    host_labels = [int(g.get_field("labels").max()) for g in gt_boxes if len(g) and not g.get_field("labels").is_cuda]
+    evaluator = VocEvaluator(num_labels=max([int(c) for c in class_ids] + host_labels) + 1)
+    with torch.no_grad():
+        for boxes, gt in zip(detect_images(net, box_coder, image_pyramids, class_head, class_ids, orig_sizes=orig_sizes, **detect_kwargs),
+                             gt_boxes):
+            evaluator.add(boxes, gt)
+    if len(evaluator) != len(gt_boxes):
+        raise RuntimeError("evaluate: {} images but {} ground-truth box lists".format(len(evaluator), len(gt_boxes)))
+    scalars = []
+    for t in mAP_iou_thresholds:
+        r = evaluator.compute(iou_thresh=t, use_07_metric=False, with_curves=False)
+        scalars.append(torch.stack([r["map"], r["map_weighted"], r["recall"], r["ap_joint_classes"]]))
+    values = torch.stack(scalars).cpu().tolist() if scalars else []
+    losses = OrderedDict()
+    for t, (m, mw, rec, joint) in zip(mAP_iou_thresholds, values):
+        losses["mAP@{:0.2f}".format(t)] = m
+        losses["mAPw@{:0.2f}".format(t)] = mw
+        losses["recall@{:0.2f}".format(t)] = rec
+        losses["AP_joint_classes@{:0.2f}".format(t)] = joint
+    losses["eval_time"] = time.time() - t_start
+    return losses
