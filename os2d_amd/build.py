@@ -4,6 +4,7 @@
     python -m os2d_amd.build --force
     python -m os2d_amd.build --train              # only libos2d_train.so (the head's backward pass)
     python -m os2d_amd.build --eval               # only libos2d_eval.so (the VOC detection metric)
+    python -m os2d_amd.build --image              # only libos2d_image.so (the image pyramid from uint8 images)
     python -m os2d_amd.build --variant TAG [--packed on|off|fft] [-DFLAG ...]
                                                   # diagnostic copy under tools/diag_libs/TAG/ (run with OS2D_HIP_LIB=...)
 """
@@ -55,6 +56,14 @@ EVAL_BUILD_DIR = os.path.join(EVAL_CSRC, "build")
 # the IoU of the match step must have the bits of the reference's CPU arithmetic, and the area under the curve is a sum of
 # separately rounded products: no fused multiply-adds in any unit
 EVAL_FLAGS = FLAGS + PACKED_OFF + ["-ffp-contract=off"]
+
+# The image pyramid from uint8 images (include/os2d_image.h) is a fourth library, for the same reason.  Integer arithmetic and a
+# table lookup: no floating-point operation whose rounding a flag could change.
+IMAGE_CSRC = os.path.join(HERE, "csrc_image")
+IMAGE_SOURCES = ["resample.hip"]
+IMAGE_LIB_PATH = os.path.join(LIB_DIR, "libos2d_image.so")
+IMAGE_BUILD_DIR = os.path.join(IMAGE_CSRC, "build")
+IMAGE_FLAGS = FLAGS + PACKED_OFF
 
 
 def headers():
@@ -163,6 +172,7 @@ def build(force=False, verbose=True):
         os.replace(STAMP_PATH + ".tmp", STAMP_PATH)
     build_train(force=force, verbose=verbose)
     build_eval(force=force, verbose=verbose)
+    build_image(force=force, verbose=verbose)
     return LIB_PATH
 
 
@@ -270,6 +280,58 @@ def build_eval(force=False, verbose=True):
     return EVAL_LIB_PATH
 
 
+def image_headers():
+    """(its units include none of csrc/*.h)"""
+    return sorted(glob.glob(os.path.join(IMAGE_CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "os2d_image.h")]
+
+
+def image_source_hash():
+    h = hashlib.sha256((" ".join(IMAGE_FLAGS) + "\n").encode())
+    for path in [os.path.join(IMAGE_CSRC, s) for s in IMAGE_SOURCES] + image_headers():
+        h.update(os.path.basename(path).encode())
+        with open(path, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()
+
+
+def image_up_to_date():
+    stamp = IMAGE_LIB_PATH + ".srchash"
+    if not (os.path.exists(IMAGE_LIB_PATH) and os.path.exists(stamp)):
+        return False
+    with open(stamp) as f:
+        return f.read().strip() == image_source_hash()
+
+
+def build_image(force=False, verbose=True):
+    """Compile the image units for gfx950 and link libos2d_image.so.  Returns its path."""
+    if not force and image_up_to_date():
+        return IMAGE_LIB_PATH
+    hipcc = _hipcc()
+    os.makedirs(LIB_DIR, exist_ok=True)
+    os.makedirs(IMAGE_BUILD_DIR, exist_ok=True)
+    procs, objs = [], []
+    for s in IMAGE_SOURCES:
+        obj = os.path.join(IMAGE_BUILD_DIR, s.replace(".hip", ".o"))
+        objs.append(obj)
+        cmd = [hipcc] + IMAGE_FLAGS + ["-c", os.path.join(IMAGE_CSRC, s), "-o", obj]
+        if verbose:
+            print("[os2d_amd.build]", " ".join(cmd), flush=True)
+        procs.append((cmd, subprocess.Popen(cmd)))
+    _wait(procs)
+    digest = image_source_hash()
+    tmp = IMAGE_LIB_PATH + ".tmp.{}".format(os.getpid())
+    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", tmp] + objs
+    if verbose:
+        print("[os2d_amd.build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    os.replace(tmp, IMAGE_LIB_PATH)
+    stamp = IMAGE_LIB_PATH + ".srchash"
+    with open(stamp + ".tmp", "w") as f:
+        f.write(digest + "\n")
+    os.replace(stamp + ".tmp", stamp)
+    return IMAGE_LIB_PATH
+
+
 def build_variant(tag, packed=None, extra=(), verbose=False):
     """A DIAGNOSTIC copy of the library (other flags, -DOS2D_DIAG_... switches) under tools/diag_libs/<tag>/; the product
     library is untouched.  Built HERE (hipcc cross-compiles) so that a GPU call spends its minutes measuring:
@@ -296,5 +358,7 @@ if __name__ == "__main__":
         print(build_train(force="--force" in argv))
     elif "--eval" in argv:
         print(build_eval(force="--force" in argv))
+    elif "--image" in argv:
+        print(build_image(force="--force" in argv))
     else:
         print(build(force="--force" in argv))

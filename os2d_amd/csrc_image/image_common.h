@@ -1,0 +1,30 @@
+// Shared by the translation units of libos2d_image.so: the error store, launch plumbing and the tile geometry (the library
+// links against none of the other three, so it carries its own error store as libos2d_eval.so does).
+#ifndef OS2D_IMAGE_COMMON_H
+#define OS2D_IMAGE_COMMON_H
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <string.h>
+
+#define IMG_THREADS 256
+#define IMG_TW 128                                   // output columns of a tile
+#define IMG_TH_MAX 16                                // output rows of a tile: 16, 8, 4, 2 or 1 (chosen per level)
+#define IMG_UNITS (IMG_TW / 4 + 1)                   // 16-byte units a tile's row of floats can touch (unaligned row start)
+#define IMG_LUT_BYTES (3 * 256 * 4)
+#define IMG_LDS_BYTES 65536
+#define IMG_MAX_ROWS ((IMG_LDS_BYTES - IMG_LUT_BYTES) / (3 * IMG_TW))    // staged source rows that fit: 162
+#define IMG_PRECISION_BITS 22                        // Pillow: 32 - 8 - 2
+
+static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// after a kernel launch: 0, or -4 with "<what>: <HIP error>" in buf
+static inline int launched(const char* what, char* buf, size_t n) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    snprintf(buf, n, "%s: %s", what, hipGetErrorString(e));
+    return -4;
+  }
+  return 0;
+}
+
+#endif

@@ -11,6 +11,8 @@ dataloaders / loss meters (out of scope).
     detect             reference evaluate.py:99-117   + Os2dBoxCoder.decode_pyramid (decode, clip, NMS, merge levels)
     detect_images      reference evaluate.py:278-371  the per-image loop, with the next image's host-to-device copy
                        prefetched on a side stream
+    detect_raw_images  reference dataloader.py:272-347 + the above: the same loop from uint8 images; the normalised pyramid is
+                       built on the device (engine/image_pyramid.py) and only the uint8 image crosses PCIe
     evaluate           reference evaluate.py:151-171  detect_images + the VOC metric on the device (engine/voc_eval.py):
                        mAP, weighted mAP, recall and joint-classes AP per IoU threshold
 """
@@ -22,7 +24,8 @@ import torch
 
 from ..modeling.box_coder import ResizeBoxes
 from ..structures.feature_map import FeatureMapSize
-from .pyramid import PyramidHeadRunner
+from .image_pyramid import IMAGENET_NORMALIZATION, ImagePyramidBuilder
+from .pyramid import DEFAULT_SCALES, PyramidHeadRunner
 from .voc_eval import VocEvaluator
 
 
@@ -142,21 +145,69 @@ def detect_images(net, box_coder, image_pyramids, class_head, class_ids, orig_si
         index += 1
 
 
+def detect_raw_images(net, box_coder, images_u8, class_head, class_ids, scales=DEFAULT_SCALES,
+                      img_normalization=IMAGENET_NORMALIZATION, orig_sizes=None, device=None, **detect_kwargs):
+    """``detect_images`` for decoded images: ``images_u8`` is an iterable of uint8 tensors [h,w,3] (host or device).  The uint8
+    image of image i+1 is copied to the device on a side stream (pinned staging buffer, ``non_blocking``) while image i is
+    processed; the pyramid of ``scales`` is built on the compute stream by ``ImagePyramidBuilder`` (``img_normalization``:
+    dict(mean, std), or None for ``ToTensor`` alone).  Yields one ``BoxList`` per image: what ``detect_images`` yields when
+    it is given that pyramid."""
+    device = device or class_head.class_feature_maps.device
+    builder = ImagePyramidBuilder(scales=scales, img_normalization=img_normalization, device=device)
+    copy_stream = torch.cuda.Stream(device=device)
+
+    def upload(image):
+        if image.is_cuda:
+            return image, None
+        with torch.cuda.stream(copy_stream):
+            out = (image if image.is_pinned() else image.pin_memory()).to(device, non_blocking=True)
+        ready = torch.cuda.Event()
+        ready.record(copy_stream)
+        return out, ready
+
+    it = iter(images_u8)
+    try:
+        nxt = upload(next(it))
+    except StopIteration:
+        return
+    index = 0
+    while nxt is not None:
+        image, ready = nxt
+        try:
+            nxt = upload(next(it))          # in flight while this image is processed
+        except StopIteration:
+            nxt = None
+        main = torch.cuda.current_stream(device)
+        if ready is not None:
+            main.wait_event(ready)
+            image.record_stream(main)       # allocated on the copy stream, consumed on the compute stream
+        levels, _ = builder.build(image)
+        orig = orig_sizes[index] if orig_sizes is not None else None
+        yield detect(net, box_coder, levels, class_head, class_ids, orig_size=orig, **detect_kwargs)
+        index += 1
+
+
 def evaluate(net, box_coder, image_pyramids, gt_boxes, class_head, class_ids, orig_sizes=None, mAP_iou_thresholds=(0.5,),
-             **detect_kwargs):
+             pyramid_scales=None, img_normalization=None, **detect_kwargs):
     """Detections of every image (``detect_images``) followed by the VOC metric, as the end of the reference's ``evaluate``
     (evaluate.py:151-171).  ``gt_boxes``: one ``BoxList`` per image with field "labels" (and optionally "difficult"), on the
     host or the device.  The detections never leave the device: each image's ``BoxList`` goes into a ``VocEvaluator``, the
     sort is shared by all thresholds, and the scalars of all thresholds come back in one transfer at the end.  Returns a dict
     of floats: ``mAP@t``, ``mAPw@t``, ``recall@t``, ``AP_joint_classes@t`` per threshold (t as ``{:0.2f}``) and ``eval_time``
-    in seconds."""
+    in seconds.  With ``pyramid_scales`` the items of ``image_pyramids`` are uint8 images [h,w,3] and go through
+    ``detect_raw_images`` (``img_normalization``: dict(mean, std), or None for ``ToTensor`` alone, as in the reference's
+    dataloader)."""
     t_start = time.time()
     gt_boxes = list(gt_boxes)
     host_labels = [int(g.get_field("labels").max()) for g in gt_boxes if len(g) and not g.get_field("labels").is_cuda]
     evaluator = VocEvaluator(num_labels=max([int(c) for c in class_ids] + host_labels) + 1)
+    if pyramid_scales is not None:
+        detections = detect_raw_images(net, box_coder, image_pyramids, class_head, class_ids, scales=pyramid_scales,
+                                       img_normalization=img_normalization, orig_sizes=orig_sizes, **detect_kwargs)
+    else:
+        detections = detect_images(net, box_coder, image_pyramids, class_head, class_ids, orig_sizes=orig_sizes, **detect_kwargs)
     with torch.no_grad():
-        for boxes, gt in zip(detect_images(net, box_coder, image_pyramids, class_head, class_ids, orig_sizes=orig_sizes, **detect_kwargs),
-                             gt_boxes):
+        for boxes, gt in zip(detections, gt_boxes):
             evaluator.add(boxes, gt)
     if len(evaluator) != len(gt_boxes):
         raise RuntimeError("evaluate: {} images but {} ground-truth box lists".format(len(evaluator), len(gt_boxes)))
