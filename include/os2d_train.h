@@ -39,14 +39,15 @@ int os2d_train_decode_backward(const float* corr, const float* params, const flo
                                void* stream);
 
 /* ---- layer 3 (64 -> P, 5x5, no BatchNorm): dparams [NB,P,HW] -> dy [NB,P,PLANE] (zero-bordered plane layout) and
- * dbias [P] = sum over pairs and positions (written).                                                                   */
+ * dbias [P] = sum over pairs and positions (written; NULL = not computed).  One grid row per plane: NB * P <= 65535, else -1. */
 int os2d_train_params_backward(const float* dparams, int NB, int P, int H, int W, float* dy, float* dbias, void* stream);
 
 /* ---- frozen (eval-mode) BatchNorm + ReLU backward of layer 1 (128 channels) or 2 (64): dh [NB,Cout,PLANE] = gradient of
  * the layer's output h [NB,Cout,PLANE]; gamma / beta / running_var of the BatchNorm, eps its epsilon.  Writes dy
  * [NB,Cout,PLANE] = dh * (h > 0) * gamma / sqrt(var + eps) (the gradient of the convolution output; zero at pad cells) and
  * dgamma, dbeta, dbias [Cout] (each may be NULL: not computed).  dgamma uses (h - beta) / gamma for the normalised
- * pre-activation: a channel with gamma == 0 gets dgamma = 0.                                                             */
+ * pre-activation: a channel with gamma == 0 gets dgamma = 0.  One grid row per plane: NB * Cout <= 65535 (NB <= 511 for layer 1,
+ * <= 1023 for layer 2), else -1.                                                                                        */
 int os2d_train_bn_relu_backward(int layer, const float* dh, const float* h, const float* gamma, const float* beta,
                                 const float* running_var, float eps, int NB, int H, int W, float* dy, float* dgamma, float* dbeta,
                                 float* dbias, void* stream);
@@ -54,7 +55,7 @@ int os2d_train_bn_relu_backward(int layer, const float* dh, const float* h, cons
 /* ---- convolution backward, layer 1 (225 -> 128, 7x7), 2 (128 -> 64, 5x5) or 3 (64 -> P, 5x5); w = the layer's raw weights
  * [Cout,Cin,k,k] (not BatchNorm-folded), dy [NB,Cout,PLANE] from the two calls above.
  *   data:   dx [NB,Cin,PLANE] (the transposed convolution; zero at pad cells).  workspace: os2d_train_conv_data_workspace_floats
- *           floats (the flipped, transposed filters).
+ *           floats (the flipped, transposed filters).  One grid slice per pair: NB <= 65535, else -1.
  *   weight: dw [Cout,Cin,k,k] = sum over pairs and positions of dy x (written); x = the layer's input as the forward read it
  *           (layer 1: rnorm [NB,226,PLANE]; 2: h1 [NB,128,PLANE]; 3: h2 [NB,64,PLANE]).  The reduction over NB * PLANE is cut
  *           into as many split-K slices as fit `workspace_floats` (at most 64, at least one slice of Cout*Cin*k*k floats).   */

@@ -137,8 +137,8 @@ def resample_and_pool(corr, grids_unit, mask):
     gy = (gy + chan * H) / (H * K - 1) * 2 - 1
     pts = torch.stack([gx, gy], dim=-1).view(A * B, -1, 1, 2)
     vals = F.grid_sample(tall, pts, mode="bilinear", padding_mode="border", align_corners=True)
-    vals = vals.view(A, B, H * W, K).float()
-    return (vals * mask.reshape(1, 1, 1, K)).sum(-1).view(A, B, 1, H, W)
+    vals = vals.view(A, B, H * W, K).to(corr.dtype)         # fp32 as the reference; a float64 correlation stays float64
+    return (vals * mask.reshape(1, 1, 1, K).to(corr.dtype)).sum(-1).view(A, B, 1, H, W)
 
 
 def encode_boxes(boxes, anchors, weights=LOC_WEIGHTS):

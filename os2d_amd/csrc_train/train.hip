@@ -509,33 +509,35 @@ __global__ __launch_bounds__(256) void norm225_backward_kernel(const float* __re
   }
 }
 
-// image map L2 over C (eps 1e-5): norms, then the backward
-__global__ __launch_bounds__(256) void image_norm_kernel(const float* __restrict__ fm, int C, int HW, float* __restrict__ rinv,
-                                                         float* __restrict__ rn) {
+// image map L2 over C (eps 1e-5): the inverse norms (the class-side GEMM's operand), then the backward
+__global__ __launch_bounds__(256) void image_norm_kernel(const float* __restrict__ fm, int C, int HW, float* __restrict__ rinv) {
   const int a = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
   if (n >= HW) return;
   const float* f = fm + (size_t)a * C * HW + n;
   float ss = 0.f;
   for (int c = 0; c < C; ++c) ss += f[(size_t)c * HW] * f[(size_t)c * HW];
-  const float r = sqrtf(ss);
-  rinv[(size_t)a * HW + n] = 1.0f / (r + 1e-5f);
-  rn[(size_t)a * HW + n] = r;
+  rinv[(size_t)a * HW + n] = 1.0f / (sqrtf(ss) + 1e-5f);
 }
 
-__global__ __launch_bounds__(256) void image_norm_backward_kernel(const float* __restrict__ fm, const float* __restrict__ dfh,
-                                                                  const float* __restrict__ rinv, const float* __restrict__ rn,
-                                                                  int C, int HW, float* __restrict__ dfm) {
+// d x = s g - s^2 (g.x / r) x, s = 1 / (r + eps), r = |x|.  The two terms cancel down to eps s^2 g where x is (nearly) parallel
+// to g - always when C = 1 - so the two reductions and the combination are done in fp64: one rounding of the result.
+__global__ __launch_bounds__(256) void image_norm_backward_kernel(const float* __restrict__ fm, const float* __restrict__ dfh, int C,
+                                                                  int HW, float* __restrict__ dfm) {
   const int a = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
   if (n >= HW) return;
   const size_t base = (size_t)a * C * HW + n;
-  float dot = 0.f;
-  for (int c = 0; c < C; ++c) dot += dfh[base + (size_t)c * HW] * fm[base + (size_t)c * HW];
-  const float s = rinv[(size_t)a * HW + n], r = rn[(size_t)a * HW + n];
-  const float q = r > 0.f ? s * s * dot / r : 0.f;
-  for (int c = 0; c < C; ++c) dfm[base + (size_t)c * HW] = s * dfh[base + (size_t)c * HW] - q * fm[base + (size_t)c * HW];
+  double ss = 0.0, dot = 0.0;
+  for (int c = 0; c < C; ++c) {
+    const double f = fm[base + (size_t)c * HW];
+    ss += f * f;
+    dot += (double)dfh[base + (size_t)c * HW] * f;
+  }
+  const double r = sqrt(ss), s = 1.0 / (r + (double)1e-5f);
+  const double q = r > 0.0 ? s * s * dot / r : 0.0;
+  for (int c = 0; c < C; ++c) dfm[base + (size_t)c * HW] = (float)(s * (double)dfh[base + (size_t)c * HW] - q * (double)fm[base + (size_t)c * HW]);
 }
 
-// class maps: L2 over C (eps 1e-5) backward per (class, cell); dq in x-major channel order, q15 / out in cell order
+// class maps: L2 over C (eps 1e-5) backward per (class, cell), in fp64 as above; dq in x-major channel order, q15 / out in cell order
 __global__ __launch_bounds__(256) void class_norm_backward_kernel(const float* __restrict__ q15, const float* __restrict__ dq, int C,
                                                                   float* __restrict__ dq15) {
   const int b = blockIdx.y, cell = threadIdx.x;
@@ -544,16 +546,16 @@ __global__ __launch_bounds__(256) void class_norm_backward_kernel(const float* _
   const int m = j * OS2D_T + i;
   const float* q = q15 + (size_t)b * C * OS2D_K;
   const float* g = dq + (size_t)b * C * OS2D_K;
-  float ss = 0.f, dot = 0.f;
+  double ss = 0.0, dot = 0.0;
   for (int c = 0; c < C; ++c) {
-    const float v = q[(size_t)c * OS2D_K + cell];
+    const double v = q[(size_t)c * OS2D_K + cell];
     ss += v * v;
-    dot += v * g[(size_t)c * OS2D_K + m];
+    dot += v * (double)g[(size_t)c * OS2D_K + m];
   }
-  const float r = sqrtf(ss), s = 1.0f / (r + 1e-5f);
-  const float qf = r > 0.f ? s * s * dot / r : 0.f;
+  const double r = sqrt(ss), s = 1.0 / (r + (double)1e-5f);
+  const double qf = r > 0.0 ? s * s * dot / r : 0.0;
   for (int c = 0; c < C; ++c)
-    dq15[((size_t)b * C + c) * OS2D_K + cell] = s * g[(size_t)c * OS2D_K + m] - qf * q[(size_t)c * OS2D_K + cell];
+    dq15[((size_t)b * C + c) * OS2D_K + cell] = (float)(s * (double)g[(size_t)c * OS2D_K + m] - qf * (double)q[(size_t)c * OS2D_K + cell]);
 }
 
 // bilinear resize backward, one thread per (class, channel): the thread owns the whole h x w plane of its channel (written
@@ -792,16 +794,15 @@ int os2d_train_corr_backward(const float* fm, const float* qp, const float* dcor
   }
   if (!dfm && !dq) return 0;
   float* rinv = workspace;
-  float* rn = rinv + (size_t)A * HW;
-  float* dfh = rn + (size_t)A * HW;
-  hipLaunchKernelGGL(image_norm_kernel, dim3(blocks(HW), A), dim3(256), 0, S(stream), fm, C, (int)HW, rinv, rn);
+  float* dfh = rinv + 2 * (size_t)A * HW;     // the second A * HW floats are not used
+  hipLaunchKernelGGL(image_norm_kernel, dim3(blocks(HW), A), dim3(256), 0, S(stream), fm, C, (int)HW, rinv);
   int rc = launched("image_norm_kernel");
   if (rc) return rc;
   if (dfm) {
     rc = gemm<false>(LdClassT{qp, C}, LdCorrRows{dcorr, B, (int)HW}, StDense{dfh, C, (int)HW}, C, (int)HW, B * OS2D_K, A, 0, S(stream),
                      "correlation backward (image)");
     if (rc) return rc;
-    hipLaunchKernelGGL(image_norm_backward_kernel, dim3(blocks(HW), A), dim3(256), 0, S(stream), fm, dfh, rinv, rn, C, (int)HW, dfm);
+    hipLaunchKernelGGL(image_norm_backward_kernel, dim3(blocks(HW), A), dim3(256), 0, S(stream), fm, dfh, C, (int)HW, dfm);
     rc = launched("image_norm_backward_kernel");
     if (rc) return rc;
   }

@@ -77,6 +77,23 @@ def test_bad_arguments_fail_before_launch(lib_path):
     assert lib.os2d_train_last_error() != b""
 
 
+def test_pair_counts_beyond_the_grid_limits_fail_before_launch(lib_path):
+    """One grid row per plane (pair x channel): at most 65535 of them (include/os2d_train.h)."""
+    from os2d_amd import _train_lib
+    lib = _train_lib.load()
+    fake = ctypes.c_void_p(256)      # never dereferenced
+    rc = lib.os2d_train_bn_relu_backward(1, fake, fake, fake, fake, fake, 1e-5, 512, 9, 13, fake, None, None, None, None)   # 512 * 128
+    assert rc == -1 and b"NB=512" in lib.os2d_train_last_error()
+    rc = lib.os2d_train_bn_relu_backward(2, fake, fake, fake, fake, fake, 1e-5, 1024, 9, 13, fake, None, None, None, None)  # 1024 * 64
+    assert rc == -1
+    rc = lib.os2d_train_params_backward(fake, 10923, 6, 9, 13, fake, None, None)                                            # 65538 planes
+    assert rc == -1 and b"NB=10923" in lib.os2d_train_last_error()
+    rc = lib.os2d_train_params_backward(fake, 16384, 4, 9, 13, fake, None, None)                                            # 65536 planes
+    assert rc == -1
+    rc = lib.os2d_train_conv_backward_data(1, 6, fake, fake, 65536, 9, 13, fake, fake, 10 ** 7, None)
+    assert rc == -1 and b"NB=65536" in lib.os2d_train_last_error()
+
+
 def test_backward_kernels_do_not_spill(lib_path):
     pytest.importorskip("msgpack")
     from os2d_amd import codeobj
