@@ -34,6 +34,16 @@
 // spectrum R * 2^8 (|R| <= window width <= 96), forward output X = acc * 2^-22; inverse: every image's spectrum is scaled by
 // its own power of two that puts its largest |component| into [2^13, 2^14) (the dynamic range of Y is far larger than that of
 // the rigorous bound), T * 2^-(14 + ceil(log2 P) + 1), output = acc * 2^(ceil(log2 P) + 1 - 13) / (scale * P * Q).
+//
+// Radix 2 in the column direction of the FORWARD transform for P = 64 (the instantiations with 8 k-steps: every plan with
+// Pp = 64 has P = 64, see dft_plan_transform).  One decimation step makes the dense 64-point matrix block-diagonal:
+//   E = F32 . R[even h], O = F32 . R[odd h];   X[u] = E[u] + w^u O[u], X[u + 32] = E[u] - w^u O[u], w = exp(-2 pi i / 64)
+// Row tiles 0, 1 of step 2 are the even block, 2, 3 the odd block, both with the SAME 64 x 64 real matrix (stored once): 4
+// k-steps instead of 8, half the matrix instructions and half the fragment registers.  The kernel orders the window rows
+// parity-major when it writes x (an index map in the W phase: step 1 then delivers R parity-major for free) and applies the
+// butterfly in fp32 where it streams the staged spectra out.  The 32 twiddles are a float64-built table behind the half-size
+// matrix.  (The mirror image in step A of the inverse kernel - butterfly in WY, two 32-point products, row 2 m + parity in WT -
+// was built and measured: step A does not shrink at 1024 pairs and the epilogue grows; tools/patches/dft_inverse_radix2.patch.)
 #pragma once
 
 #ifndef DFT_DEV
@@ -119,7 +129,16 @@ DFT_HD unsigned dft_magic(unsigned d) { return d > 1 ? (unsigned)(((1ull << 32) 
 // sizes of the constant operand arrays of a (P, Q) transform, in 16-byte units: they depend on P and Q only, so every map
 // (and every tiling) that uses the transform shares them
 DFT_HD int dft_units_fqt(int P, int Q) { return (dft_round_up(Q, 16) / 8) * 2 * dft_round_up(Q + 2, 32); }
-DFT_HD int dft_units_fp2(int P, int Q) { return (2 * dft_round_up(P, 8) / 8) * 2 * dft_round_up(2 * P, 32); }
+// P = 64 (radix 2 in the forward kernel): Fp2 is the 64 x 64 real matrix of the 32-point transform [k / 8 = 8][hi|lo][64 rows] followed by
+// DFT_R2_TWU units of twiddles: float [32][re|im] = exp(-2 pi i u / 64)
+constexpr int DFT_R2_P = 64, DFT_R2_MATU = 8 * 2 * 64, DFT_R2_TWU = 16;
+// the 1024 bytes behind the union region of LDS (lds_total): the inverse kernel keeps its per-image maxima in the first 256, the
+// forward kernel of the 64-row transform its twiddles (DFT_R2_TWU units = 256 bytes) from this offset
+constexpr int DFT_R2_LDS_TW = 512;
+DFT_HD bool dft_radix2(int P) { return P == DFT_R2_P; }
+DFT_HD int dft_units_fp2(int P, int Q) {
+  return dft_radix2(P) ? DFT_R2_MATU + DFT_R2_TWU : (2 * dft_round_up(P, 8) / 8) * 2 * dft_round_up(2 * P, 32);
+}
 DFT_HD int dft_units_e2(int P, int Q) { return (2 * dft_round_up(P, 8) / 8) * 2 * dft_round_up(2 * P, 32); }
 DFT_HD int dft_units_gq(int P, int Q) { return (dft_round_up(Q + 2, 16) / 8) * 2 * dft_round_up(Q, 32); }
 DFT_HD size_t dft_matrices_units(int P, int Q) {
@@ -130,6 +149,9 @@ DFT_HD size_t dft_matrices_units(int P, int Q) {
 static inline bool dft_plan_transform(int LH, int LW, int RH, int ncols, int minP, int minQ, int G, DftPlan* pl) {
   pl->G = G;
   pl->P = dft_round_up(minP, 4);
+  // 60 rows pad to the operand arrays of 64 (Pp) anyway and would be the only other size with 8 k-steps in step 2 / step A: it
+  // takes the 64-row transform, so that 8 k-steps always mean the radix-2 product (7 % more bins under the "exact" policy only)
+  if (pl->P == 60) pl->P = DFT_R2_P;
   pl->Q = dft_round_up(minQ, 2);
   pl->V = pl->Q / 2 + 1;
   pl->NBINS = dft_round_up(pl->P * pl->V, 8);
@@ -162,6 +184,7 @@ static inline bool dft_plan_transform(int LH, int LW, int RH, int ncols, int min
   if (y2 > u) u = y2;
   if (tt > u) u = tt;
   if (G == 8) {
+    if (dft_radix2(pl->P)) return false;      // (the 64-row transform keeps its half-size matrix in registers: 4 images)
     // EIGHT images per iteration (round 6): the fixed phases of an iteration - six barriers, the fill and drain of
     // four products, the burst of the next window's requests - do not shrink with the transform, so the small transforms of the
     // pyramid paid 1.3 - 1.9x per location.  With 8 images the products have 20 - 24 tiles (three per wave: the tile grids of
@@ -180,7 +203,7 @@ static inline bool dft_plan_transform(int LH, int LW, int RH, int ncols, int min
   }
   pl->lds_const = fqt > gq ? fqt : gq;
   pl->lds_union = dft_round_up(u, 256);
-  pl->lds_total = pl->lds_const + pl->lds_union + 1024;      // + per-image maxima / scales
+  pl->lds_total = pl->lds_const + pl->lds_union + 1024;      // + per-image maxima / scales (inverse) | twiddles at DFT_R2_LDS_TW (forward, P = 64)
   return pl->lds_total <= 160 * 1024;
 }
 
@@ -445,8 +468,21 @@ DFT_DEV void dft_product_lds_any(f32x16* acc, int ntiles, int ks0, int ks1, cons
 //   Fp2 [k = (ri * Pp + h) / 8][hi|lo][m = 2 u + ro]  value = ro == 0 ? (ri == 0 ? cos : sin) : (ri == 0 ? -sin : cos) of 2 pi u h / P
 //   E2  [k = (ri * Pp + u) / 8][hi|lo][m = 2 h + ro]  value = ro == 0 ? (ri == 0 ? cos : -sin) : (ri == 0 ? sin : cos)
 //   Gq  [k = (2 v + ri) / 8][hi|lo][n = w]            value = a_v * E_Q[v w].{re, im}, a_0 = a_{Q/2} = 1, else 2   * 2^13
+// P = 64 (dft_radix2): Fp2 is the matrix of the 32-point transform, the same formula with (P, Pp) = (32, 32) - 64 rows,
+// k < 64 - followed by the twiddle units: float (cos, sin) of -2 pi u / 64, u = 0 .. 31 (two u per unit, rounded once from float64)
 DFT_DEV void dft_matrix_unit(int which, int unit, int P, int Q, const double* twP, const double* twQ, u32x4* out) {
-  const int V = Q / 2 + 1, Pp = dft_round_up(P, 8);
+  const int V = Q / 2 + 1;
+  const bool r2 = which == 1 && dft_radix2(P);
+  if (r2 && unit >= DFT_R2_MATU) {
+    const int u = 2 * (unit - DFT_R2_MATU);
+    u32x4 o;
+    for (int t = 0; t < 4; ++t) o[t] = __builtin_bit_cast(unsigned, (float)twP[2 * u + t]);
+    *out = o;
+    return;
+  }
+  const int tws = r2 ? 2 : 1;      // the table twP has P entries: every second one is the table of P / 2
+  if (r2) P /= 2;
+  const int Pp = dft_round_up(P, 8);
   int cols, kidx, hl, col;
   double vals[8];
   if (which == 0) cols = dft_round_up(2 * V, 32);
@@ -464,7 +500,7 @@ DFT_DEV void dft_matrix_unit(int which, int unit, int P, int Q, const double* tw
     } else if (which == 1) {           // Fp2: k = ri * Pp + h, col (row of the product) = 2 u + ro
       const int ri = k / Pp, h = k - ri * Pp, u = col >> 1, ro = col & 1;
       if (h < P && u < P && ri < 2) {
-        const int a = (int)(((long long)u * h) % P);
+        const int a = (int)(((long long)u * h) % P) * tws;
         const double c = twP[2 * a], s = -twP[2 * a + 1];          // cos, sin of +2 pi u h / P
         x = (ro == 0 ? (ri == 0 ? c : s) : (ri == 0 ? -s : c)) * 16384.0;
       }
@@ -513,6 +549,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
                               const u32x4* FqT, const u32x4* Fp2, const DftPlan& pl, int C, int Cpad, int NBT, int iters) {
   constexpr int THR = NW * 64;
   constexpr bool ALDS = G == 8;    // the row operand of step 2 lives in LDS
+  constexpr bool R2 = !ALDS && KS2 == 8;      // P = 64: radix 2 (the head of this file)
   unsigned char* smem = DFT_LDS;
   const int tid = DFT_TID, lane = tid & 63, l31 = lane & 31, hw = lane >> 5;
   const int wv = DFT_UNIFORM(tid >> 6);      // wave-uniform (a scalar register): the tile ownership below is real branching, not exec masks
@@ -524,6 +561,8 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
   unsigned char* ldsUb = smem + pl.lds_const;
   const int nF = (Wk / 8) * 2 * N1;
   for (int i = tid; i < nF; i += THR) ldsF[i] = FqT[i];
+  const unsigned char* ldsTw = smem + pl.lds_const + pl.lds_union + DFT_R2_LDS_TW;           // R2: the twiddles, float [32][re|im]
+  if (R2 && tid < DFT_R2_TWU) reinterpret_cast<u32x4*>(smem + pl.lds_const + pl.lds_union + DFT_R2_LDS_TW)[tid] = Fp2[DFT_R2_MATU + tid];
   u32x4* ldsP = ldsF + nF;                                                         // ALDS: Fp2 [2 Pp / 8][2][M2]
   if (ALDS)
     for (int i = tid; i < (2 * Pp / 8) * 2 * pl.M2; i += THR) ldsP[i] = Fp2[i];
@@ -533,9 +572,16 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
   const int mt1n = Mx / 32, nt1n = N1 / 32, nt2n = N2 / 32, mt2n = pl.M2 / 32;
   const int ks1n = Wk / 16, ks2n = 2 * Pp / 16;
   const int mt2 = wv & 3;
-  constexpr int KR2 = KS2 ? KS2 : DFT_KREG;      // KS2 > 0: exactly the k-steps of step 2 (ks2n == KS2)
+  // R2: the wave's block is the parity mt2 >> 1, its fragments the 4 k-steps of row tile mt2 & 1 of the 64 x 64 matrix
+  constexpr int KR2 = R2 ? 4 : KS2 ? KS2 : DFT_KREG;      // KS2 > 0: exactly the k-steps of step 2 (ks2n == KS2)
   half8 fp2h[KR2], fp2l[KR2];
-  if (!ALDS) {
+  if (R2) {
+#pragma unroll
+    for (int ks = 0; ks < KR2; ++ks) {
+      fp2h[ks] = dft_frag(Fp2 + ((size_t)((2 * ks + hw) * 2 + 0)) * 64 + (mt2 & 1) * 32 + l31);
+      fp2l[ks] = dft_frag(Fp2 + ((size_t)((2 * ks + hw) * 2 + 1)) * 64 + (mt2 & 1) * 32 + l31);
+    }
+  } else if (!ALDS) {
 #pragma unroll
     for (int ks = 0; ks < KR2; ++ks) {
       const int kc = ks < ks2n ? ks : 0, mc = mt2 < mt2n ? mt2 : 0;
@@ -657,7 +703,8 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
             if (c0_ + g < C)         // (uniform: only the last channel group of a pair has channels beyond C)
               dft_split4(fmaxf(pc[s][g][0], 0.f) * nsc[0], fmaxf(pc[s][g][1], 0.f) * nsc[1], fmaxf(pc[s][g][2], 0.f) * nsc[2],
                          fmaxf(pc[s][g][3], 0.f) * nsc[3], &hi, &lo);
-            const int m = g * Pp + r_;
+            // R2: rows parity-major (even rows, then odd rows) - step 1 then delivers R in the k order of the two half products
+            const int m = g * Pp + (R2 ? (r_ & 1) * 32 + (r_ >> 1) : r_);
             unsigned char* dst = ldsUb + ((size_t)((c4_ >> 1) * 2) * MxS + m) * 16 + (c4_ & 1) * 8;
             *reinterpret_cast<u32x2*>(dst) = hi;
             *reinterpret_cast<u32x2*>(dst + (size_t)MxS * 16) = lo;
@@ -707,7 +754,8 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
           u32x2 hi, lo;
           const float sc = 1.0f / 2097152.0f;      // 2^-21 = 2^8 / (2^15 * 2^14)
           dft_split4(acc[j][4 * q] * sc, acc[j][4 * q + 1] * sc, acc[j][4 * q + 2] * sc, acc[j][4 * q + 3] * sc, &hi, &lo);
-          const int kg = ri * (Pp / 8) + (h0 >> 3);
+          // R2: h0 counts the parity-major rows of the W phase: k = parity * 64 + ri * 32 + h / 2
+          const int kg = R2 ? (h0 >> 5) * 8 + ri * 4 + ((h0 & 31) >> 3) : ri * (Pp / 8) + (h0 >> 3);
           unsigned char* dst = ldsUb + ((size_t)(kg * 2) * N2S + img * V + v) * 16 + (h0 & 4) * 2;
           *reinterpret_cast<u32x2*>(dst) = hi;
           *reinterpret_cast<u32x2*>(dst + (size_t)N2S * 16) = lo;
@@ -745,9 +793,12 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
       if (ALDS) {
         dft_product_lds_any<NW, DFT_PIPE_LDS ? 2 : 0>(xc, nt2w, 0, ks2n, ldsP, pl.M2, ldsU, N2S, wv, mt2n, l31, hw);
         DFT_FWD_PREFETCH_SLOTS(itn, tl, 0, NSLOT)
-      } else if (DFT_FWD_PREFETCH_AFTER == 1 || (DFT_FWD_PREFETCH_AFTER == 2 && KS2 > 0 && KS2 <= 6)) {      // the burst behind the product
+      } else if (!R2 && (DFT_FWD_PREFETCH_AFTER == 1 || (DFT_FWD_PREFETCH_AFTER == 2 && KS2 > 0 && KS2 <= 6))) {      // the burst behind the product
         dft_product_rega_any<KS2>(xc, nt2w, fp2h, fp2l, ks2n, ldsU, N2S, wv >> 2, NW / 4, l31, hw);
         DFT_FWD_PREFETCH_SLOTS(itn, tl, 0, NSLOT)
+      } else if (R2) {      // E | O = F32 . R2[this wave's parity block: 8 k groups of 2 N2S units]
+        DFT_FWD_PREFETCH_SLOTS(itn, tl, 0, NSLOT)
+        dft_product_rega_any<4>(xc, nt2w, fp2h, fp2l, 4, ldsU + (size_t)(mt2 >> 1) * 16 * N2S, N2S, wv >> 2, NW / 4, l31, hw);
       } else {
         DFT_FWD_PREFETCH_SLOTS(itn, tl, 0, NSLOT)
         dft_product_rega_any<KS2>(xc, nt2w, fp2h, fp2l, ks2n, ldsU, N2S, wv >> 2, NW / 4, l31, hw);
@@ -766,6 +817,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
       const int img = dft_div(n2, pl.inv_v), v = n2 - img * V;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
+        // R2: row tiles 0, 1 are E[u], u < 32, staged at u; row tiles 2, 3 are O[u], staged at 32 + u
         const int u0 = (um[j] * 32 + 8 * q + 4 * hw) >> 1;
         if (img < G && u0 < P) {
           const float sc = 1.0f / 4194304.0f;      // 2^-22 = 1 / (2^8 * 2^14)
@@ -786,6 +838,27 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
       const int per_v = (P / 4) * (G * 2), npieces = V * per_v;
       size_t qstride;                                            // floats between consecutive quads of bins
       float* dstbase = X + dft_spectra_pair0(pr_, NBT, pl.NBINS / 4, Cpad, &qstride) + (size_t)c0_ * 8;
+      if (R2) {
+        // the butterfly rides on this pass: a thread takes the E and the O piece of two u < 32 (one image), multiplies O by the
+        // twiddles and streams out X[u] = E + w^u O and X[u + 32] = E - w^u O - the same 128-byte runs as the plain copy
+        constexpr int per_h = (DFT_R2_P / 8) * (G * 2);
+        for (int i = tl; i < V * per_h; i += THR) {
+          const int v = i / per_h, rem = i - v * per_h;
+          const int uq = rem / (2 * G), jj = rem - uq * (2 * G);
+          const unsigned char* src = ldsUb + (size_t)v * XS + uq * (G * 32) + jj * 16;
+          const f32x4 e = *reinterpret_cast<const f32x4*>(src);
+          const f32x4 o = *reinterpret_cast<const f32x4*>(src + (DFT_R2_P / 8) * (G * 32));
+          const f32x4 w = *reinterpret_cast<const f32x4*>(ldsTw + (4 * uq + 2 * (jj & 1)) * 8);
+          f32x4 t;
+          t[0] = w[0] * o[0] - w[1] * o[1];
+          t[1] = w[0] * o[1] + w[1] * o[0];
+          t[2] = w[2] * o[2] - w[3] * o[3];
+          t[3] = w[2] * o[3] + w[3] * o[2];
+          float* dst = dstbase + (size_t)(v * (P / 4) + uq) * qstride + jj * 4;
+          DFT_STREAM_STORE(reinterpret_cast<f32x4*>(dst), e + t);
+          DFT_STREAM_STORE(reinterpret_cast<f32x4*>(dst + (size_t)(DFT_R2_P / 8) * qstride), e - t);
+        }
+      } else
       for (int i = tl; i < npieces; i += THR) {
         const int v = dft_div(i, pl.inv_pq), rem = i - v * per_v;
         const int uq = rem / (2 * G), jj = rem - uq * (2 * G);

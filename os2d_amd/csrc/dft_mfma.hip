@@ -57,7 +57,8 @@ using namespace os2d_dft;
 
 // KS = k-steps of the product whose row operand lives in registers (step 2 / step A: 2 Pp / 16): a template parameter for the
 // canonical transform sizes (5 .. 8: straight-line products, exactly as many fragment registers as the size needs), 0 = any
-// size behind uniform guards ($OS2D_DFT_SIZES=exact)
+// size behind uniform guards ($OS2D_DFT_SIZES=exact).  KS = 8 is the 64-row transform and nothing else (dft_plan_transform): the
+// forward instantiations run the radix-2 form of step 2 - two half-size products of 4 k-steps and a butterfly (dft_mfma.h)
 template <bool TILED, bool FAST, int G, int NW, int KS>
 __global__ __launch_bounds__(NW * 64, 8 / NW) void dft_forward_kernel(const float* __restrict__ corr, const float* __restrict__ invn,
                                                                       float* __restrict__ X, const u32x4* __restrict__ FqT,
@@ -110,7 +111,7 @@ dft_inverse_fn dft_inverse_pick(const DftPlan& pl) {
   }
 }
 
-// FqT | Fp2 | E2 | Gq of a (P, Q) transform, one thread per 16-byte unit
+// FqT | Fp2 | E2 | Gq of a (P, Q) transform (P = 64: the half-size Fp2 with the twiddles behind it), one thread per 16-byte unit
 __global__ __launch_bounds__(256) void dft_matrices_kernel(const double* __restrict__ twP, const double* __restrict__ twQ, int P, int Q,
                                                            u32x4* __restrict__ out) {
   const int n0 = dft_units_fqt(P, Q), n1 = n0 + dft_units_fp2(P, Q), n2 = n1 + dft_units_e2(P, Q), n3 = n2 + dft_units_gq(P, Q);
@@ -204,6 +205,10 @@ int os2d_launch_dft_forward(const float* corr, const float* inv, float* X, const
   if (Cpad < dft_round_up(C, G)) {
     os2d_set_error("dft_forward: channel stride %d < %d", Cpad, dft_round_up(C, G));
     return -1;
+  }
+  if (G == 4 && pl.Pp == 64 && !dft_radix2(pl.P)) {
+    os2d_set_error("dft_forward: a plan of 8 k-steps with %d rows (the radix-2 kernel takes 64)", pl.P);
+    return -3;
   }
   const int CG = (C + G - 1) / G, NBT = NB * pl.T, iters = NBT * CG;
   pl.inv_cg = dft_magic((unsigned)CG);
