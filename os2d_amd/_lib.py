@@ -1,13 +1,12 @@
 """ctypes binding of libos2d_hip.so (C ABI declared in include/os2d_hip.h).
 
-There is deliberately NO fallback: if the shared library is missing or does not export the declared ABI the
-import of the compute path fails loudly (``Os2dLibraryError``).  Build it with ``python -m os2d_amd.build``
-(or ``__graft_entry__.build()``).
+There is deliberately NO fallback: if the shared library is missing or does not export the declared ABI, loading it fails
+loudly (``Os2dLibraryError``, os2d_amd/_native.py).  Build it with ``python -m os2d_amd.build`` (or ``__graft_entry__.build()``).
 """
 import ctypes
-import os
 
-from .build import LIB_PATH
+from . import build
+from ._native import NativeLibrary, Os2dLibraryError  # noqa: F401  (Os2dLibraryError: imported from here by the package)
 
 ABI_VERSION = 9
 
@@ -17,7 +16,7 @@ _i = ctypes.c_int
 _f = ctypes.c_float
 _sz = ctypes.c_size_t
 
-# name -> (restype, argtypes): must list EVERY symbol of include/os2d_hip.h (tests/test_abi.py checks the header)
+# name -> (restype, argtypes): must list EVERY symbol of include/os2d_hip.h (tests/test_native_libs.py checks the header)
 SIGNATURES = {
     "os2d_abi_version": (_i, []),
     "os2d_last_error": (ctypes.c_char_p, []),
@@ -92,68 +91,8 @@ SIGNATURES = {
 }
 
 
-class Os2dLibraryError(RuntimeError):
-    pass
-
-
-_LIB = None
-
-
-def lib_path():
-    return os.environ.get("OS2D_HIP_LIB", LIB_PATH)
-
-
-def load():
-    """Load (once) and return the ctypes handle; raises Os2dLibraryError if it is not there."""
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    path = lib_path()
-    if "OS2D_HIP_LIB" not in os.environ:
-        # The .so is a build artefact (not tracked): compile it in-tree when it is missing OR was built from other
-        # sources than the ones in the tree (content hash, os2d_amd/build.py - an edited kernel never runs stale).
-        # This is the same HIP library, not a fallback implementation; if hipcc is missing the error below fires.
-        from . import build as _build
-        if not _build.up_to_date():
-            try:
-                import fcntl
-                os.makedirs(os.path.dirname(path), exist_ok=True)
-                with open(path + ".lock", "w") as lock:      # one builder at a time (torchrun starts N ranks at once);
-                    fcntl.flock(lock, fcntl.LOCK_EX)         # the check is repeated under the lock
-                    if not _build.up_to_date():
-                        _build.build(verbose=False)
-            except Exception as e:  # noqa: BLE001
-                raise Os2dLibraryError("libos2d_hip.so is missing or stale and building it failed ({}); the OS2D head "
-                                       "has no CPU or PyTorch fallback".format(e))
-    if not os.path.exists(path):
-        raise Os2dLibraryError(
-            "libos2d_hip.so not found at {} - the OS2D head has no CPU or PyTorch fallback; build the HIP "
-            "extension first: python -m os2d_amd.build".format(path))
-    # torch must be imported first so that the HIP runtime already mapped in the process (same soname,
-    # libamdhip64.so.7) is the one our library binds to: one runtime, shared streams and allocations.
-    import torch  # noqa: F401
-    try:
-        handle = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
-    except OSError as e:
-        raise Os2dLibraryError("cannot load {}: {}".format(path, e))
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(handle, name)
-        except AttributeError:
-            raise Os2dLibraryError("{} does not export {} (stale build? run python -m os2d_amd.build --force)".format(path, name))
-        fn.restype = res
-        fn.argtypes = args
-    if handle.os2d_abi_version() != ABI_VERSION:
-        raise Os2dLibraryError("ABI version mismatch: library {} vs binding {}".format(handle.os2d_abi_version(), ABI_VERSION))
-    _LIB = handle
-    return _LIB
-
-
-def check(rc, what):
-    """Raise RuntimeError with the library's message if a call returned an error code."""
-    if rc != 0:
-        msg = load().os2d_last_error()
-        raise RuntimeError("{} failed (code {}): {}".format(what, rc, msg.decode("utf-8", "replace") if msg else "?"))
+LIBRARY = NativeLibrary(build.HIP, SIGNATURES, ABI_VERSION, "os2d_abi_version", "os2d_last_error", "the OS2D head")
+lib_path, load, check = LIBRARY.lib_path, LIBRARY.load, LIBRARY.check
 
 
 def ptr(t):

@@ -1,6 +1,6 @@
-"""In-tree build of libos2d_hip.so for gfx950 with hipcc (no JIT cache: the .so travels with the tree).
+"""In-tree build of the four HIP libraries for gfx950 with hipcc (no JIT cache: the .so files travel with the tree).
 
-    python -m os2d_amd.build                      # build if stale
+    python -m os2d_amd.build                      # build what is stale
     python -m os2d_amd.build --force
     python -m os2d_amd.build --train              # only libos2d_train.so (the head's backward pass)
     python -m os2d_amd.build --eval               # only libos2d_eval.so (the VOC detection metric)
@@ -8,6 +8,8 @@
     python -m os2d_amd.build --variant TAG [--packed on|off|fft] [-DFLAG ...]
                                                   # diagnostic copy under tools/diag_libs/TAG/ (run with OS2D_HIP_LIB=...)
 """
+import collections
+import functools
 import glob
 import hashlib
 import os
@@ -18,9 +20,9 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+SHARED = os.path.join(HERE, "csrc_shared")        # abi_common.h: the error text and launch check of every library
+INCLUDE = os.path.join(HERE, "..", "include")
 LIB_DIR = os.path.join(HERE, "lib")
-LIB_PATH = os.path.join(LIB_DIR, "libos2d_hip.so")
-BUILD_DIR = os.path.join(HERE, "csrc", "build")
 VARIANT_DIR = os.path.join(HERE, "..", "tools", "diag_libs")
 SOURCES = ["abi.hip", "prep.hip", "corr_mfma.hip", "conv_mfma.hip", "conv_f16x3.hip", "conv3_f16x3.hip", "corr_f16x3.hip", "sample_decode.hip", "nms.hip", "detect.hip", "detect_pyramid.hip", "spectral.hip", "spectral_f16.hip", "spectra_pack.hip", "fft.hip", "dft_mfma.hip"]
 ARCH = "gfx950"
@@ -36,40 +38,48 @@ PACKED_OFF = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 NO_PACKED_FP32 = set(SOURCES)             # which translation units are compiled without the packed instructions
 FLAGS += os.environ.get("OS2D_EXTRA_HIPCC_FLAGS", "").split()      # kernel experiments (-DOS2D_DIAG_...); part of the source hash
 
+# A library is a record; headers(), source_hash(), up_to_date() and build_library() are the whole build, for any of them.
+#   flags        of every unit
+#   unit_flags   {source: flags of that unit on top}
+#   header_dirs  the directories whose *.h its units may include: all of them are hashed, and a quoted #include that resolves
+#                nowhere in them fails the tests
+#   header       the public C ABI under include/
+#   env          the environment variable that names another file to load instead (os2d_amd/_native.py)
+Library = collections.namedtuple("Library", "name csrc sources flags unit_flags header_dirs header env")
+
+HIP = Library("libos2d_hip.so", CSRC, SOURCES, FLAGS, {s: PACKED_OFF for s in NO_PACKED_FP32}, [CSRC, SHARED], "os2d_hip.h", "OS2D_HIP_LIB")
 # The backward pass of the head is a library of its own (include/os2d_train.h): libos2d_hip.so keeps exactly the sources and
 # kernels above.  Its units may include the forward's headers (csrc/*.h) to share the sampling and decode arithmetic.
-TRAIN_CSRC = os.path.join(HERE, "csrc_train")
-TRAIN_SOURCES = ["train.hip", "objective.hip"]
-TRAIN_LIB_PATH = os.path.join(LIB_DIR, "libos2d_train.so")
-TRAIN_BUILD_DIR = os.path.join(TRAIN_CSRC, "build")
-TRAIN_FLAGS = FLAGS + PACKED_OFF
 # objective.hip restates the reference's IoU and box encoding operation for operation: a fused multiply-add would round
 # differently from the CPU reference
-TRAIN_UNIT_FLAGS = {"objective.hip": ["-ffp-contract=off"]}
-
-# The VOC evaluation (include/os2d_eval.h) is a third library: the kernel list of libos2d_hip.so and the ABI of
-# libos2d_train.so stay what they are.  Its units may include csrc/detect_common.h for the score sort key.
+TRAIN_CSRC = os.path.join(HERE, "csrc_train")
+TRAIN = Library("libos2d_train.so", TRAIN_CSRC, ["train.hip", "objective.hip"], FLAGS + PACKED_OFF, {"objective.hip": ["-ffp-contract=off"]},
+                [TRAIN_CSRC, CSRC, SHARED], "os2d_train.h", "OS2D_TRAIN_LIB")
+# The VOC evaluation (include/os2d_eval.h): the kernel list of libos2d_hip.so and the ABI of libos2d_train.so stay what they
+# are.  Its units may include csrc/detect_common.h for the score sort key.  The IoU of the match step must have the bits of the
+# reference's CPU arithmetic, and the area under the curve is a sum of separately rounded products: no fused multiply-adds in
+# any unit
 EVAL_CSRC = os.path.join(HERE, "csrc_eval")
-EVAL_SOURCES = ["match.hip", "sort.hip", "metric.hip"]
-EVAL_LIB_PATH = os.path.join(LIB_DIR, "libos2d_eval.so")
-EVAL_BUILD_DIR = os.path.join(EVAL_CSRC, "build")
-# the IoU of the match step must have the bits of the reference's CPU arithmetic, and the area under the curve is a sum of
-# separately rounded products: no fused multiply-adds in any unit
-EVAL_FLAGS = FLAGS + PACKED_OFF + ["-ffp-contract=off"]
-
-# The image pyramid from uint8 images (include/os2d_image.h) is a fourth library, for the same reason.  Integer arithmetic and a
-# table lookup: no floating-point operation whose rounding a flag could change.
+EVAL = Library("libos2d_eval.so", EVAL_CSRC, ["match.hip", "sort.hip", "metric.hip"], FLAGS + PACKED_OFF + ["-ffp-contract=off"], {},
+               [EVAL_CSRC, CSRC, SHARED], "os2d_eval.h", "OS2D_EVAL_LIB")
+# The image pyramid from uint8 images (include/os2d_image.h).  Integer arithmetic and a table lookup: no floating-point
+# operation whose rounding a flag could change.  Its units include none of csrc/*.h.
 IMAGE_CSRC = os.path.join(HERE, "csrc_image")
-IMAGE_SOURCES = ["resample.hip"]
-IMAGE_LIB_PATH = os.path.join(LIB_DIR, "libos2d_image.so")
-IMAGE_BUILD_DIR = os.path.join(IMAGE_CSRC, "build")
-IMAGE_FLAGS = FLAGS + PACKED_OFF
+IMAGE = Library("libos2d_image.so", IMAGE_CSRC, ["resample.hip"], FLAGS + PACKED_OFF, {}, [IMAGE_CSRC, SHARED], "os2d_image.h", "OS2D_IMAGE_LIB")
+LIBRARIES = [HIP, TRAIN, EVAL, IMAGE]
 
 
-def headers():
-    """Every header a translation unit can include: csrc/*.h + the public ABI header.  Globbed, not listed: a new header
-    (fft_regs.h was missed in round 2) is part of the source hash and of every object's dependencies from the day it exists."""
-    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "os2d_hip.h")]
+def lib_path(lib):
+    return os.path.join(LIB_DIR, lib.name)
+
+
+LIB_PATH, TRAIN_LIB_PATH, EVAL_LIB_PATH, IMAGE_LIB_PATH = [lib_path(lib) for lib in LIBRARIES]
+
+
+def headers(lib=HIP):
+    """Every header a unit of the library can include: *.h of its header directories + its public ABI header.  Globbed, not
+    listed: a new header (fft_regs.h was missed in round 2) is part of the source hash from the day it exists."""
+    return [h for d in lib.header_dirs for h in sorted(glob.glob(os.path.join(d, "*.h")))] + [os.path.join(INCLUDE, lib.header)]
 
 
 def local_includes(path):
@@ -78,14 +88,17 @@ def local_includes(path):
         return re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), flags=re.M)
 
 
+def unit_flags(lib, source):
+    """hipcc flags of one translation unit of a library."""
+    return lib.flags + lib.unit_flags.get(source, [])
+
+
 def flags_for(source, packed=None):
-    """hipcc flags of one translation unit.  packed: None = the product setting (NO_PACKED_FP32), 'on' / 'off' = every
-    unit with / without packed-FP32 instructions, 'fft' = only fft.hip without them (diagnostic variants)."""
+    """hipcc flags of one unit of the forward library.  packed: None = the product setting, 'on' / 'off' = every unit with /
+    without packed-FP32 instructions, 'fft' = only fft.hip without them (diagnostic variants, build_variant)."""
     if packed is None:
-        off = source in NO_PACKED_FP32
-    else:
-        off = packed == "off" or (packed == "fft" and source == "fft.hip")
-    return FLAGS + (PACKED_OFF if off else [])
+        return unit_flags(HIP, source)
+    return HIP.flags + (PACKED_OFF if packed == "off" or (packed == "fft" and source == "fft.hip") else [])
 
 
 def _hipcc():
@@ -95,51 +108,45 @@ def _hipcc():
     raise RuntimeError("hipcc not found (set HIPCC or install ROCm under /opt/rocm)")
 
 
-STAMP_PATH = LIB_PATH + ".srchash"
-
-
-def source_hash():
+def source_hash(lib=HIP):
     """sha256 over every source, header and the compiler flags of every unit: what decides whether the library is up to
     date (mtimes do not survive a copy of the tree to another machine, contents do)."""
     h = hashlib.sha256()
-    for s in SOURCES:
-        h.update((s + ":" + " ".join(flags_for(s)) + "\n").encode())
-    for path in [os.path.join(CSRC, s) for s in SOURCES] + headers():
+    for s in lib.sources:
+        h.update((s + ":" + " ".join(unit_flags(lib, s)) + "\n").encode())
+    for path in [os.path.join(lib.csrc, s) for s in lib.sources] + headers(lib):
         h.update(os.path.basename(path).encode())
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()
 
 
-def up_to_date():
-    """True when libos2d_hip.so exists and was built from exactly the sources in the tree."""
-    if not (os.path.exists(LIB_PATH) and os.path.exists(STAMP_PATH)):
+def up_to_date(lib=HIP):
+    """True when the library exists and was built from exactly the sources in the tree (the .srchash next to it)."""
+    if not (os.path.exists(lib_path(lib)) and os.path.exists(lib_path(lib) + ".srchash")):
         return False
-    with open(STAMP_PATH) as f:
-        return f.read().strip() == source_hash()
+    with open(lib_path(lib) + ".srchash") as f:
+        return f.read().strip() == source_hash(lib)
 
 
-def _stale(target, deps):
-    if not os.path.exists(target):
-        return True
-    t = os.path.getmtime(target)
-    return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
+def _jobs():
+    """Compilers started at once: 16 at the most, fewer when MAX_JOBS says so (a shared host reports far more CPUs than a
+    command may use)."""
+    return max(1, min(16, int(os.environ.get("MAX_JOBS") or 16)))
 
 
-def _compile_all(hipcc, build_dir, packed, extra, force, verbose):
+def _compile(hipcc, csrc, units, build_dir, verbose):
+    """units: [(source, flags)].  Compiles every one of them, _jobs() at a time; returns the objects."""
     os.makedirs(build_dir, exist_ok=True)
     objs, procs = [], []
-    for s in [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]:
-        src = os.path.join(CSRC, s)
-        obj = os.path.join(build_dir, s.replace(".hip", ".o"))
-        objs.append(obj)
-        if force or _stale(obj, [src] + headers()):
-            cmd = [hipcc] + flags_for(s, packed) + list(extra) + ["-c", src, "-o", obj]
-            if verbose:
-                print("[os2d_amd.build]", " ".join(cmd), flush=True)
-            procs.append((cmd, subprocess.Popen(cmd)))
-            if len(procs) >= (os.cpu_count() or 4):
-                _wait(procs)
+    for s, flags in units:
+        objs.append(os.path.join(build_dir, s.replace(".hip", ".o")))
+        cmd = [hipcc] + flags + ["-c", os.path.join(csrc, s), "-o", objs[-1]]
+        if verbose:
+            print("[os2d_amd.build]", " ".join(cmd), flush=True)
+        procs.append((cmd, subprocess.Popen(cmd)))
+        if len(procs) >= _jobs():
+            _wait(procs)
     _wait(procs)
     return objs
 
@@ -151,185 +158,43 @@ def _wait(procs):
         raise subprocess.CalledProcessError(1, failed[0])
 
 
-def build(force=False, verbose=True):
-    """Compile every HIP translation unit for gfx950 and link libos2d_hip.so. Returns the library path."""
+def _link(hipcc, objs, out, verbose):
+    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", out] + objs
+    if verbose:
+        print("[os2d_amd.build]", " ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+
+
+def build_library(lib, force=False, verbose=True):
+    """Compile every unit of the library for gfx950 and link it, unless its stamp matches the tree.  Object files carry no
+    record of the flags they were compiled with, so a stale stamp recompiles all of them.  Returns the library's path."""
+    path = lib_path(lib)
+    if not force and up_to_date(lib):
+        return path
     hipcc = _hipcc()
     os.makedirs(LIB_DIR, exist_ok=True)
-    # object files carry no record of the flags they were compiled with: when the stamp (sources + headers + flags) does not
-    # match, everything is recompiled - a flag change must not leave objects of the old flavour in the library
-    force = force or not up_to_date()
-    objs = _compile_all(hipcc, BUILD_DIR, None, [], force, verbose)
-    digest = source_hash()
-    if force or _stale(LIB_PATH, objs) or not up_to_date():
-        tmp = LIB_PATH + ".tmp.{}".format(os.getpid())          # link aside, then rename: a concurrent loader never
-        cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", tmp] + objs   # maps a half-written file
-        if verbose:
-            print("[os2d_amd.build]", " ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-        os.replace(tmp, LIB_PATH)
-        with open(STAMP_PATH + ".tmp", "w") as f:
-            f.write(digest + "\n")
-        os.replace(STAMP_PATH + ".tmp", STAMP_PATH)
-    build_train(force=force, verbose=verbose)
-    build_eval(force=force, verbose=verbose)
-    build_image(force=force, verbose=verbose)
+    digest = source_hash(lib)
+    objs = _compile(hipcc, lib.csrc, [(s, unit_flags(lib, s)) for s in lib.sources], os.path.join(lib.csrc, "build"), verbose)
+    tmp = path + ".tmp.{}".format(os.getpid())          # link aside, then rename: a concurrent loader never maps a
+    _link(hipcc, objs, tmp, verbose)                    # half-written file
+    os.replace(tmp, path)
+    with open(path + ".srchash.tmp", "w") as f:
+        f.write(digest + "\n")
+    os.replace(path + ".srchash.tmp", path + ".srchash")
+    return path
+
+
+def build(force=False, verbose=True):
+    """Build every library that is stale (force: all of them).  Returns the forward library's path."""
+    for lib in LIBRARIES:
+        build_library(lib, force=force, verbose=verbose)
     return LIB_PATH
 
 
-def train_headers():
-    return sorted(glob.glob(os.path.join(TRAIN_CSRC, "*.h"))) + headers() + [os.path.join(HERE, "..", "include", "os2d_train.h")]
-
-
-def train_source_hash():
-    h = hashlib.sha256((" ".join(TRAIN_FLAGS) + "\n").encode())
-    for s in TRAIN_SOURCES:
-        h.update((s + ":" + " ".join(TRAIN_UNIT_FLAGS.get(s, [])) + "\n").encode())
-    for path in [os.path.join(TRAIN_CSRC, s) for s in TRAIN_SOURCES] + train_headers():
-        h.update(os.path.basename(path).encode())
-        with open(path, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()
-
-
-def train_up_to_date():
-    stamp = TRAIN_LIB_PATH + ".srchash"
-    if not (os.path.exists(TRAIN_LIB_PATH) and os.path.exists(stamp)):
-        return False
-    with open(stamp) as f:
-        return f.read().strip() == train_source_hash()
-
-
-def build_train(force=False, verbose=True):
-    """Compile the backward-pass units for gfx950 and link libos2d_train.so.  Returns its path."""
-    if not force and train_up_to_date():
-        return TRAIN_LIB_PATH
-    hipcc = _hipcc()
-    os.makedirs(LIB_DIR, exist_ok=True)
-    os.makedirs(TRAIN_BUILD_DIR, exist_ok=True)
-    procs, objs = [], []
-    for s in TRAIN_SOURCES:
-        obj = os.path.join(TRAIN_BUILD_DIR, s.replace(".hip", ".o"))
-        objs.append(obj)
-        cmd = [hipcc] + TRAIN_FLAGS + TRAIN_UNIT_FLAGS.get(s, []) + ["-c", os.path.join(TRAIN_CSRC, s), "-o", obj]
-        if verbose:
-            print("[os2d_amd.build]", " ".join(cmd), flush=True)
-        procs.append((cmd, subprocess.Popen(cmd)))
-    _wait(procs)
-    digest = train_source_hash()
-    tmp = TRAIN_LIB_PATH + ".tmp.{}".format(os.getpid())
-    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", tmp] + objs
-    if verbose:
-        print("[os2d_amd.build]", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    os.replace(tmp, TRAIN_LIB_PATH)
-    stamp = TRAIN_LIB_PATH + ".srchash"
-    with open(stamp + ".tmp", "w") as f:
-        f.write(digest + "\n")
-    os.replace(stamp + ".tmp", stamp)
-    return TRAIN_LIB_PATH
-
-
-def eval_headers():
-    return sorted(glob.glob(os.path.join(EVAL_CSRC, "*.h"))) + headers() + [os.path.join(HERE, "..", "include", "os2d_eval.h")]
-
-
-def eval_source_hash():
-    h = hashlib.sha256((" ".join(EVAL_FLAGS) + "\n").encode())
-    for path in [os.path.join(EVAL_CSRC, s) for s in EVAL_SOURCES] + eval_headers():
-        h.update(os.path.basename(path).encode())
-        with open(path, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()
-
-
-def eval_up_to_date():
-    stamp = EVAL_LIB_PATH + ".srchash"
-    if not (os.path.exists(EVAL_LIB_PATH) and os.path.exists(stamp)):
-        return False
-    with open(stamp) as f:
-        return f.read().strip() == eval_source_hash()
-
-
-def build_eval(force=False, verbose=True):
-    """Compile the evaluation units for gfx950 and link libos2d_eval.so.  Returns its path."""
-    if not force and eval_up_to_date():
-        return EVAL_LIB_PATH
-    hipcc = _hipcc()
-    os.makedirs(LIB_DIR, exist_ok=True)
-    os.makedirs(EVAL_BUILD_DIR, exist_ok=True)
-    procs, objs = [], []
-    for s in EVAL_SOURCES:
-        obj = os.path.join(EVAL_BUILD_DIR, s.replace(".hip", ".o"))
-        objs.append(obj)
-        cmd = [hipcc] + EVAL_FLAGS + ["-c", os.path.join(EVAL_CSRC, s), "-o", obj]
-        if verbose:
-            print("[os2d_amd.build]", " ".join(cmd), flush=True)
-        procs.append((cmd, subprocess.Popen(cmd)))
-    _wait(procs)
-    digest = eval_source_hash()
-    tmp = EVAL_LIB_PATH + ".tmp.{}".format(os.getpid())
-    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", tmp] + objs
-    if verbose:
-        print("[os2d_amd.build]", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    os.replace(tmp, EVAL_LIB_PATH)
-    stamp = EVAL_LIB_PATH + ".srchash"
-    with open(stamp + ".tmp", "w") as f:
-        f.write(digest + "\n")
-    os.replace(stamp + ".tmp", stamp)
-    return EVAL_LIB_PATH
-
-
-def image_headers():
-    """(its units include none of csrc/*.h)"""
-    return sorted(glob.glob(os.path.join(IMAGE_CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "os2d_image.h")]
-
-
-def image_source_hash():
-    h = hashlib.sha256((" ".join(IMAGE_FLAGS) + "\n").encode())
-    for path in [os.path.join(IMAGE_CSRC, s) for s in IMAGE_SOURCES] + image_headers():
-        h.update(os.path.basename(path).encode())
-        with open(path, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()
-
-
-def image_up_to_date():
-    stamp = IMAGE_LIB_PATH + ".srchash"
-    if not (os.path.exists(IMAGE_LIB_PATH) and os.path.exists(stamp)):
-        return False
-    with open(stamp) as f:
-        return f.read().strip() == image_source_hash()
-
-
-def build_image(force=False, verbose=True):
-    """Compile the image units for gfx950 and link libos2d_image.so.  Returns its path."""
-    if not force and image_up_to_date():
-        return IMAGE_LIB_PATH
-    hipcc = _hipcc()
-    os.makedirs(LIB_DIR, exist_ok=True)
-    os.makedirs(IMAGE_BUILD_DIR, exist_ok=True)
-    procs, objs = [], []
-    for s in IMAGE_SOURCES:
-        obj = os.path.join(IMAGE_BUILD_DIR, s.replace(".hip", ".o"))
-        objs.append(obj)
-        cmd = [hipcc] + IMAGE_FLAGS + ["-c", os.path.join(IMAGE_CSRC, s), "-o", obj]
-        if verbose:
-            print("[os2d_amd.build]", " ".join(cmd), flush=True)
-        procs.append((cmd, subprocess.Popen(cmd)))
-    _wait(procs)
-    digest = image_source_hash()
-    tmp = IMAGE_LIB_PATH + ".tmp.{}".format(os.getpid())
-    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", tmp] + objs
-    if verbose:
-        print("[os2d_amd.build]", " ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    os.replace(tmp, IMAGE_LIB_PATH)
-    stamp = IMAGE_LIB_PATH + ".srchash"
-    with open(stamp + ".tmp", "w") as f:
-        f.write(digest + "\n")
-    os.replace(stamp + ".tmp", stamp)
-    return IMAGE_LIB_PATH
+# The names the per-library test fixtures call: each is the record's field or the one function bound to the record.
+TRAIN_SOURCES, EVAL_SOURCES, IMAGE_SOURCES = TRAIN.sources, EVAL.sources, IMAGE.sources
+build_train, build_eval, build_image = [functools.partial(build_library, lib) for lib in (TRAIN, EVAL, IMAGE)]
+train_up_to_date = functools.partial(up_to_date, TRAIN)
 
 
 def build_variant(tag, packed=None, extra=(), verbose=False):
@@ -338,9 +203,9 @@ def build_variant(tag, packed=None, extra=(), verbose=False):
     OS2D_HIP_LIB=tools/diag_libs/<tag>/libos2d_hip.so selects it at run time (os2d_amd/_lib.py)."""
     hipcc = _hipcc()
     out = os.path.join(VARIANT_DIR, tag)
-    objs = _compile_all(hipcc, os.path.join(out, "build"), packed, extra, True, verbose)
+    objs = _compile(hipcc, CSRC, [(s, flags_for(s, packed) + list(extra)) for s in SOURCES], os.path.join(out, "build"), verbose)
     lib = os.path.join(out, "libos2d_hip.so")
-    subprocess.check_call([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs)
+    _link(hipcc, objs, lib, False)
     shutil.rmtree(os.path.join(out, "build"))
     with open(os.path.join(out, "FLAGS.txt"), "w") as f:
         f.write("packed={} extra={}\n".format(packed, " ".join(extra)))
@@ -354,11 +219,9 @@ if __name__ == "__main__":
         tag = argv[i + 1]
         packed = argv[argv.index("--packed") + 1] if "--packed" in argv else None
         print(build_variant(tag, packed, [a for a in argv if a.startswith("-D")], verbose=True))
-    elif "--train" in argv:
-        print(build_train(force="--force" in argv))
-    elif "--eval" in argv:
-        print(build_eval(force="--force" in argv))
-    elif "--image" in argv:
-        print(build_image(force="--force" in argv))
     else:
-        print(build(force="--force" in argv))
+        only = [lib for lib, switch in ((TRAIN, "--train"), (EVAL, "--eval"), (IMAGE, "--image")) if switch in argv]
+        if only:
+            print(build_library(only[0], force="--force" in argv))
+        else:
+            print(build(force="--force" in argv))

@@ -1,5 +1,4 @@
 // C ABI of libos2d_hip.so (include/os2d_hip.h): argument checking, workspace carving, stage sequencing.
-#include <stdarg.h>
 #include <stdio.h>
 
 #include "../../include/os2d_hip.h"
@@ -11,10 +10,6 @@
 #include <vector>
 
 namespace {
-thread_local char g_err[512] = {0};
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
 struct ConvShape {
   int cout, cin, ks, mt;
 };
@@ -161,17 +156,10 @@ void os2d_debug_set_dump(void* stream, int slot, void* dst, size_t bytes) {
 #endif
 }
 
-void os2d_set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
 extern "C" {
 
 int os2d_abi_version(void) { return OS2D_ABI_VERSION; }
-const char* os2d_last_error(void) { return g_err; }
+const char* os2d_last_error(void) { return os2d_error_text; }
 
 size_t os2d_packed_conv_floats(int layer) {
   ConvShape s;
@@ -202,7 +190,7 @@ int os2d_pack_conv(int layer, int P, const float* w, const float* b, const float
     return -1;
   }
   return os2d_launch_pack_conv(w, b, bn_weight, bn_bias, bn_running_mean, bn_running_var, bn_eps, s.cout, s.cin, s.ks,
-                               s.mt, packed_w, packed_b, S(stream));
+                               s.mt, packed_w, packed_b, os2d_stream(stream));
 }
 
 int os2d_class_prepare(const float* src, int C, int h, int w, int normalize, float* q15, float* qp, void* stream) {
@@ -210,7 +198,7 @@ int os2d_class_prepare(const float* src, int C, int h, int w, int normalize, flo
     os2d_set_error("os2d_class_prepare: bad arguments (C=%d h=%d w=%d)", C, h, w);
     return -1;
   }
-  return os2d_launch_class_prepare(src, C, h, w, normalize, q15, qp, S(stream));
+  return os2d_launch_class_prepare(src, C, h, w, normalize, q15, qp, os2d_stream(stream));
 }
 
 size_t os2d_class_prepare_workspace_floats(int B, int C) {
@@ -224,7 +212,7 @@ int os2d_class_prepare_batch(const float* const* srcs, const int* sizes, int B, 
     os2d_set_error("os2d_class_prepare_batch: bad arguments (B=%d C=%d; at most 65535 classes per call)", B, C);
     return -1;
   }
-  return os2d_launch_class_prepare_batch(srcs, sizes, B, C, normalize, q15, qp, workspace, S(stream));
+  return os2d_launch_class_prepare_batch(srcs, sizes, B, C, normalize, q15, qp, workspace, os2d_stream(stream));
 }
 
 size_t os2d_plane_floats(int H, int W) { return (size_t)os2d_plane(H, W); }
@@ -264,7 +252,7 @@ int os2d_fm_sumsq(const float* fm, float* sumsq, int A, int C, int H, int W, voi
     os2d_set_error("os2d_fm_sumsq: bad arguments");
     return -1;
   }
-  return os2d_launch_fm_sumsq(fm, sumsq, A, C, H * W, S(stream));
+  return os2d_launch_fm_sumsq(fm, sumsq, A, C, H * W, os2d_stream(stream));
 }
 
 int os2d_corr(const float* fm, const float* qp, const float* sumsq, float* corr, float* rnorm, int A, int B, int C,
@@ -274,9 +262,9 @@ int os2d_corr(const float* fm, const float* qp, const float* sumsq, float* corr,
     return -1;
   }
   if (!head_args_ok(A, B, C, H, W, 6)) return -1;
-  int rc = os2d_launch_border_zero(rnorm, A * B * OS2D_KP, H, W, S(stream));
+  int rc = os2d_launch_border_zero(rnorm, A * B * OS2D_KP, H, W, os2d_stream(stream));
   if (rc) return rc;
-  return os2d_launch_corr(fm, qp, sumsq, corr, rnorm, nullptr, A, B, C, H, W, 0, S(stream));
+  return os2d_launch_corr(fm, qp, sumsq, corr, rnorm, nullptr, A, B, C, H, W, 0, os2d_stream(stream));
 }
 
 size_t os2d_corr_f16x3_workspace_bytes(int A, int C, int H, int W) {
@@ -297,10 +285,10 @@ int os2d_corr_f16x3(const float* fm, const void* qs, float* corr, void* rshb, in
   }
   float* sumsq = static_cast<float*>(workspace);
   void* fs = static_cast<char*>(workspace) + align_up((size_t)A * H * W * sizeof(float), 256);
-  int rc = os2d_launch_fm_sumsq(fm, sumsq, A, C, H * W, S(stream));
-  if (!rc) rc = os2d_launch_split_fm(fm, sumsq, fs, A, C, H * W, nullptr, 0, Os2dRangeFlag{nullptr, 0}, S(stream));
-  if (!rc) rc = os2d_launch_border_zero_shb(rshb, A * B, H, W, S(stream));
-  if (!rc) rc = os2d_launch_corr_f16x3(fs, qs, corr, rshb, nullptr, nullptr, 0, A, B, C, H, W, S(stream));
+  int rc = os2d_launch_fm_sumsq(fm, sumsq, A, C, H * W, os2d_stream(stream));
+  if (!rc) rc = os2d_launch_split_fm(fm, sumsq, fs, A, C, H * W, nullptr, 0, Os2dRangeFlag{nullptr, 0}, os2d_stream(stream));
+  if (!rc) rc = os2d_launch_border_zero_shb(rshb, A * B, H, W, os2d_stream(stream));
+  if (!rc) rc = os2d_launch_corr_f16x3(fs, qs, corr, rshb, nullptr, nullptr, 0, A, B, C, H, W, os2d_stream(stream));
   return rc;
 }
 
@@ -323,15 +311,15 @@ int os2d_corr_f16x3_packed(const float* fm, const void* qs, float* corr, float* 
   float* sumsq = static_cast<float*>(workspace);
   void* fs = static_cast<char*>(workspace) + align_up((size_t)A * H * W * sizeof(float), 256);
   void* sumfx = static_cast<char*>(workspace) + align_up(os2d_corr_f16x3_workspace_bytes(A, C, H, W), 256);
-  int rc = os2d_launch_fm_sumsq(fm, sumsq, A, C, H * W, S(stream));
-  if (!rc) rc = os2d_launch_split_fm(fm, sumsq, fs, A, C, H * W, nullptr, 0, Os2dRangeFlag{nullptr, 0}, S(stream));
+  int rc = os2d_launch_fm_sumsq(fm, sumsq, A, C, H * W, os2d_stream(stream));
+  if (!rc) rc = os2d_launch_split_fm(fm, sumsq, fs, A, C, H * W, nullptr, 0, Os2dRangeFlag{nullptr, 0}, os2d_stream(stream));
   if (form < -1 || form > 7 || (form >= 0 && (form & 3) > 1)) {
     os2d_set_error("os2d_corr_f16x3_packed: form %d (0 padded | 1 packed | -1 the head's choice; + 4: no half tiles at the tail)", form);
     return -1;
   }
   const bool packed = form < 0 ? os2d_corr_f16x3_use_packed(A, B, H, W) != 0 : (form & 1) != 0;
-  if (!rc && packed) rc = os2d_launch_corr_sums_clear(sumfx, A, B, H, W, S(stream));
-  if (!rc) rc = os2d_launch_corr_f16x3(fs, qs, corr, nullptr, inv_norm, packed ? sumfx : nullptr, (form >= 0 && (form & 4)) ? 2 : 0, A, B, C, H, W, S(stream));
+  if (!rc && packed) rc = os2d_launch_corr_sums_clear(sumfx, A, B, H, W, os2d_stream(stream));
+  if (!rc) rc = os2d_launch_corr_f16x3(fs, qs, corr, nullptr, inv_norm, packed ? sumfx : nullptr, (form >= 0 && (form & 4)) ? 2 : 0, A, B, C, H, W, os2d_stream(stream));
   return rc;
 }
 
@@ -340,7 +328,7 @@ int os2d_corr_normalize(const float* corr, float* rnorm, int NB, int H, int W, v
     os2d_set_error("os2d_corr_normalize: bad arguments");
     return -1;
   }
-  return os2d_launch_corr_normalize(corr, rnorm, NB, H, W, S(stream));
+  return os2d_launch_corr_normalize(corr, rnorm, NB, H, W, os2d_stream(stream));
 }
 
 int os2d_transform_conv(int layer, const float* in, const float* packed_w, const float* packed_b, float* out, int NB,
@@ -349,7 +337,7 @@ int os2d_transform_conv(int layer, const float* in, const float* packed_w, const
     os2d_set_error("os2d_transform_conv: bad arguments (layer=%d NB=%d P=%d)", layer, NB, P);
     return -1;
   }
-  return os2d_launch_conv(layer, in, packed_w, packed_b, out, NB, P, H, W, S(stream));
+  return os2d_launch_conv(layer, in, packed_w, packed_b, out, NB, P, H, W, os2d_stream(stream));
 }
 
 int os2d_sample_decode(const float* corr, const float* params, int NB, int H, int W, int P, int inverse, int stride,
@@ -359,7 +347,7 @@ int os2d_sample_decode(const float* corr, const float* params, int NB, int H, in
     return -1;
   }
   return os2d_launch_sample_decode(corr, params, NB, H, W, P, inverse, stride, rec_field, NB, NB, 0, loc, cls,
-                                   corners, nullptr, 0, nullptr, S(stream));
+                                   corners, nullptr, 0, nullptr, os2d_stream(stream));
 }
 
 int os2d_decode_boxes(const float* loc, int NB, int H, int W, int stride, int rec_field, float img_w, float img_h,
@@ -368,7 +356,7 @@ int os2d_decode_boxes(const float* loc, int NB, int H, int W, int stride, int re
     os2d_set_error("os2d_decode_boxes: bad arguments");
     return -1;
   }
-  return os2d_launch_decode_boxes(loc, NB, H, W, stride, rec_field, img_w, img_h, boxes, S(stream));
+  return os2d_launch_decode_boxes(loc, NB, H, W, stride, rec_field, img_w, img_h, boxes, os2d_stream(stream));
 }
 
 int os2d_detect_level_supported(int H, int W) { return os2d_detect_level_lds_bytes(H, W) != 0 ? 1 : 0; }
@@ -382,7 +370,7 @@ int os2d_detect_level(const float* loc, const float* cls, int B, int H, int W, i
     return -1;
   }
   return os2d_launch_detect_level(loc, cls, B, H, W, stride, rec_field, img_w, img_h, os2d_box_ops_scale<OS2D_BOX_MAX_OPS>(scale_x, scale_y),
-                                  score_threshold, iou_threshold, out_boxes, out_scores, out_index, out_count, S(stream));
+                                  score_threshold, iou_threshold, out_boxes, out_scores, out_index, out_count, os2d_stream(stream));
 }
 
 int os2d_detect_level_ops(const float* loc, const float* cls, int B, int H, int W, int stride, int rec_field, float img_w,
@@ -400,7 +388,7 @@ int os2d_detect_level_ops(const float* loc, const float* cls, int B, int H, int 
     return -1;
   }
   return os2d_launch_detect_level(loc, cls, B, H, W, stride, rec_field, img_w, img_h, ops, score_threshold, iou_threshold,
-                                  out_boxes, out_scores, out_index, out_count, S(stream));
+                                  out_boxes, out_scores, out_index, out_count, os2d_stream(stream));
 }
 
 int os2d_nms_workspace_bytes(int NC, int N, size_t* bytes) {
@@ -426,7 +414,7 @@ int os2d_nms(const float* boxes, const int* counts, int NC, int N, float iou_thr
     os2d_set_error("os2d_nms: workspace too small");
     return -2;
   }
-  return os2d_launch_nms(boxes, counts, NC, N, iou_threshold, keep, num_keep, workspace, S(stream));
+  return os2d_launch_nms(boxes, counts, NC, N, iou_threshold, keep, num_keep, workspace, os2d_stream(stream));
 }
 
 int os2d_head_forward_ex(const float* fm, const float* qp, const void* w1, const float* b1, const void* w2,
@@ -489,7 +477,7 @@ int os2d_head_forward_ex(const float* fm, const float* qp, const void* w1, const
     if (guess < 1) guess = 1;
     Bc = guess;
   }
-  hipStream_t st = S(stream);
+  hipStream_t st = os2d_stream(stream);
   char* ws = static_cast<char*>(workspace);
   const Carve c = carve(A, Bc, C, H, W, P, fft_bins, fft_T, xch);
   float* invn = fft_bins ? reinterpret_cast<float*>(ws + c.invn) : nullptr;
@@ -662,7 +650,7 @@ int os2d_class_split(const float* qp, void* qs, int B, int C, void* stream) {
     os2d_set_error("os2d_class_split: bad arguments");
     return -1;
   }
-  return os2d_launch_split_qp(qp, qs, B, C, S(stream));
+  return os2d_launch_split_qp(qp, qs, B, C, os2d_stream(stream));
 }
 
 size_t os2d_packed_conv_bytes(int layer, int precision) {
@@ -688,12 +676,12 @@ int os2d_pack_conv_f16x3(int layer, int P, const float* w, const float* b, const
   if (layer == 1)
     return os2d_launch_pack_conv_f16(w, b, bn_weight, bn_bias, bn_running_mean, bn_running_var, bn_eps, 128, OS2D_K, 7,
                                      128, os2d_conv1_steps_padded(), weight_exp, in_exp, out_exp, packed_w, packed_b,
-                                     S(stream));
+                                     os2d_stream(stream));
   if (layer == 2)
     return os2d_launch_pack_conv_f16(w, b, bn_weight, bn_bias, bn_running_mean, bn_running_var, bn_eps, 64, 128, 5, 64,
-                                     14, weight_exp, in_exp, out_exp, packed_w, packed_b, S(stream));
+                                     14, weight_exp, in_exp, out_exp, packed_w, packed_b, os2d_stream(stream));
   return os2d_launch_pack_conv_f16(w, b, bn_weight, bn_bias, bn_running_mean, bn_running_var, bn_eps, P, 64, 5, 32, 14,
-                                   weight_exp, in_exp, nullptr, packed_w, packed_b, S(stream));
+                                   weight_exp, in_exp, nullptr, packed_w, packed_b, os2d_stream(stream));
 }
 
 int os2d_rnorm_exp(void) { return OS2D_RNORM_EXP; }
@@ -703,7 +691,7 @@ int os2d_corr_normalize_f16x3(const float* corr, void* rshb, int NB, int H, int 
     os2d_set_error("os2d_corr_normalize_f16x3: bad arguments");
     return -1;
   }
-  return os2d_launch_corr_normalize_shb(corr, rshb, NB, H, W, S(stream));
+  return os2d_launch_corr_normalize_shb(corr, rshb, NB, H, W, os2d_stream(stream));
 }
 
 int os2d_transform_conv_f16x3(int layer, const void* in, const void* packed_w, const float* packed_b, void* out, int NB,
@@ -717,7 +705,7 @@ int os2d_transform_conv_f16x3(int layer, const void* in, const void* packed_w, c
     os2d_set_error("os2d_transform_conv_f16x3: feature map width %d > %d", W, layer == 1 ? OS2D_MAX_W_DIRECT7 : OS2D_MAX_W);
     return -1;
   }
-  return os2d_launch_conv_f16x3(layer, in, packed_w, packed_b, Os2dRangeFlag{status, OS2D_STATUS_F16_RANGE}, out, NB, P, H, W, terms, S(stream));
+  return os2d_launch_conv_f16x3(layer, in, packed_w, packed_b, Os2dRangeFlag{status, OS2D_STATUS_F16_RANGE}, out, NB, P, H, W, terms, os2d_stream(stream));
 }
 
 int os2d_fft_sizes(int H, int W, int* P, int* Q, int* nbins) {
@@ -755,7 +743,7 @@ int os2d_fft_forward(const float* corr, const float* inv_norm, float* X, const f
     os2d_set_error("os2d_fft_forward: bad arguments");
     return -1;
   }
-  return os2d_launch_fft_forward(corr, inv_norm, X, twQ, twP, NB, C, H, W, S(stream));
+  return os2d_launch_fft_forward(corr, inv_norm, X, twQ, twP, NB, C, H, W, os2d_stream(stream));
 }
 
 int os2d_fft_inverse_ex(const float* Y, const float* packed_b, void* out, const float* twQ, const float* twP, int NB, int Cout,
@@ -765,9 +753,9 @@ int os2d_fft_inverse_ex(const float* Y, const float* packed_b, void* out, const 
     os2d_set_error("os2d_fft_inverse: bad arguments (Cout must be 128: the 7x7 layer)");
     return -1;
   }
-  int rc = os2d_launch_border_zero_shb_planes(out, NB * (Cout / 8) * 2, H, W, S(stream));
+  int rc = os2d_launch_border_zero_shb_planes(out, NB * (Cout / 8) * 2, H, W, os2d_stream(stream));
   if (rc) return rc;
-  return os2d_launch_fft_inverse(Y, packed_b, 128, out, twQ, twP, NB, Cout, H, W, Os2dRangeFlag{status, OS2D_STATUS_F16_RANGE}, layout, 0, S(stream));
+  return os2d_launch_fft_inverse(Y, packed_b, 128, out, twQ, twP, NB, Cout, H, W, Os2dRangeFlag{status, OS2D_STATUS_F16_RANGE}, layout, 0, os2d_stream(stream));
 }
 
 int os2d_fft_inverse(const float* Y, const float* packed_b, void* out, const float* twQ, const float* twP, int NB, int Cout,
@@ -790,7 +778,7 @@ int os2d_spectral_gemm(const float* wspec, const float* X, float* Y, int NB, int
     os2d_set_error("os2d_spectral_gemm: buffers must be 16-byte aligned");
     return -1;
   }
-  return os2d_launch_spectral_gemm(wspec, X, Y, NB, C, Cout, nbins, S(stream));
+  return os2d_launch_spectral_gemm(wspec, X, Y, NB, C, Cout, nbins, os2d_stream(stream));
 }
 
 int os2d_spectral_weights_build(const double* wfold, const double* twP64, const double* twQ64, int C, int Cout, int P, int Q,
@@ -803,7 +791,7 @@ int os2d_spectral_weights_build(const double* wfold, const double* twP64, const 
     os2d_set_error("os2d_spectral_weights_build: out must be 16-byte, workspace 8-byte aligned");
     return -1;
   }
-  return os2d_launch_spectra_pack(wfold, twP64, twQ64, C, Cout, P, Q, nbins, split, 0, out, workspace, S(stream));
+  return os2d_launch_spectra_pack(wfold, twP64, twQ64, C, Cout, P, Q, nbins, split, 0, out, workspace, os2d_stream(stream));
 }
 
 size_t os2d_spectral_weight16_bytes(int C, int nbins) {
@@ -828,7 +816,7 @@ int os2d_spectral_gemm_f16(const void* w16, const float* X, float* Y, int NB, in
     os2d_set_error("os2d_spectral_gemm_f16: buffers must be 16-byte aligned");
     return -1;
   }
-  return os2d_launch_spectral_gemm_f16(w16, X, Y, NB, C, Cout, nbins, xscale, 0, 0, S(stream));
+  return os2d_launch_spectral_gemm_f16(w16, X, Y, NB, C, Cout, nbins, xscale, 0, 0, os2d_stream(stream));
 }
 
 /* ---- the transforms of the frequency-domain 7x7 layer as matrix products (dft_mfma.hip; OS2D_PRECISION_FFTX3) */
@@ -856,7 +844,7 @@ int os2d_dft_matrices_build(const double* twP64, const double* twQ64, int P, int
     os2d_set_error("os2d_dft_matrices_build: bad arguments (out must be 16-byte aligned)");
     return -1;
   }
-  return os2d_launch_dft_matrices(twP64, twQ64, P, Q, out, S(stream));
+  return os2d_launch_dft_matrices(twP64, twQ64, P, Q, out, os2d_stream(stream));
 }
 
 int os2d_dft_forward(const float* corr, const float* inv_norm, float* X, const void* matrices, int NB, int C, int H, int W,
@@ -865,7 +853,7 @@ int os2d_dft_forward(const float* corr, const float* inv_norm, float* X, const v
     os2d_set_error("os2d_dft_forward: bad arguments");
     return -1;
   }
-  return os2d_launch_dft_forward(corr, inv_norm, X, matrices, NB, C, os2d_dft_channel_stride(C), H, W, S(stream));
+  return os2d_launch_dft_forward(corr, inv_norm, X, matrices, NB, C, os2d_dft_channel_stride(C), H, W, os2d_stream(stream));
 }
 
 int os2d_dft_inverse(const float* Y, const float* packed_b, void* out, const void* matrices, int NB, int Cout, int H, int W,
@@ -874,7 +862,7 @@ int os2d_dft_inverse(const float* Y, const float* packed_b, void* out, const voi
     os2d_set_error("os2d_dft_inverse: bad arguments (Cout must be 128: the 7x7 layer)");
     return -1;
   }
-  return os2d_launch_dft_inverse(Y, packed_b, 128, out, matrices, NB, Cout, H, W, Os2dRangeFlag{status, OS2D_STATUS_F16_RANGE}, 1, S(stream));   // incl. the plane borders
+  return os2d_launch_dft_inverse(Y, packed_b, 128, out, matrices, NB, Cout, H, W, Os2dRangeFlag{status, OS2D_STATUS_F16_RANGE}, 1, os2d_stream(stream));   // incl. the plane borders
 }
 
 int os2d_spectral_weights_build_dft(const double* wfold, const double* twP64, const double* twQ64, int C, int Cout, int P, int Q,
@@ -887,7 +875,7 @@ int os2d_spectral_weights_build_dft(const double* wfold, const double* twP64, co
     os2d_set_error("os2d_spectral_weights_build_dft: out must be 16-byte, workspace 8-byte aligned");
     return -1;
   }
-  return os2d_launch_spectra_pack(wfold, twP64, twQ64, C, Cout, P, Q, nbins, 1, 1, out, workspace, S(stream));
+  return os2d_launch_spectra_pack(wfold, twP64, twQ64, C, Cout, P, Q, nbins, 1, 1, out, workspace, os2d_stream(stream));
 }
 
 int os2d_spectral_gemm_f16_quads(const void* w16, const float* X, float* Y, int NB, int C, int Cout, int nbins, float xscale,
@@ -900,7 +888,7 @@ int os2d_spectral_gemm_f16_quads(const void* w16, const float* X, float* Y, int 
     os2d_set_error("os2d_spectral_gemm_f16_quads: buffers must be 16-byte aligned");
     return -1;
   }
-  return os2d_launch_spectral_gemm_f16(w16, X, Y, NB, C, Cout, nbins, xscale, 1, os2d_dft_channel_stride(C), S(stream));
+  return os2d_launch_spectral_gemm_f16(w16, X, Y, NB, C, Cout, nbins, xscale, 1, os2d_dft_channel_stride(C), os2d_stream(stream));
 }
 
 float os2d_dft_xscale(int H, int W) {
@@ -915,7 +903,7 @@ int os2d_alignment_grids(const float* params, int NB, int H, int W, int P, int i
     os2d_set_error("os2d_alignment_grids: bad arguments");
     return -1;
   }
-  return os2d_launch_alignment_grids(params, NB, H, W, P, inverse, theta, grids, S(stream));
+  return os2d_launch_alignment_grids(params, NB, H, W, P, inverse, theta, grids, os2d_stream(stream));
 }
 
 int os2d_prof_event_create(void** ev) {

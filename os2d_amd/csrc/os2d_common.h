@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../csrc_shared/abi_common.h"   // the thread's error text: os2d_set_error, os2d_refuse, os2d_launched, os2d_stream
+
 #define OS2D_PAD 3
 #define OS2D_T 15            // template side (reference head.py:66-69)
 #define OS2D_K 225           // T*T correlation channels
@@ -101,9 +103,6 @@ static inline __host__ __device__ bool os2d_interior(int n, int H, int W) {
   const int r = n - os2d_base(W);
   return r >= 0 && r < H * os2d_ws(W) && (r % os2d_ws(W)) < W;
 }
-
-// error plumbing (abi.hip)
-void os2d_set_error(const char* fmt, ...);
 
 // ---- launchers implemented by the kernel translation units (all asynchronous on `stream`) ----
 // prep.hip

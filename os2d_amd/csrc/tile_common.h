@@ -119,12 +119,4 @@ int os2d_set_dynamic_lds(K kernel, size_t bytes, const char* what) {
   }
   return 0;
 }
-static inline int os2d_launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    os2d_set_error("%s launch: %s", what, hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
-}
 #endif

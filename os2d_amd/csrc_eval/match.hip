@@ -12,16 +12,6 @@
 #include "../../include/os2d_eval.h"
 #include "../csrc/detect_common.h"
 #include "eval_common.h"
-#include <string.h>
-
-namespace {
-thread_local char g_err[512] = {0};
-}
-
-void os2d_eval_store_error(const char* text) {
-  strncpy(g_err, text, sizeof(g_err) - 1);
-  g_err[sizeof(g_err) - 1] = 0;
-}
 
 namespace {
 
@@ -108,37 +98,37 @@ __global__ __launch_bounds__(EVAL_THREADS) void resolve_kernel(const float* __re
 extern "C" {
 
 int os2d_eval_abi_version(void) { return OS2D_EVAL_ABI_VERSION; }
-const char* os2d_eval_last_error(void) { return g_err; }
+const char* os2d_eval_last_error(void) { return os2d_error_text; }
 
 int os2d_eval_count_gt(const int* gt_labels, const unsigned char* gt_difficult, int G, int L, int* n_pos, int* gt_count, void* stream) {
-  if (G < 0 || L < 1) return refuse("count_gt: bad shape (G >= 0, L >= 1)");
-  if (!n_pos || !gt_count || (G > 0 && (!gt_labels || !gt_difficult))) return refuse("count_gt: null pointer");
-  if (hipMemsetAsync(n_pos, 0, sizeof(int) * ((size_t)L + 1), S(stream)) != hipSuccess ||
-      hipMemsetAsync(gt_count, 0, sizeof(int) * (size_t)L, S(stream)) != hipSuccess)
-    return launched("count_gt: memset");
+  if (G < 0 || L < 1) return os2d_refuse("count_gt: bad shape (G >= 0, L >= 1)");
+  if (!n_pos || !gt_count || (G > 0 && (!gt_labels || !gt_difficult))) return os2d_refuse("count_gt: null pointer");
+  if (hipMemsetAsync(n_pos, 0, sizeof(int) * ((size_t)L + 1), os2d_stream(stream)) != hipSuccess ||
+      hipMemsetAsync(gt_count, 0, sizeof(int) * (size_t)L, os2d_stream(stream)) != hipSuccess)
+    return os2d_launched("count_gt: memset");
   if (G == 0) return 0;
-  hipLaunchKernelGGL(count_gt_kernel, dim3((G + EVAL_THREADS - 1) / EVAL_THREADS), dim3(EVAL_THREADS), 0, S(stream), gt_labels, gt_difficult,
+  hipLaunchKernelGGL(count_gt_kernel, dim3((G + EVAL_THREADS - 1) / EVAL_THREADS), dim3(EVAL_THREADS), 0, os2d_stream(stream), gt_labels, gt_difficult,
                      G, L, n_pos, gt_count);
-  return launched("count_gt_kernel");
+  return os2d_launched("count_gt_kernel");
 }
 
 int os2d_eval_match(const float* det_boxes, const float* det_scores, const int* det_labels, const int* det_offsets, int D, int N,
                     const float* gt_boxes, const int* gt_labels, const unsigned char* gt_difficult, const int* gt_offsets, int G,
                     float iou_thresh, int* gt_index, unsigned long long* winner, signed char* match, void* stream) {
-  if (D < 0 || G < 0 || N < 1) return refuse("match: bad shape (D >= 0, G >= 0, N >= 1)");
-  if (!det_offsets || !gt_offsets) return refuse("match: null pointer (offsets)");
+  if (D < 0 || G < 0 || N < 1) return os2d_refuse("match: bad shape (D >= 0, G >= 0, N >= 1)");
+  if (!det_offsets || !gt_offsets) return os2d_refuse("match: null pointer (offsets)");
   if (D == 0) return 0;
-  if (!det_boxes || !det_scores || !det_labels || !gt_index || !match) return refuse("match: null pointer (detections)");
-  if (G > 0 && (!gt_boxes || !gt_labels || !gt_difficult || !winner)) return refuse("match: null pointer (ground truth)");
-  if (((size_t)det_boxes | (size_t)gt_boxes) & 15) return refuse("match: boxes must be 16-byte aligned");
-  if (G > 0 && hipMemsetAsync(winner, 0xff, sizeof(u64) * (size_t)G, S(stream)) != hipSuccess) return launched("match: memset");
+  if (!det_boxes || !det_scores || !det_labels || !gt_index || !match) return os2d_refuse("match: null pointer (detections)");
+  if (G > 0 && (!gt_boxes || !gt_labels || !gt_difficult || !winner)) return os2d_refuse("match: null pointer (ground truth)");
+  if (((size_t)det_boxes | (size_t)gt_boxes) & 15) return os2d_refuse("match: boxes must be 16-byte aligned");
+  if (G > 0 && hipMemsetAsync(winner, 0xff, sizeof(u64) * (size_t)G, os2d_stream(stream)) != hipSuccess) return os2d_launched("match: memset");
   const dim3 grid((D + EVAL_THREADS - 1) / EVAL_THREADS);
-  hipLaunchKernelGGL(match_kernel, grid, dim3(EVAL_THREADS), 0, S(stream), reinterpret_cast<const float4*>(det_boxes), det_scores, det_labels,
+  hipLaunchKernelGGL(match_kernel, grid, dim3(EVAL_THREADS), 0, os2d_stream(stream), reinterpret_cast<const float4*>(det_boxes), det_scores, det_labels,
                      det_offsets, D, N, reinterpret_cast<const float4*>(gt_boxes), gt_labels, gt_offsets, iou_thresh, gt_index, winner);
-  if (int rc = launched("match_kernel")) return rc;
-  hipLaunchKernelGGL(resolve_kernel, grid, dim3(EVAL_THREADS), 0, S(stream), det_scores, det_offsets, D, N, gt_difficult, gt_index, winner,
+  if (int rc = os2d_launched("match_kernel")) return rc;
+  hipLaunchKernelGGL(resolve_kernel, grid, dim3(EVAL_THREADS), 0, os2d_stream(stream), det_scores, det_offsets, D, N, gt_difficult, gt_index, winner,
                      match);
-  return launched("resolve_kernel");
+  return os2d_launched("resolve_kernel");
 }
 
 }  // extern "C"

@@ -298,12 +298,12 @@ int device_scan(const P& p, int D, const ScanWorkspace& w, hipStream_t st, const
   typedef typename P::T T;
   const int nt = tiles(D);
   hipLaunchKernelGGL(scan_partials_kernel<P>, dim3(nt), dim3(EVAL_THREADS), 0, st, p, D, static_cast<T*>(w.part_v), w.part_f);
-  if (int rc = launched(what)) return rc;
+  if (int rc = os2d_launched(what)) return rc;
   hipLaunchKernelGGL(scan_carries_kernel<P>, dim3(1), dim3(EVAL_THREADS), 0, st, static_cast<const T*>(w.part_v), w.part_f, nt,
                      static_cast<T*>(w.carry));
-  if (int rc = launched(what)) return rc;
+  if (int rc = os2d_launched(what)) return rc;
   hipLaunchKernelGGL(scan_apply_kernel<P>, dim3(nt), dim3(EVAL_THREADS), 0, st, p, D, static_cast<const T*>(w.carry));
-  return launched(what);
+  return os2d_launched(what);
 }
 
 }  // namespace
@@ -315,12 +315,12 @@ size_t os2d_eval_scan_workspace_bytes(int D) { return D <= 0 ? 0 : 3 * align256(
 int os2d_eval_prec_rec(const signed char* match, const unsigned int* perm, const int* seg, const int* n_pos, int L, int D,
                        unsigned long long* tpfp, double* prec, double* rec, double* rec_last, void* workspace, size_t workspace_bytes,
                        void* stream) {
-  if (D < 0 || L < 1) return refuse("prec_rec: bad shape (D >= 0, L >= 1)");
+  if (D < 0 || L < 1) return os2d_refuse("prec_rec: bad shape (D >= 0, L >= 1)");
   if (D == 0) return 0;
-  if (!match || !perm || !n_pos || !prec || !rec || !rec_last) return refuse("prec_rec: null pointer");
+  if (!match || !perm || !n_pos || !prec || !rec || !rec_last) return os2d_refuse("prec_rec: null pointer");
   ScanWorkspace w;
   if (!carve(workspace, workspace_bytes, D, &w)) {
-    os2d_eval_store_error("prec_rec: workspace too small");
+    os2d_set_error("prec_rec: workspace too small");
     return -2;
   }
   PrecRec p;
@@ -333,27 +333,27 @@ int os2d_eval_prec_rec(const signed char* match, const unsigned int* perm, const
   p.prec = prec;
   p.rec = rec;
   p.rec_last = rec_last;
-  return device_scan(p, D, w, S(stream), "prec_rec scan");
+  return device_scan(p, D, w, os2d_stream(stream), "prec_rec scan");
 }
 
 int os2d_eval_ap(const double* prec, const double* rec, const int* seg, int L, int D, int use_07_metric, double* mpre, double* acc,
                  void* workspace, size_t workspace_bytes, void* stream) {
-  if (D < 0 || L < 1) return refuse("ap: bad shape (D >= 0, L >= 1)");
+  if (D < 0 || L < 1) return os2d_refuse("ap: bad shape (D >= 0, L >= 1)");
   if (D == 0) return 0;
-  if (!prec || !rec || !mpre || !acc) return refuse("ap: null pointer");
+  if (!prec || !rec || !mpre || !acc) return os2d_refuse("ap: null pointer");
   ScanWorkspace w;
   if (!carve(workspace, workspace_bytes, D, &w)) {
-    os2d_eval_store_error("ap: workspace too small");
+    os2d_set_error("ap: workspace too small");
     return -2;
   }
   RunMax m;
   m.prec = prec;
   m.seg = seg;
   m.mpre = mpre;
-  if (int rc = device_scan(m, D, w, S(stream), "running maximum scan")) return rc;
+  if (int rc = device_scan(m, D, w, os2d_stream(stream), "running maximum scan")) return rc;
   if (use_07_metric) {
-    hipLaunchKernelGGL(ap11_kernel, dim3((D + EVAL_THREADS - 1) / EVAL_THREADS), dim3(EVAL_THREADS), 0, S(stream), rec, mpre, seg, L, D, acc);
-    return launched("ap11_kernel");
+    hipLaunchKernelGGL(ap11_kernel, dim3((D + EVAL_THREADS - 1) / EVAL_THREADS), dim3(EVAL_THREADS), 0, os2d_stream(stream), rec, mpre, seg, L, D, acc);
+    return os2d_launched("ap11_kernel");
   }
   ApSum a;
   a.rec = rec;
@@ -361,16 +361,16 @@ int os2d_eval_ap(const double* prec, const double* rec, const int* seg, int L, i
   a.seg = seg;
   a.L = L;
   a.acc = acc;
-  return device_scan(a, D, w, S(stream), "average precision scan");
+  return device_scan(a, D, w, os2d_stream(stream), "average precision scan");
 }
 
 int os2d_eval_finalise(const double* acc, const double* rec_last, const int* n_pos, int L, int use_07_metric, double* ap_per_class,
                        double* recall_per_class, double* n_pos_out, double* scalars, void* stream) {
-  if (L < 1) return refuse("finalise: bad shape (L >= 1)");
-  if (!acc || !rec_last || !n_pos || !ap_per_class || !recall_per_class || !n_pos_out || !scalars) return refuse("finalise: null pointer");
-  hipLaunchKernelGGL(finalise_kernel, dim3(1), dim3(EVAL_THREADS), 0, S(stream), acc, rec_last, n_pos, L, use_07_metric, ap_per_class,
+  if (L < 1) return os2d_refuse("finalise: bad shape (L >= 1)");
+  if (!acc || !rec_last || !n_pos || !ap_per_class || !recall_per_class || !n_pos_out || !scalars) return os2d_refuse("finalise: null pointer");
+  hipLaunchKernelGGL(finalise_kernel, dim3(1), dim3(EVAL_THREADS), 0, os2d_stream(stream), acc, rec_last, n_pos, L, use_07_metric, ap_per_class,
                      recall_per_class, n_pos_out, scalars);
-  return launched("finalise_kernel");
+  return os2d_launched("finalise_kernel");
 }
 
 }  // extern "C"

@@ -154,11 +154,11 @@ struct SortBuffers {
 int radix_pass(const u32* kin, const u32* iin, u32* kout, u32* iout, int D, int shift, u32* hist, hipStream_t st) {
   const int nt = tiles(D);
   hipLaunchKernelGGL(radix_hist_kernel, dim3(nt), dim3(EVAL_THREADS), 0, st, kin, D, shift, hist, nt);
-  if (int rc = launched("radix_hist_kernel")) return rc;
+  if (int rc = os2d_launched("radix_hist_kernel")) return rc;
   hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, hist, 256 * nt);
-  if (int rc = launched("radix_scan_kernel")) return rc;
+  if (int rc = os2d_launched("radix_scan_kernel")) return rc;
   hipLaunchKernelGGL(radix_scatter_kernel, dim3(nt), dim3(EVAL_THREADS), 0, st, kin, iin, kout, iout, D, shift, hist, nt);
-  return launched("radix_scatter_kernel");
+  return os2d_launched("radix_scatter_kernel");
 }
 
 }  // namespace
@@ -173,16 +173,16 @@ size_t os2d_eval_sort_workspace_bytes(int D) {
 int os2d_eval_sort(const float* det_scores, const int* det_labels, int D, int L, int label_bits, unsigned int* perm_joint,
                    unsigned int* perm_class, int* sorted_labels, int* class_offsets, void* workspace, size_t workspace_bytes, void* stream) {
   if (D < 0 || L < 1 || label_bits < 0 || label_bits > 31 || ((L - 1) >> label_bits) != 0)
-    return refuse("sort: bad shape (D >= 0, L >= 1, L <= 2^label_bits)");
-  if (!class_offsets) return refuse("sort: null pointer (class_offsets)");
-  hipStream_t st = S(stream);
+    return os2d_refuse("sort: bad shape (D >= 0, L >= 1, L <= 2^label_bits)");
+  if (!class_offsets) return os2d_refuse("sort: null pointer (class_offsets)");
+  hipStream_t st = os2d_stream(stream);
   if (D == 0) {
-    if (hipMemsetAsync(class_offsets, 0, sizeof(int) * ((size_t)L + 1), st) != hipSuccess) return launched("sort: memset");
+    if (hipMemsetAsync(class_offsets, 0, sizeof(int) * ((size_t)L + 1), st) != hipSuccess) return os2d_launched("sort: memset");
     return 0;
   }
-  if (!det_scores || !det_labels || !perm_joint || !perm_class || !sorted_labels || !workspace) return refuse("sort: null pointer");
+  if (!det_scores || !det_labels || !perm_joint || !perm_class || !sorted_labels || !workspace) return os2d_refuse("sort: null pointer");
   if (workspace_bytes < os2d_eval_sort_workspace_bytes(D)) {
-    os2d_eval_store_error("sort: workspace too small");
+    os2d_set_error("sort: workspace too small");
     return -2;
   }
   char* w = static_cast<char*>(workspace);
@@ -194,7 +194,7 @@ int os2d_eval_sort(const float* det_scores, const int* det_labels, int D, int L,
   u32* hist = reinterpret_cast<u32*>(w + 4 * each);
   const dim3 flat((D + EVAL_THREADS - 1) / EVAL_THREADS);
   hipLaunchKernelGGL(sort_init_kernel, flat, dim3(EVAL_THREADS), 0, st, det_scores, D, key_a, idx_a);
-  if (int rc = launched("sort_init_kernel")) return rc;
+  if (int rc = os2d_launched("sort_init_kernel")) return rc;
   // score key: a -> b -> a -> b -> (a, perm_joint)
   if (int rc = radix_pass(key_a, idx_a, key_b, idx_b, D, 0, hist, st)) return rc;
   if (int rc = radix_pass(key_b, idx_b, key_a, idx_a, D, 8, hist, st)) return rc;
@@ -202,7 +202,7 @@ int os2d_eval_sort(const float* det_scores, const int* det_labels, int D, int L,
   if (int rc = radix_pass(key_b, idx_b, key_a, perm_joint, D, 24, hist, st)) return rc;
   // label: starts from the joint order, so equal labels stay in descending score
   hipLaunchKernelGGL(gather_labels_kernel, flat, dim3(EVAL_THREADS), 0, st, det_labels, perm_joint, D, key_a);
-  if (int rc = launched("gather_labels_kernel")) return rc;
+  if (int rc = os2d_launched("gather_labels_kernel")) return rc;
   const int passes = label_bits <= 8 ? 1 : (label_bits + 7) / 8;
   const u32* kin = key_a;
   const u32* iin = perm_joint;
@@ -216,7 +216,7 @@ int os2d_eval_sort(const float* det_scores, const int* det_labels, int D, int L,
   }
   hipLaunchKernelGGL(class_offsets_kernel, dim3((L + 1 + EVAL_THREADS - 1) / EVAL_THREADS), dim3(EVAL_THREADS), 0, st, sorted_labels, D, L,
                      class_offsets);
-  return launched("class_offsets_kernel");
+  return os2d_launched("class_offsets_kernel");
 }
 
 }  // extern "C"

@@ -1,10 +1,8 @@
-// Shared by the translation units of libos2d_image.so: the error store, launch plumbing and the tile geometry (the library
-// links against none of the other three, so it carries its own error store as libos2d_eval.so does).
+// Shared by the translation units of libos2d_image.so: the tile geometry (error text, launch check and stream cast:
+// csrc_shared/abi_common.h).
 #ifndef OS2D_IMAGE_COMMON_H
 #define OS2D_IMAGE_COMMON_H
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <string.h>
+#include "../csrc_shared/abi_common.h"
 
 #define IMG_THREADS 256
 #define IMG_TW 128                                   // output columns of a tile
@@ -14,17 +12,5 @@
 #define IMG_LDS_BYTES 65536
 #define IMG_MAX_ROWS ((IMG_LDS_BYTES - IMG_LUT_BYTES) / (3 * IMG_TW))    // staged source rows that fit: 162
 #define IMG_PRECISION_BITS 22                        // Pillow: 32 - 8 - 2
-
-static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-// after a kernel launch: 0, or -4 with "<what>: <HIP error>" in buf
-static inline int launched(const char* what, char* buf, size_t n) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(buf, n, "%s: %s", what, hipGetErrorString(e));
-    return -4;
-  }
-  return 0;
-}
 
 #endif

@@ -15,14 +15,6 @@
 
 namespace {
 
-thread_local char g_err[512] = {0};
-
-int refuse(const char* text) {
-  strncpy(g_err, text, sizeof(g_err) - 1);
-  g_err[sizeof(g_err) - 1] = 0;
-  return -1;
-}
-
 struct Resample {
   const unsigned char* src;
   long long row_pitch, image_stride;
@@ -172,33 +164,33 @@ bool misaligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) &
 extern "C" {
 
 int os2d_image_abi_version(void) { return OS2D_IMAGE_ABI_VERSION; }
-const char* os2d_image_last_error(void) { return g_err; }
+const char* os2d_image_last_error(void) { return os2d_error_text; }
 
 int os2d_image_resample(const unsigned char* src, int A, int img_w, int img_h, long long row_pitch, long long image_stride, int x0,
                         int y0, int w, int h, int hflip, int vflip, const int* xcoef, const int* xbounds, const int* xbounds_host,
                         int kx, const int* ycoef, const int* ybounds, const int* ybounds_host, int ky, int ow, int oh,
                         const float* lut, void* out, int out_u8, void* stream) {
   if (!src || !xcoef || !xbounds || !xbounds_host || !ycoef || !ybounds || !ybounds_host || !out || (!out_u8 && !lut))
-    return refuse("resample: null pointer");
+    return os2d_refuse("resample: null pointer");
   if (misaligned(xcoef, 4) || misaligned(xbounds, 4) || misaligned(ycoef, 4) || misaligned(ybounds, 4) || misaligned(xbounds_host, 4) ||
       misaligned(ybounds_host, 4) || (!out_u8 && (misaligned(lut, 4) || misaligned(out, 16))))
-    return refuse("resample: pointer not aligned (tables 4 bytes, float output 16 bytes)");
+    return os2d_refuse("resample: pointer not aligned (tables 4 bytes, float output 16 bytes)");
   if (A < 1 || A > 65535 || img_w < 1 || img_h < 1 || w < 1 || h < 1 || ow < 1 || oh < 1 || kx < 1 || ky < 1)
-    return refuse("resample: bad shape (1 <= A <= 65535, sizes and tap counts >= 1)");
+    return os2d_refuse("resample: bad shape (1 <= A <= 65535, sizes and tap counts >= 1)");
   if (row_pitch < 3LL * img_w || (A > 1 && image_stride < row_pitch * img_h))
-    return refuse("resample: bad shape (row pitch below 3 * img_w or image stride below img_h * row pitch)");
-  if (x0 < 0 || y0 < 0 || x0 > img_w - w || y0 > img_h - h) return refuse("resample: window outside the image");
+    return os2d_refuse("resample: bad shape (row pitch below 3 * img_w or image stride below img_h * row pitch)");
+  if (x0 < 0 || y0 < 0 || x0 > img_w - w || y0 > img_h - h) return os2d_refuse("resample: window outside the image");
   const long long R = OS2D_IMAGE_MAX_RATIO;
-  if (w > R * ow || ow > R * w || h > R * oh || oh > R * h) return refuse("resample: size ratio beyond 16 on an axis");
+  if (w > R * ow || ow > R * w || h > R * oh || oh > R * h) return os2d_refuse("resample: size ratio beyond 16 on an axis");
   if (!bounds_ok(xbounds_host, ow, kx, w) || !bounds_ok(ybounds_host, oh, ky, h))
-    return refuse("resample: table bounds outside the window (0 <= first, 1 <= taps <= k, first + taps <= n)");
+    return os2d_refuse("resample: table bounds outside the window (0 <= first, 1 <= taps <= k, first + taps <= n)");
   // tile height: the largest whose staged rows fit in LDS (fewer tile rows for strong down-scaling)
   int th = IMG_TH_MAX, nrows = 0;
   for (; th >= 1; th >>= 1) {
     nrows = max_tile_rows(ybounds_host, oh, th);
     if (nrows <= IMG_MAX_ROWS) break;
   }
-  if (th < 1) return refuse("resample: the taps of one output row do not fit in LDS");
+  if (th < 1) return os2d_refuse("resample: the taps of one output row do not fit in LDS");
   Resample p;
   p.src = src;
   p.row_pitch = row_pitch;
@@ -211,12 +203,12 @@ int os2d_image_resample(const unsigned char* src, int A, int img_w, int img_h, l
   p.out = out;
   const dim3 grid((ow + IMG_TW - 1) / IMG_TW, (oh + th - 1) / th, A);
   const size_t lds = (size_t)nrows * 3 * IMG_TW + (out_u8 ? 0 : IMG_LUT_BYTES);
-  if (grid.y > 65535) return refuse("resample: bad shape (output too high)");
+  if (grid.y > 65535) return os2d_refuse("resample: bad shape (output too high)");
   if (out_u8)
-    hipLaunchKernelGGL(resample_kernel<true>, grid, dim3(IMG_THREADS), lds, S(stream), p);
+    hipLaunchKernelGGL(resample_kernel<true>, grid, dim3(IMG_THREADS), lds, os2d_stream(stream), p);
   else
-    hipLaunchKernelGGL(resample_kernel<false>, grid, dim3(IMG_THREADS), lds, S(stream), p);
-  return launched("resample_kernel", g_err, sizeof(g_err));
+    hipLaunchKernelGGL(resample_kernel<false>, grid, dim3(IMG_THREADS), lds, os2d_stream(stream), p);
+  return os2d_launched("resample_kernel");
 }
 
 }  // extern "C"

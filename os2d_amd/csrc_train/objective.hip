@@ -15,25 +15,15 @@
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
 
 #include "../../include/os2d_train.h"
-#include "train_common.h"
+#include "../csrc_shared/abi_common.h"
 
 namespace {
 
 constexpr int OBJ_THREADS = 256;
 constexpr int OBJ_WAVES = OBJ_THREADS / 64;
-
-void set_error(const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  os2d_train_store_error(buf);
-}
 
 // flags byte of one element
 constexpr unsigned char F_POS = 1;      // positive of the class loss (remapped targets when given)
@@ -627,31 +617,31 @@ int os2d_train_assign_targets(int mode, const float* gt_boxes, const int* gt_lab
                               int rec_field, float iou_high, float iou_low, float* loc_targets, long long* cls_targets,
                               float* ious_anchor, float* ious_anchor_corrected, void* stream) {
   if (mode != 0 && mode != 1) {
-    set_error("os2d_train_assign_targets: unknown mode %d (0 = encode, 1 = remap)", mode);
+    os2d_set_error("os2d_train_assign_targets: unknown mode %d (0 = encode, 1 = remap)", mode);
     return -1;
   }
   if (H < 1 || W < 1 || (long long)H * W > (1ll << 28) || !dims_ok(A, B, H * W)) {
-    set_error("os2d_train_assign_targets: bad shape A=%d B=%d H=%d W=%d", A, B, H, W);
+    os2d_set_error("os2d_train_assign_targets: bad shape A=%d B=%d H=%d W=%d", A, B, H, W);
     return -1;
   }
   if (stride < 1 || rec_field + 14 * stride < 1 || num_boxes < 0) {
-    set_error("os2d_train_assign_targets: bad stride=%d rec_field=%d num_boxes=%d", stride, rec_field, num_boxes);
+    os2d_set_error("os2d_train_assign_targets: bad stride=%d rec_field=%d num_boxes=%d", stride, rec_field, num_boxes);
     return -1;
   }
   if (!image_offsets || !cls_targets || (num_boxes > 0 && (!gt_boxes || !gt_labels || !gt_difficult))) {
-    set_error("os2d_train_assign_targets: null pointer");
+    os2d_set_error("os2d_train_assign_targets: null pointer");
     return -1;
   }
   if (mode == 0 ? !loc_targets : (!loc_scores || !ious_anchor || !ious_anchor_corrected)) {
-    set_error("os2d_train_assign_targets: null pointer for mode %d", mode);
+    os2d_set_error("os2d_train_assign_targets: null pointer for mode %d", mode);
     return -1;
   }
   const int HW = H * W;
   const dim3 grid((HW + OBJ_THREADS - 1) / OBJ_THREADS, A * B);
-  assign_targets_kernel<<<grid, OBJ_THREADS, 0, S(stream)>>>(mode, gt_boxes, gt_labels, gt_difficult, image_offsets, num_boxes, loc_scores,
+  assign_targets_kernel<<<grid, OBJ_THREADS, 0, os2d_stream(stream)>>>(mode, gt_boxes, gt_labels, gt_difficult, image_offsets, num_boxes, loc_scores,
                                                             B, H, W, (float)stride, (float)(rec_field + 14 * stride), iou_high,
                                                             iou_low, loc_targets, cls_targets, ious_anchor, ious_anchor_corrected);
-  return launched("os2d_train_assign_targets");
+  return os2d_launched("os2d_train_assign_targets");
 }
 
 size_t os2d_train_objective_workspace_floats(int A, int B, int HW) {
@@ -666,28 +656,28 @@ int os2d_train_objective_forward(int class_loss, int patch_mining_mode, const fl
                                  double rll_neg_weight_ratio, float* losses, float* cls_loss, float* loc_loss, unsigned char* flags,
                                  float* coef, float* workspace, size_t workspace_floats, void* stream) {
   if (class_loss != 0 && class_loss != 1) {
-    set_error("os2d_train_objective_forward: unknown class loss %d (0 = ContrastiveLoss, 1 = RLL)", class_loss);
+    os2d_set_error("os2d_train_objective_forward: unknown class loss %d (0 = ContrastiveLoss, 1 = RLL)", class_loss);
     return -1;
   }
   if (!dims_ok(A, B, HW)) {
-    set_error("os2d_train_objective_forward: bad shape A=%d B=%d HW=%d", A, B, HW);
+    os2d_set_error("os2d_train_objective_forward: bad shape A=%d B=%d HW=%d", A, B, HW);
     return -1;
   }
   if (!loc_preds || !loc_targets || !cls_preds || !cls_targets || !losses || !cls_loss || !flags || !coef || !workspace) {
-    set_error("os2d_train_objective_forward: null pointer");
+    os2d_set_error("os2d_train_objective_forward: null pointer");
     return -1;
   }
   if (class_loss == 1 && !(rll_neg_weight_ratio > 0.0)) {
-    set_error("os2d_train_objective_forward: rll_neg_weight_ratio must be positive");
+    os2d_set_error("os2d_train_objective_forward: rll_neg_weight_ratio must be positive");
     return -1;
   }
   if (!(neg_to_pos_ratio >= 0.f)) {
-    set_error("os2d_train_objective_forward: neg_to_pos_ratio must not be negative");
+    os2d_set_error("os2d_train_objective_forward: neg_to_pos_ratio must not be negative");
     return -1;
   }
   const Layout l = layout(A, B, HW);
   if (workspace_floats < l.total) {
-    set_error("os2d_train_objective_forward: workspace of %zu floats, %zu needed", workspace_floats, l.total);
+    os2d_set_error("os2d_train_objective_forward: workspace of %zu floats, %zu needed", workspace_floats, l.total);
     return -2;
   }
   ObjParams P;
@@ -708,10 +698,10 @@ int os2d_train_objective_forward(int class_loss, int patch_mining_mode, const fl
   P.part = (unsigned)l.part;
   P.wpart = (unsigned)l.wpart;
   P.tie = (unsigned)l.tie;
-  hipStream_t s = S(stream);
+  hipStream_t s = os2d_stream(stream);
   unsigned* ws = reinterpret_cast<unsigned*>(workspace);
   const dim3 grid(l.chunks, A * B);
-  if (hipMemsetAsync(ws, 0, l.part * sizeof(unsigned), s) != hipSuccess) return launched("os2d_train_objective_forward: memset");
+  if (hipMemsetAsync(ws, 0, l.part * sizeof(unsigned), s) != hipSuccess) return os2d_launched("os2d_train_objective_forward: memset");
   objective_elements_kernel<<<grid, OBJ_THREADS, 0, s>>>(P, loc_preds, loc_targets, cls_preds, cls_targets, cls_targets_remapped,
                                                         cls_preds_for_neg, cls_loss, loc_loss, flags, coef, ws);
   if (!P.patch && P.kind == 0) {
@@ -725,7 +715,7 @@ int os2d_train_objective_forward(int class_loss, int patch_mining_mode, const fl
     rll_elements_kernel<<<grid, OBJ_THREADS, 0, s>>>(P, cls_loss, flags, coef, ws);
   }
   objective_finalise_kernel<<<1, OBJ_THREADS, 0, s>>>(P, losses, ws);
-  return launched("os2d_train_objective_forward");
+  return os2d_launched("os2d_train_objective_forward");
 }
 
 int os2d_train_objective_backward(const float* grad_loss, const float* loc_preds, const float* loc_targets, const unsigned char* flags,
@@ -733,22 +723,22 @@ int os2d_train_objective_backward(const float* grad_loss, const float* loc_preds
                                   float localization_weight, float* dloc_preds, float* dcls_preds, float* dcls_preds_for_neg,
                                   void* stream) {
   if (!dims_ok(A, B, HW)) {
-    set_error("os2d_train_objective_backward: bad shape A=%d B=%d HW=%d", A, B, HW);
+    os2d_set_error("os2d_train_objective_backward: bad shape A=%d B=%d HW=%d", A, B, HW);
     return -1;
   }
   if (!grad_loss || !flags || !coef || !workspace || (dloc_preds && (!loc_preds || !loc_targets))) {
-    set_error("os2d_train_objective_backward: null pointer");
+    os2d_set_error("os2d_train_objective_backward: null pointer");
     return -1;
   }
   if (!dloc_preds && !dcls_preds && !dcls_preds_for_neg) {
-    set_error("os2d_train_objective_backward: null pointer for every gradient");
+    os2d_set_error("os2d_train_objective_backward: null pointer for every gradient");
     return -1;
   }
   const dim3 grid((HW + OBJ_THREADS - 1) / OBJ_THREADS, A * B);
-  objective_backward_kernel<<<grid, OBJ_THREADS, 0, S(stream)>>>(grad_loss, loc_preds, loc_targets, flags, coef, workspace, HW,
+  objective_backward_kernel<<<grid, OBJ_THREADS, 0, os2d_stream(stream)>>>(grad_loss, loc_preds, loc_targets, flags, coef, workspace, HW,
                                                                 class_loss_neg_weight, localization_weight, dloc_preds, dcls_preds,
                                                                 dcls_preds_for_neg);
-  return launched("os2d_train_objective_backward");
+  return os2d_launched("os2d_train_objective_backward");
 }
 
 }  // extern "C"

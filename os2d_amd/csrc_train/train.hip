@@ -8,24 +8,13 @@
 //   * the two correlation GEMMs (d F^ = Q^T d corr per image, d Q^ = d corr F^T per class).
 // The rest is per-location work: resample / pool / box decode backward, BatchNorm + ReLU masks, the two L2 normalisations
 // and the bilinear class-map resize.
-#include <stdarg.h>
 #include <stdio.h>
 
 #include "../../include/os2d_train.h"
 #include "../csrc/os2d_common.h"
 #include "../csrc/sample_decode.h"
-#include "train_common.h"
 
 namespace {
-
-thread_local char g_err[512] = {0};
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
 
 struct Layer {
   int cout, cin, ks;
@@ -113,7 +102,7 @@ template <bool B_KFAST, class LA, class LB, class ST>
 int gemm(LA la, LB lb, ST st, int M, int N, int K, int Z, int ksplit, hipStream_t stream, const char* what) {
   const dim3 grid((N + GT - 1) / GT, (M + GT - 1) / GT, Z);
   hipLaunchKernelGGL((gemm16_kernel<LA, LB, ST, B_KFAST>), grid, dim3(256), 0, stream, la, lb, st, M, N, K, ksplit);
-  return launched(what);
+  return os2d_launched(what);
 }
 
 // tap offset of the zero-bordered plane layout: flat distance of tap t = (dy, dx) of a KS x KS kernel
@@ -592,80 +581,78 @@ inline unsigned blocks(size_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
-void os2d_train_store_error(const char* text) { set_error("%s", text); }
-
 // ================================================================================================ C ABI
 extern "C" {
 
 int os2d_train_abi_version(void) { return OS2D_TRAIN_ABI_VERSION; }
-const char* os2d_train_last_error(void) { return g_err; }
+const char* os2d_train_last_error(void) { return os2d_error_text; }
 
 int os2d_train_decode_backward(const float* corr, const float* params, const float* dcls, const float* dcls_det, const float* dloc,
                                int NB, int H, int W, int P, int inverse, int stride, int rec_field, float* dcorr, float* dparams,
                                void* stream) {
-  g_err[0] = 0;
+  os2d_clear_error();
   if (!corr || !params || !dcorr || !dparams) {
-    set_error("os2d_train_decode_backward: null pointer");
+    os2d_set_error("os2d_train_decode_backward: null pointer");
     return -1;
   }
   if (NB < 1 || H < 1 || W < 1 || (P != 6 && P != 4) || stride < 1 || rec_field < 1) {
-    set_error("os2d_train_decode_backward: bad shape NB=%d H=%d W=%d P=%d stride=%d rec_field=%d", NB, H, W, P, stride, rec_field);
+    os2d_set_error("os2d_train_decode_backward: bad shape NB=%d H=%d W=%d P=%d stride=%d rec_field=%d", NB, H, W, P, stride, rec_field);
     return -1;
   }
   if (NB > 65535) {
-    set_error("os2d_train_decode_backward: NB=%d > 65535", NB);
+    os2d_set_error("os2d_train_decode_backward: NB=%d > 65535", NB);
     return -3;
   }
   const float half_box = 0.5f * (float)(stride * (OS2D_T - 1) + rec_field);
-  hipLaunchKernelGGL(decode_backward_kernel, dim3(blocks((size_t)H * W), NB), dim3(256), 0, S(stream), corr, params, dcls, dcls_det,
+  hipLaunchKernelGGL(decode_backward_kernel, dim3(blocks((size_t)H * W), NB), dim3(256), 0, os2d_stream(stream), corr, params, dcls, dcls_det,
                      dloc, H, W, P, inverse ? 1 : 0, (float)stride, half_box, dcorr, dparams);
-  return launched("decode_backward_kernel");
+  return os2d_launched("decode_backward_kernel");
 }
 
 int os2d_train_params_backward(const float* dparams, int NB, int P, int H, int W, float* dy, float* dbias, void* stream) {
-  g_err[0] = 0;
+  os2d_clear_error();
   if (!dparams || !dy) {
-    set_error("os2d_train_params_backward: null pointer");
+    os2d_set_error("os2d_train_params_backward: null pointer");
     return -1;
   }
   if ((P != 6 && P != 4) || !shape_ok(NB, H, W) || (size_t)NB * P > 65535) {
-    set_error("os2d_train_params_backward: bad shape NB=%d P=%d H=%d W=%d", NB, P, H, W);
+    os2d_set_error("os2d_train_params_backward: bad shape NB=%d P=%d H=%d W=%d", NB, P, H, W);
     return -1;
   }
   const int PL = os2d_plane(H, W);
-  hipLaunchKernelGGL(compact_to_plane_kernel, dim3(blocks(PL), NB * P), dim3(256), 0, S(stream), dparams, P, H, W, PL, dy);
-  int rc = launched("compact_to_plane_kernel");
+  hipLaunchKernelGGL(compact_to_plane_kernel, dim3(blocks(PL), NB * P), dim3(256), 0, os2d_stream(stream), dparams, P, H, W, PL, dy);
+  int rc = os2d_launched("compact_to_plane_kernel");
   if (rc || !dbias) return rc;
-  hipLaunchKernelGGL(channel_sum_kernel, dim3(P), dim3(256), 0, S(stream), dparams, NB, P, H * W, dbias);
-  return launched("channel_sum_kernel");
+  hipLaunchKernelGGL(channel_sum_kernel, dim3(P), dim3(256), 0, os2d_stream(stream), dparams, NB, P, H * W, dbias);
+  return os2d_launched("channel_sum_kernel");
 }
 
 int os2d_train_bn_relu_backward(int layer, const float* dh, const float* h, const float* gamma, const float* beta,
                                 const float* running_var, float eps, int NB, int H, int W, float* dy, float* dgamma, float* dbeta,
                                 float* dbias, void* stream) {
-  g_err[0] = 0;
+  os2d_clear_error();
   Layer L;
   if (layer != 1 && layer != 2) {
-    set_error("os2d_train_bn_relu_backward: layer %d has no BatchNorm (1 or 2)", layer);
+    os2d_set_error("os2d_train_bn_relu_backward: layer %d has no BatchNorm (1 or 2)", layer);
     return -1;
   }
   layer_shape(layer, 6, &L);
   if (!dh || !h || !gamma || !beta || !running_var || !dy) {
-    set_error("os2d_train_bn_relu_backward: null pointer");
+    os2d_set_error("os2d_train_bn_relu_backward: null pointer");
     return -1;
   }
   if (!shape_ok(NB, H, W) || (size_t)NB * L.cout > 65535 || !(eps >= 0.f)) {
-    set_error("os2d_train_bn_relu_backward: bad shape NB=%d H=%d W=%d eps=%g", NB, H, W, (double)eps);
+    os2d_set_error("os2d_train_bn_relu_backward: bad shape NB=%d H=%d W=%d eps=%g", NB, H, W, (double)eps);
     return -1;
   }
   const int PL = os2d_plane(H, W);
-  hipLaunchKernelGGL(bn_relu_mask_kernel, dim3(blocks(PL), NB * L.cout), dim3(256), 0, S(stream), dh, h, gamma, running_var, eps,
+  hipLaunchKernelGGL(bn_relu_mask_kernel, dim3(blocks(PL), NB * L.cout), dim3(256), 0, os2d_stream(stream), dh, h, gamma, running_var, eps,
                      L.cout, H, W, PL, dy);
-  int rc = launched("bn_relu_mask_kernel");
+  int rc = os2d_launched("bn_relu_mask_kernel");
   if (rc || (!dgamma && !dbeta && !dbias)) return rc;
-  hipLaunchKernelGGL(bn_relu_sums_kernel, dim3(L.cout), dim3(256), 0, S(stream), dh, h, gamma, beta, running_var, eps, NB, L.cout, H,
+  hipLaunchKernelGGL(bn_relu_sums_kernel, dim3(L.cout), dim3(256), 0, os2d_stream(stream), dh, h, gamma, beta, running_var, eps, NB, L.cout, H,
                      W, PL, dgamma, dbeta, dbias);
-  return launched("bn_relu_sums_kernel");
+  return os2d_launched("bn_relu_sums_kernel");
 }
 
 size_t os2d_train_conv_data_workspace_floats(int layer, int P) {
@@ -676,52 +663,52 @@ size_t os2d_train_conv_data_workspace_floats(int layer, int P) {
 
 int os2d_train_conv_backward_data(int layer, int P, const float* w, const float* dy, int NB, int H, int W, float* dx,
                                   float* workspace, size_t workspace_floats, void* stream) {
-  g_err[0] = 0;
+  os2d_clear_error();
   Layer L;
   if (!layer_shape(layer, P, &L)) {
-    set_error("os2d_train_conv_backward_data: bad layer %d / P %d", layer, P);
+    os2d_set_error("os2d_train_conv_backward_data: bad layer %d / P %d", layer, P);
     return -1;
   }
   if (!w || !dy || !dx || !workspace) {
-    set_error("os2d_train_conv_backward_data: null pointer");
+    os2d_set_error("os2d_train_conv_backward_data: null pointer");
     return -1;
   }
   if (!shape_ok(NB, H, W) || NB > 65535) {
-    set_error("os2d_train_conv_backward_data: bad shape NB=%d H=%d W=%d (W <= %d)", NB, H, W, OS2D_MAX_W_DIRECT7);
+    os2d_set_error("os2d_train_conv_backward_data: bad shape NB=%d H=%d W=%d (W <= %d)", NB, H, W, OS2D_MAX_W_DIRECT7);
     return -1;
   }
   const int T2 = L.ks * L.ks;
   const size_t wf = (size_t)L.cout * L.cin * T2;
   if (workspace_floats < wf) {
-    set_error("os2d_train_conv_backward_data: workspace %zu floats < %zu", workspace_floats, wf);
+    os2d_set_error("os2d_train_conv_backward_data: workspace %zu floats < %zu", workspace_floats, wf);
     return -2;
   }
-  hipLaunchKernelGGL(flip_weights_kernel, dim3(blocks(wf)), dim3(256), 0, S(stream), w, L.cout, L.cin, T2, workspace);
-  int rc = launched("flip_weights_kernel");
+  hipLaunchKernelGGL(flip_weights_kernel, dim3(blocks(wf)), dim3(256), 0, os2d_stream(stream), w, L.cout, L.cin, T2, workspace);
+  int rc = os2d_launched("flip_weights_kernel");
   if (rc) return rc;
   const int PL = os2d_plane(H, W);
   const Taps tp{L.ks, L.ks / 2, os2d_ws(W), T2};
   const int K = L.cout * T2;
   return gemm<false>(LdRows{workspace, K}, LdShifted{dy, (size_t)L.cout * PL, PL, tp}, StPlane{dx, (size_t)L.cin * PL, PL, H, W}, L.cin,
-                     PL, K, NB, 0, S(stream), "conv data gradient");
+                     PL, K, NB, 0, os2d_stream(stream), "conv data gradient");
 }
 
 size_t os2d_train_conv_weight_slice_floats(int layer, int P) { return os2d_train_conv_data_workspace_floats(layer, P); }
 
 int os2d_train_conv_backward_weight(int layer, int P, const float* x, const float* dy, int NB, int H, int W, float* dw,
                                     float* workspace, size_t workspace_floats, void* stream) {
-  g_err[0] = 0;
+  os2d_clear_error();
   Layer L;
   if (!layer_shape(layer, P, &L)) {
-    set_error("os2d_train_conv_backward_weight: bad layer %d / P %d", layer, P);
+    os2d_set_error("os2d_train_conv_backward_weight: bad layer %d / P %d", layer, P);
     return -1;
   }
   if (!x || !dy || !dw || !workspace) {
-    set_error("os2d_train_conv_backward_weight: null pointer");
+    os2d_set_error("os2d_train_conv_backward_weight: null pointer");
     return -1;
   }
   if (!shape_ok(NB, H, W)) {
-    set_error("os2d_train_conv_backward_weight: bad shape NB=%d H=%d W=%d (W <= %d)", NB, H, W, OS2D_MAX_W_DIRECT7);
+    os2d_set_error("os2d_train_conv_backward_weight: bad shape NB=%d H=%d W=%d (W <= %d)", NB, H, W, OS2D_MAX_W_DIRECT7);
     return -1;
   }
   const int T2 = L.ks * L.ks;
@@ -729,12 +716,12 @@ int os2d_train_conv_backward_weight(int layer, int P, const float* x, const floa
   const int PL = os2d_plane(H, W);
   const long long K = (long long)NB * PL;
   if (K > 0x7fffffffLL) {
-    set_error("os2d_train_conv_backward_weight: NB * PLANE = %lld positions exceed the 32-bit index", K);
+    os2d_set_error("os2d_train_conv_backward_weight: NB * PLANE = %lld positions exceed the 32-bit index", K);
     return -3;
   }
   long long splits = (long long)(workspace_floats / slice);
   if (splits < 1) {
-    set_error("os2d_train_conv_backward_weight: workspace %zu floats < one slice of %zu", workspace_floats, slice);
+    os2d_set_error("os2d_train_conv_backward_weight: workspace %zu floats < one slice of %zu", workspace_floats, slice);
     return -2;
   }
   if (splits > 64) splits = 64;
@@ -744,25 +731,25 @@ int os2d_train_conv_backward_weight(int layer, int P, const float* x, const floa
   const Taps tp{L.ks, L.ks / 2, os2d_ws(W), T2};
   const int N = L.cin * T2;
   int rc = gemm<true>(LdPairRows{dy, (size_t)L.cout * PL, PL}, LdPairShifted{x, (size_t)input_planes(layer) * PL, PL, tp},
-                      StSlice{workspace, L.cout, N}, L.cout, N, (int)K, (int)splits, ksplit, S(stream), "conv weight gradient");
+                      StSlice{workspace, L.cout, N}, L.cout, N, (int)K, (int)splits, ksplit, os2d_stream(stream), "conv weight gradient");
   if (rc) return rc;
-  hipLaunchKernelGGL(split_sum_kernel, dim3(blocks(slice)), dim3(256), 0, S(stream), workspace, (int)splits, slice, dw);
-  return launched("split_sum_kernel");
+  hipLaunchKernelGGL(split_sum_kernel, dim3(blocks(slice)), dim3(256), 0, os2d_stream(stream), workspace, (int)splits, slice, dw);
+  return os2d_launched("split_sum_kernel");
 }
 
 int os2d_train_norm225_backward(const float* corr, const float* dxn, int NB, int H, int W, float* dcorr, void* stream) {
-  g_err[0] = 0;
+  os2d_clear_error();
   if (!corr || !dxn || !dcorr) {
-    set_error("os2d_train_norm225_backward: null pointer");
+    os2d_set_error("os2d_train_norm225_backward: null pointer");
     return -1;
   }
   if (!shape_ok(NB, H, W) || NB > 65535) {
-    set_error("os2d_train_norm225_backward: bad shape NB=%d H=%d W=%d", NB, H, W);
+    os2d_set_error("os2d_train_norm225_backward: bad shape NB=%d H=%d W=%d", NB, H, W);
     return -1;
   }
-  hipLaunchKernelGGL(norm225_backward_kernel, dim3(blocks((size_t)H * W), NB), dim3(256), 0, S(stream), corr, dxn, H, W,
+  hipLaunchKernelGGL(norm225_backward_kernel, dim3(blocks((size_t)H * W), NB), dim3(256), 0, os2d_stream(stream), corr, dxn, H, W,
                      os2d_plane(H, W), dcorr);
-  return launched("norm225_backward_kernel");
+  return os2d_launched("norm225_backward_kernel");
 }
 
 size_t os2d_train_corr_workspace_floats(int A, int C, int H, int W) {
@@ -773,66 +760,66 @@ size_t os2d_train_corr_workspace_floats(int A, int C, int H, int W) {
 
 int os2d_train_corr_backward(const float* fm, const float* qp, const float* dcorr, int A, int B, int C, int H, int W, float* dfm,
                              float* dq, float* workspace, size_t workspace_floats, void* stream) {
-  g_err[0] = 0;
+  os2d_clear_error();
   if (!fm || !qp || !dcorr || !workspace) {
-    set_error("os2d_train_corr_backward: null pointer");
+    os2d_set_error("os2d_train_corr_backward: null pointer");
     return -1;
   }
   if (A < 1 || B < 1 || C < 1 || H < 1 || W < 1 || A > 65535 || B > 65535) {
-    set_error("os2d_train_corr_backward: bad shape A=%d B=%d C=%d H=%d W=%d", A, B, C, H, W);
+    os2d_set_error("os2d_train_corr_backward: bad shape A=%d B=%d C=%d H=%d W=%d", A, B, C, H, W);
     return -1;
   }
   const long long HW = (long long)H * W;
   if ((long long)B * OS2D_K > 0x7fffffffLL || (long long)A * HW > 0x7fffffffLL) {
-    set_error("os2d_train_corr_backward: reduction length exceeds the 32-bit index");
+    os2d_set_error("os2d_train_corr_backward: reduction length exceeds the 32-bit index");
     return -3;
   }
   const size_t need = os2d_train_corr_workspace_floats(A, C, H, W);
   if (workspace_floats < need) {
-    set_error("os2d_train_corr_backward: workspace %zu floats < %zu", workspace_floats, need);
+    os2d_set_error("os2d_train_corr_backward: workspace %zu floats < %zu", workspace_floats, need);
     return -2;
   }
   if (!dfm && !dq) return 0;
   float* rinv = workspace;
   float* dfh = rinv + 2 * (size_t)A * HW;     // the second A * HW floats are not used
-  hipLaunchKernelGGL(image_norm_kernel, dim3(blocks(HW), A), dim3(256), 0, S(stream), fm, C, (int)HW, rinv);
-  int rc = launched("image_norm_kernel");
+  hipLaunchKernelGGL(image_norm_kernel, dim3(blocks(HW), A), dim3(256), 0, os2d_stream(stream), fm, C, (int)HW, rinv);
+  int rc = os2d_launched("image_norm_kernel");
   if (rc) return rc;
   if (dfm) {
-    rc = gemm<false>(LdClassT{qp, C}, LdCorrRows{dcorr, B, (int)HW}, StDense{dfh, C, (int)HW}, C, (int)HW, B * OS2D_K, A, 0, S(stream),
+    rc = gemm<false>(LdClassT{qp, C}, LdCorrRows{dcorr, B, (int)HW}, StDense{dfh, C, (int)HW}, C, (int)HW, B * OS2D_K, A, 0, os2d_stream(stream),
                      "correlation backward (image)");
     if (rc) return rc;
-    hipLaunchKernelGGL(image_norm_backward_kernel, dim3(blocks(HW), A), dim3(256), 0, S(stream), fm, dfh, C, (int)HW, dfm);
-    rc = launched("image_norm_backward_kernel");
+    hipLaunchKernelGGL(image_norm_backward_kernel, dim3(blocks(HW), A), dim3(256), 0, os2d_stream(stream), fm, dfh, C, (int)HW, dfm);
+    rc = os2d_launched("image_norm_backward_kernel");
     if (rc) return rc;
   }
   if (dq)
     rc = gemm<true>(LdImageNorm{fm, rinv, C, (int)HW}, LdCorrCols{dcorr, B, (int)HW}, StDense{dq, C, OS2D_K}, C, OS2D_K, A * (int)HW, B,
-                    0, S(stream), "correlation backward (class)");
+                    0, os2d_stream(stream), "correlation backward (class)");
   return rc;
 }
 
 int os2d_train_class_backward(const float* q15, const float* dq, int B, int C, float* const* dsrcs, const int* sizes,
                               float* workspace, size_t workspace_floats, void* stream) {
-  g_err[0] = 0;
+  os2d_clear_error();
   if (!q15 || !dq || !dsrcs || !sizes || !workspace) {
-    set_error("os2d_train_class_backward: null pointer");
+    os2d_set_error("os2d_train_class_backward: null pointer");
     return -1;
   }
   if (B < 1 || C < 1 || B > 65535) {
-    set_error("os2d_train_class_backward: bad shape B=%d C=%d", B, C);
+    os2d_set_error("os2d_train_class_backward: bad shape B=%d C=%d", B, C);
     return -1;
   }
   const size_t need = (size_t)B * C * OS2D_K;
   if (workspace_floats < need) {
-    set_error("os2d_train_class_backward: workspace %zu floats < %zu", workspace_floats, need);
+    os2d_set_error("os2d_train_class_backward: workspace %zu floats < %zu", workspace_floats, need);
     return -2;
   }
-  hipLaunchKernelGGL(class_norm_backward_kernel, dim3(1, B), dim3(256), 0, S(stream), q15, dq, C, workspace);
-  int rc = launched("class_norm_backward_kernel");
+  hipLaunchKernelGGL(class_norm_backward_kernel, dim3(1, B), dim3(256), 0, os2d_stream(stream), q15, dq, C, workspace);
+  int rc = os2d_launched("class_norm_backward_kernel");
   if (rc) return rc;
-  hipLaunchKernelGGL(class_resize_backward_kernel, dim3(blocks(C), B), dim3(256), 0, S(stream), workspace, C, dsrcs, sizes);
-  return launched("class_resize_backward_kernel");
+  hipLaunchKernelGGL(class_resize_backward_kernel, dim3(blocks(C), B), dim3(256), 0, os2d_stream(stream), workspace, C, dsrcs, sizes);
+  return os2d_launched("class_resize_backward_kernel");
 }
 
 }  // extern "C"

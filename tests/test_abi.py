@@ -1,19 +1,8 @@
-"""CPU: the C-ABI library builds, loads and exports every symbol include/os2d_hip.h declares (no compute calls)."""
+"""CPU: the host-side helpers of libos2d_hip.so (sizes, argument checks, transform plans; no compute calls) and its packed-FP32
+setting.  What the four libraries have in common - header, binding, exports, build stamp - is in test_native_libs.py."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
-
-REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-HEADER = os.path.join(REPO, "include", "os2d_hip.h")
-
-
-def declared_functions():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(os2d_[a-z0-9_]+)\s*\(", text)))
 
 
 @pytest.fixture(scope="module")
@@ -22,16 +11,6 @@ def lib_path():
     return build.build(verbose=False)
 
 
-def test_header_and_binding_agree():
-    from os2d_amd import _lib
-    assert declared_functions() == sorted(_lib.SIGNATURES), "include/os2d_hip.h and os2d_amd/_lib.py list different entry points"
-
-
-def test_library_exports_every_declared_symbol(lib_path):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", lib_path]).decode()
-    exported = set(re.findall(r" T (os2d_[a-z0-9_]+)", out))
-    missing = [f for f in declared_functions() if f not in exported]
-    assert not missing, "not exported: {}".format(missing)
 
 
 def test_library_loads_and_reports_abi(lib_path):
@@ -67,13 +46,6 @@ def test_library_loads_and_reports_abi(lib_path):
             assert lib.os2d_head_workspace_bytes_ex(1, 1, 64, h, 80, 6, prec, ctypes.byref(n)) == 0, (prec, h, lib.os2d_last_error())
 
 
-def test_missing_library_fails_loudly(monkeypatch, tmp_path):
-    from os2d_amd import _lib
-    monkeypatch.setattr(_lib, "_LIB", None)
-    monkeypatch.setenv("OS2D_HIP_LIB", str(tmp_path / "nope.so"))
-    with pytest.raises(_lib.Os2dLibraryError, match="no CPU or PyTorch fallback"):
-        _lib.load()
-
 
 def test_packed_fp32_setting_is_per_translation_unit():
     """docs/DESIGN_HISTORY_r1-r3.md section 8: v_pk_*_f32 results were wrong in 16-lane groups next to MFMA-heavy kernels of other streams.
@@ -88,35 +60,6 @@ def test_packed_fp32_setting_is_per_translation_unit():
     assert "-packed-fp32-ops" not in build.flags_for("nms.hip", packed="fft")
 
 
-def test_compiler_flags_are_part_of_the_build_stamp(monkeypatch):
-    """Object files carry no record of their flags: a flag change must invalidate the stamp (and with it every object) -
-    the first -packed-fp32-ops build left the untouched sources compiled the old way (docs/DESIGN_HISTORY_r1-r3.md section 8)."""
-    from os2d_amd import build
-    h0 = build.source_hash()
-    monkeypatch.setattr(build, "FLAGS", build.FLAGS + ["-DOS2D_SOME_EXPERIMENT"])
-    h1 = build.source_hash()
-    assert h1 != h0
-    monkeypatch.setattr(build, "NO_PACKED_FP32", set(build.NO_PACKED_FP32) - {"nms.hip"})      # a per-unit flag counts too
-    assert build.source_hash() != h1
-
-
-def test_every_included_header_is_part_of_the_build_stamp(tmp_path, monkeypatch):
-    """fft_regs.h (all the register DFTs) was in neither the hash nor the object dependencies, so editing it left a
-    stale library in use.  Headers are globbed now; every quoted #include of every source must resolve to one of them, and a
-    header that appears later changes the hash."""
-    import os
-    from os2d_amd import build
-    names = {os.path.basename(h) for h in build.headers()}
-    assert "fft_regs.h" in names and "os2d_common.h" in names and "os2d_hip.h" in names
-    for path in [os.path.join(build.CSRC, s) for s in build.SOURCES] + build.headers():
-        for inc in build.local_includes(path):
-            assert os.path.basename(inc) in names, (path, inc)
-    h0 = build.source_hash()
-    extra = tmp_path / "new_header.h"
-    extra.write_text("// new\n")
-    real = build.headers
-    monkeypatch.setattr(build, "headers", lambda: real() + [str(extra)])
-    assert build.source_hash() != h0
 
 
 def test_fft_plan_host_logic():

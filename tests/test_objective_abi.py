@@ -102,4 +102,5 @@ def test_no_float_atomic_add_in_the_objective_source():
         assert "1u" in args or "hist[tid]" in args or re.search(r"&ws\[W_CNT \+ \d\], n", args), args
     assert not re.search(r"atomicAdd\s*\(\s*(reinterpret_cast<float|\(float)", code)
     assert "unsafeAtomicAdd" not in code and "atomicAdd_system" not in code
-    assert "-ffp-contract=off" in open(os.path.join(REPO, "os2d_amd", "build.py")).read()
+    from os2d_amd import build
+    assert "-ffp-contract=off" in build.unit_flags(build.TRAIN, "objective.hip")
