@@ -148,9 +148,22 @@ int os2d_head_forward_ex(const float* fm, const float* qp, const void* w1, const
                          void* workspace, size_t workspace_bytes, void* stream, int precision, const void* qs,
                          void** stage_events, int* chunk_classes, int* status, const float* wspec, const float* twQ,
                          const float* twP);
+/* os2d_head_forward_ex + wspec2: under OS2D_PRECISION_FFTX3 a non-NULL wspec2 - the split weight spectra of the 5x5 layer
+ * 128 -> 64 for the same transform size (os2d_spectral_weights_build_dft with C = 128, Cout = 64 on the filters zero-embedded in
+ * 7x7, input channel c scaled by 2^(15 - out_exp1[c])) - runs that layer in the frequency domain as well: the layer-1 inverse
+ * writes fp32 planes scaled to <= 1 (os2d_dft_inverse_planes), then os2d_dft_forward (unit norms), the per-bin GEMM and
+ * os2d_dft_inverse with the layer-2 bias and scales.  NULL, any other precision or $OS2D_CONV2_FREQ=0 (read once): exactly
+ * os2d_head_forward_ex.                                                                                                    */
+int os2d_head_forward_ex2(const float* fm, const float* qp, const void* w1, const float* b1, const void* w2,
+                          const float* b2, const void* w3, const float* b3, int A, int B, int C, int H, int W, int P,
+                          int inverse, int stride, int rec_field, float* loc, float* cls, float* corners,
+                          void* workspace, size_t workspace_bytes, void* stream, int precision, const void* qs,
+                          void** stage_events, int* chunk_classes, int* status, const float* wspec, const float* twQ,
+                          const float* twP, const void* wspec2);
 /* debugging aid, DIAGNOSTIC builds only (-DOS2D_DIAG_DUMP; the product library ignores the call and sets os2d_last_error):
  * from now on os2d_head_forward_ex on `stream` copies an intermediate buffer of its first class chunk to dst (slot 0 corr,
- * 1 inverse norms, 2 input spectra, 3 output spectra, 4 h1, 5 h2, 6 params; at most `bytes`) on that stream; dst == NULL
+ * 1 inverse norms, 2 input spectra, 3 output spectra, 4 h1 (os2d_head_forward_ex2 with wspec2: the fp32 planes), 5 h2, 6 params;
+ * at most `bytes`) on that stream; dst == NULL
  * unregisters the slot (do that before freeing the destination).                                                         */
 void os2d_debug_set_dump(void* stream, int slot, void* dst, size_t bytes);
 int os2d_prof_event_create(void** ev);
@@ -344,7 +357,8 @@ int os2d_spectral_gemm_f16(const void* w16, const float* X, float* Y, int NB, in
  *                            -2 pi m / n as for os2d_spectral_weights_build), os2d_dft_matrices_bytes(P, Q) bytes; they depend
  *                            on (P, Q) only
  *   os2d_dft_forward         relu(corr [NB,C,H*W]) * inv_norm [NB,H*W] -> X [nbins/4, NB*T, Cpad, 4] complex64 (quads of bins x
- *                            channels: 128-byte runs per work-group iteration, 256-byte runs per k-step of the GEMM)
+ *                            channels: 128-byte runs per work-group iteration, 256-byte runs per k-step of the GEMM);
+ *                            inv_norm == NULL: unit norms (the input holds samples in [0, 1] already)
  *   os2d_spectral_weights_build_dft   the split weight spectra of os2d_spectral_gemm_f16 in that bin order
  *   os2d_spectral_gemm_f16_quads      the per-bin GEMM reading X in that layout (xscale: os2d_dft_xscale(H, W)); Y
  *                            [nbins/4, NB*T, Cout, 4]
@@ -356,7 +370,9 @@ int os2d_spectral_gemm_f16(const void* w16, const float* X, float* Y, int NB, in
  *                            layout is exactly the one written above.
  *   os2d_dft_inverse         Y -> the layer's activations (bias, ReLU, channel scale, fp16 hi | lo) in the split-half blocked
  *                            buffer, as os2d_fft_inverse; the kernel also writes the ZERO BORDERS of the planes it fills (the
- *                            buffer may hold anything before the call)                                                     */
+ *                            buffer may hold anything before the call); Cout = 128 (packed_b of layer 1) or 64 (layer 2)
+ *   os2d_dft_inverse_planes  the same values times 2^-15 - every sample <= 1 under the range plan - as fp32 planes
+ *                            [NB, Cout, H*W]: the input form of os2d_dft_forward                                             */
 int os2d_dft_sizes(int H, int W, int* P, int* Q, int* nbins, int* tiles);
 int os2d_dft_channel_stride(int C);
 size_t os2d_dft_matrices_bytes(int P, int Q);
@@ -365,6 +381,8 @@ int os2d_dft_forward(const float* corr, const float* inv_norm, float* X, const v
                      void* stream);
 int os2d_dft_inverse(const float* Y, const float* packed_b, void* out, const void* matrices, int NB, int Cout, int H, int W,
                      int* status, void* stream);
+int os2d_dft_inverse_planes(const float* Y, const float* packed_b, float* out, const void* matrices, int NB, int Cout, int H, int W,
+                            int* status, void* stream);
 int os2d_spectral_weights_build_dft(const double* wfold, const double* twP64, const double* twQ64, int C, int Cout, int P, int Q,
                                     int nbins, void* out, void* workspace, void* stream);
 int os2d_spectral_gemm_f16_quads(const void* w16, const float* X, float* Y, int NB, int C, int Cout, int nbins, float xscale,

@@ -60,6 +60,9 @@ SIGNATURES = {
     "os2d_class_split_bytes": (_sz, [_i, _i]),
     "os2d_head_forward_ex": (_i, [_vp] * 8 + [_i] * 9 + [_vp, _vp, _vp, _vp, _sz, _vp, _i, _vp,
                                   ctypes.POINTER(_vp), ctypes.POINTER(_i), _vp, _vp, _vp, _vp]),
+    "os2d_head_forward_ex2": (_i, [_vp] * 8 + [_i] * 9 + [_vp, _vp, _vp, _vp, _sz, _vp, _i, _vp,
+                                   ctypes.POINTER(_vp), ctypes.POINTER(_i), _vp, _vp, _vp, _vp, _vp]),
+    "os2d_dft_inverse_planes": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "os2d_head_workspace_bytes_ex": (_i, [_i, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_sz)]),
     "os2d_prof_event_create": (_i, [ctypes.POINTER(_vp)]),
     "os2d_prof_event_destroy": (_i, [_vp]),

@@ -417,12 +417,12 @@ int os2d_nms(const float* boxes, const int* counts, int NC, int N, float iou_thr
   return os2d_launch_nms(boxes, counts, NC, N, iou_threshold, keep, num_keep, workspace, os2d_stream(stream));
 }
 
-int os2d_head_forward_ex(const float* fm, const float* qp, const void* w1, const float* b1, const void* w2,
-                         const float* b2, const void* w3, const float* b3, int A, int B, int C, int H, int W, int P,
-                         int inverse, int stride, int rec_field, float* loc, float* cls, float* corners,
-                         void* workspace, size_t workspace_bytes, void* stream, int precision, const void* qs,
-                         void** stage_events, int* chunk_classes, int* status, const float* wspec, const float* twQ,
-                         const float* twP) {
+int os2d_head_forward_ex2(const float* fm, const float* qp, const void* w1, const float* b1, const void* w2,
+                          const float* b2, const void* w3, const float* b3, int A, int B, int C, int H, int W, int P,
+                          int inverse, int stride, int rec_field, float* loc, float* cls, float* corners,
+                          void* workspace, size_t workspace_bytes, void* stream, int precision, const void* qs,
+                          void** stage_events, int* chunk_classes, int* status, const float* wspec, const float* twQ,
+                          const float* twP, const void* wspec2) {
   if (!fm || !qp || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !loc || !cls || !corners || !workspace) {
     os2d_set_error("os2d_head_forward: null pointer");
     return -1;
@@ -448,6 +448,14 @@ int os2d_head_forward_ex(const float* fm, const float* qp, const void* w1, const
     return -1;
   }
   const int fft_T = tiles[0] * tiles[1], xch = dft ? OS2D_XSPEC_CPAD : OS2D_K;
+  // the 5x5 layer 128 -> 64 in the frequency domain as well (fftx3 with the layer's weight spectra; $OS2D_CONV2_FREQ=0: the direct
+  // kernel, for measurements): the layer-1 inverse writes fp32 planes scaled to <= 1, a forward transform of those 128 channels,
+  // the per-bin GEMM 128 -> 64 and the inverse with the layer-2 bias and scales follow.
+  static const bool conv2_freq_env = [] {
+    const char* e = getenv("OS2D_CONV2_FREQ");
+    return !(e && e[0] == '0');
+  }();
+  const bool conv2_freq = dft && wspec2 && conv2_freq_env;
   const bool fp32_ops = precision == OS2D_PRECISION_F32 || precision == OS2D_PRECISION_FFT32;   // fp32 MFMA correlation / 5x5 layers
   if (!fp32_ops && !qs) {
     os2d_set_error("os2d_head_forward: precision f16x3 / f16x2 needs the split class operand (os2d_class_split)");
@@ -545,7 +553,7 @@ int os2d_head_forward_ex(const float* fm, const float* qp, const void* w1, const
           return !(e && e[0] == '0');
         }();
         inv_borders = dft && borders_in_inverse;
-        const int planes = inv_borders ? 0 : NB * 16 * 2;
+        const int planes = (inv_borders || conv2_freq) ? 0 : NB * 16 * 2;      // (fp32 planes for the next transform have no borders)
         if ((planes || sumfx) &&
             (rc = os2d_launch_border_zero_shb_planes_norms(h1, planes, H, W, sumfx, invn, (size_t)NB * H * W, st)))
           return rc;
@@ -565,7 +573,9 @@ int os2d_head_forward_ex(const float* fm, const float* qp, const void* w1, const
                                                 os2d_spectral_xscale_for(tiles[4], tiles[5]), 1, xch, st)))
           return rc;
         mark(b0, 12);
-        if ((rc = os2d_launch_dft_inverse(yspec, b1, 128, h1, mats, NB, 128, H, W, whole_call, inv_borders ? 1 : 0, st))) return rc;
+        if ((rc = os2d_launch_dft_inverse(yspec, b1, 128, h1, mats, NB, 128, H, W, whole_call,
+                                          conv2_freq ? OS2D_DFT_OUT_PLANES : inv_borders ? OS2D_DFT_OUT_SHB_BORDERS : OS2D_DFT_OUT_SHB, st)))
+          return rc;
       } else {
         if ((rc = os2d_launch_fft_forward(corr, invn, xspec, twQ, twP, NB, OS2D_K, H, W, st))) return rc;
         mark(b0, 11);
@@ -588,9 +598,17 @@ int os2d_head_forward_ex(const float* fm, const float* qp, const void* w1, const
         dump_slot(stream, 2, xspec, (size_t)NB * fft_T * OS2D_K * fft_bins * 8);
         dump_slot(stream, 3, yspec, (size_t)NB * fft_T * 128 * fft_bins * 8);
       }
-      dump_slot(stream, 4, h1, (size_t)NB * 128 * PLb * 4);
+      dump_slot(stream, 4, h1, (size_t)NB * 128 * (conv2_freq ? (size_t)H * W : PLb) * 4);      // (fp32 planes on the transform route of layer 2)
     }
-    if (f16) {
+    if (conv2_freq) {
+      // h1: fp32 planes [pair][128][H * W], every sample in [0, 1] - unit norms, and the ReLU of the forward kernel changes nothing;
+      // both spectra buffers are reused (128 channels fit the input stride, 64 the output buffer)
+      if ((rc = os2d_launch_dft_forward(h1, nullptr, xspec, twQ, NB, 128, 128, H, W, st))) return rc;
+      if ((rc = os2d_launch_spectral_gemm_f16(wspec2, xspec, yspec, NB * fft_T, 128, 64, fft_bins,
+                                              os2d_spectral_xscale_for(tiles[4], tiles[5]), 1, 128, st)))
+        return rc;
+      if ((rc = os2d_launch_dft_inverse(yspec, b2, 64, h2, twQ, NB, 64, H, W, whole_call, OS2D_DFT_OUT_SHB_BORDERS, st))) return rc;
+    } else if (f16) {
       if ((rc = os2d_launch_conv_f16x3(2, h1, w2, b2, whole_call, h2, NB, P, H, W, 3, st))) return rc;
     } else {
       if ((rc = os2d_launch_conv(2, h1, static_cast<const float*>(w2), b2, h2, NB, P, H, W, st))) return rc;
@@ -629,6 +647,16 @@ int os2d_head_forward_ex(const float* fm, const float* qp, const void* w1, const
     mark(b0, 9);
   }
   return 0;
+}
+
+int os2d_head_forward_ex(const float* fm, const float* qp, const void* w1, const float* b1, const void* w2,
+                         const float* b2, const void* w3, const float* b3, int A, int B, int C, int H, int W, int P,
+                         int inverse, int stride, int rec_field, float* loc, float* cls, float* corners,
+                         void* workspace, size_t workspace_bytes, void* stream, int precision, const void* qs,
+                         void** stage_events, int* chunk_classes, int* status, const float* wspec, const float* twQ,
+                         const float* twP) {
+  return os2d_head_forward_ex2(fm, qp, w1, b1, w2, b2, w3, b3, A, B, C, H, W, P, inverse, stride, rec_field, loc, cls, corners, workspace,
+                               workspace_bytes, stream, precision, qs, stage_events, chunk_classes, status, wspec, twQ, twP, nullptr);
 }
 
 int os2d_head_forward(const float* fm, const float* qp, const float* w1, const float* b1, const float* w2,
@@ -849,7 +877,7 @@ int os2d_dft_matrices_build(const double* twP64, const double* twQ64, int P, int
 
 int os2d_dft_forward(const float* corr, const float* inv_norm, float* X, const void* matrices, int NB, int C, int H, int W,
                      void* stream) {
-  if (!corr || !inv_norm || !X || !matrices || NB < 1 || C < 1 || H < 1 || W < 1) {
+  if (!corr || !X || !matrices || NB < 1 || C < 1 || H < 1 || W < 1) {      // inv_norm == NULL: unit norms
     os2d_set_error("os2d_dft_forward: bad arguments");
     return -1;
   }
@@ -858,11 +886,22 @@ int os2d_dft_forward(const float* corr, const float* inv_norm, float* X, const v
 
 int os2d_dft_inverse(const float* Y, const float* packed_b, void* out, const void* matrices, int NB, int Cout, int H, int W,
                      int* status, void* stream) {
-  if (!Y || !packed_b || !out || !matrices || NB < 1 || Cout != 128 || H < 1 || W < 1) {
-    os2d_set_error("os2d_dft_inverse: bad arguments (Cout must be 128: the 7x7 layer)");
+  if (!Y || !packed_b || !out || !matrices || NB < 1 || (Cout != 128 && Cout != 64) || H < 1 || W < 1) {
+    os2d_set_error("os2d_dft_inverse: bad arguments (Cout must be 128 or 64: the 7x7 layer / the 5x5 layer 128 -> 64)");
     return -1;
   }
-  return os2d_launch_dft_inverse(Y, packed_b, 128, out, matrices, NB, Cout, H, W, Os2dRangeFlag{status, OS2D_STATUS_F16_RANGE}, 1, os2d_stream(stream));   // incl. the plane borders
+  return os2d_launch_dft_inverse(Y, packed_b, Cout, out, matrices, NB, Cout, H, W, Os2dRangeFlag{status, OS2D_STATUS_F16_RANGE},
+                                 OS2D_DFT_OUT_SHB_BORDERS, os2d_stream(stream));
+}
+
+int os2d_dft_inverse_planes(const float* Y, const float* packed_b, float* out, const void* matrices, int NB, int Cout, int H, int W,
+                            int* status, void* stream) {
+  if (!Y || !packed_b || !out || !matrices || NB < 1 || (Cout != 128 && Cout != 64) || H < 1 || W < 1) {
+    os2d_set_error("os2d_dft_inverse_planes: bad arguments (Cout must be 128 or 64)");
+    return -1;
+  }
+  return os2d_launch_dft_inverse(Y, packed_b, Cout, out, matrices, NB, Cout, H, W, Os2dRangeFlag{status, OS2D_STATUS_F16_RANGE},
+                                 OS2D_DFT_OUT_PLANES, os2d_stream(stream));
 }
 
 int os2d_spectral_weights_build_dft(const double* wfold, const double* twP64, const double* twQ64, int C, int Cout, int P, int Q,

@@ -97,6 +97,9 @@ constexpr int DFT_MAXP = 64;        // transform rows (P <= 64: the 2P rows of s
 constexpr int DFT_MAXV = 48;        // half-spectrum columns (2V <= 96: three 32-column tiles; Q <= 94)
 constexpr int DFT_MAXWK = 96;       // window columns rounded up to 16
 constexpr int DFT_KREG = 8;         // k-steps of the register-resident operand (2 * Pp / 16 <= 8)
+// output forms of the inverse kernel (its ``zero_borders`` argument): split-fp16 activation units, the same + the zero border
+// cells of the planes, or fp32 channel planes [pair][channel][H * W] scaled to <= 1 - what the forward kernel reads
+constexpr int DFT_OUT_SHB = 0, DFT_OUT_SHB_BORDERS = 1, DFT_OUT_PLANES = 2;
 
 struct DftPlan {
   int H, W;                        // map
@@ -544,7 +547,7 @@ DFT_DEV void dft_matrix_unit(int which, int unit, int P, int Q, const double* tw
 // G = 4: Fp2 in registers (the wave owns one row tile of step 2); G = 8 (dft_plan_transform): Fp2 in LDS, free tile ownership
 template <bool TILED, bool FAST, int G, int NW, int KS2 = 0>
 DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
-                              const float* invn,      // [NB][H * W]
+                              const float* invn,      // [NB][H * W]; nullptr: all ones
                               float* X,               // [NBT / 64][NBINS / 4][64][Cpad][4][2] (dft_spectra_pair0)
                               const u32x4* FqT, const u32x4* Fp2, const DftPlan& pl, int C, int Cpad, int NBT, int iters) {
   constexpr int THR = NW * 64;
@@ -556,6 +559,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
   const int P = pl.P, V = pl.V, Pp = pl.Pp, Wk = pl.Wk, N1 = pl.N1, Mx = pl.Mx, N2 = pl.N2, LH = pl.LH, LW = pl.LW, W = pl.W, H = pl.H;
   const int MxS = Mx + 1, N2S = N2 + 1;
   const int CG = (C + G - 1) / G, HW = H * W;
+  const bool unit_norm = invn == nullptr;      // the input is already normalised (every sample in [0, 1]): x = relu(corr)
   u32x4* ldsF = reinterpret_cast<u32x4*>(smem);                                   // FqT [Wk / 8][2][N1]
   u32x4* ldsU = reinterpret_cast<u32x4*>(smem + pl.lds_const);                    // x | R2 | X staging
   unsigned char* ldsUb = smem + pl.lds_const;
@@ -623,12 +627,14 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
 #define DFT_FWD_PREFETCH_SLOTS(IT, TID, S0, S1)                                                              \
   {                                                                                                          \
     DFT_FWD_ITER(IT)                                                                                         \
+    /* invn == nullptr (unit norms): the request stays - the same schedule on both routes - and re-reads the first channel */ \
+    const float* nrm_ = invn ? invn + (size_t)nb_ * HW : corr + ((size_t)nb_ * C + (c0_ < C ? c0_ : C - 1)) * HW; \
     _Pragma("unroll") for (int s = (S0); s < (S1); ++s) {                                                    \
       DFT_FWD_POS(TID, s)                                                                                    \
       if (FAST) {                                                                                            \
         const bool ok = i_ < npos && r_ < LH && 4 * c4_ < LW;                                                \
         const int off = ok ? y_ * W + x_ : 0;                                                                \
-        pn[s] = *reinterpret_cast<const f32x4*>(invn + (size_t)nb_ * HW + off);                             \
+        pn[s] = *reinterpret_cast<const f32x4*>(nrm_ + off);                                                \
         _Pragma("unroll") for (int g = 0; g < G; ++g) {                                                  \
           const int c = c0_ + g < C ? c0_ + g : C - 1;                                                       \
           pc[s][g] = *reinterpret_cast<const f32x4*>(corr + ((size_t)nb_ * C + c) * HW + off);              \
@@ -645,7 +651,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
         const int off0 = y_ * W + x_;                                                                        \
         const bool vec = rok && off0 >= 0 && off0 + 3 < HW;                                                  \
         const int offv = vec ? off0 : 0;                                                                     \
-        pn[s] = *reinterpret_cast<const f32x4u*>(invn + (size_t)nb_ * HW + offv);                            \
+        pn[s] = *reinterpret_cast<const f32x4u*>(nrm_ + offv);                                               \
         _Pragma("unroll") for (int g = 0; g < G; ++g) {                                                      \
           const int c = c0_ + g < C ? c0_ + g : C - 1;                                                       \
           pc[s][g] = *reinterpret_cast<const f32x4u*>(corr + ((size_t)nb_ * C + c) * HW + offv);             \
@@ -654,7 +660,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
           _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                    \
             const bool ok = 4 * c4_ + e < LW && x_ + e >= 0 && x_ + e < W;                                   \
             const int off = ok ? y_ * W + x_ + e : 0;                                                        \
-            pn[s][e] = invn[(size_t)nb_ * HW + off];                                                         \
+            pn[s][e] = nrm_[off];                                                                            \
             _Pragma("unroll") for (int g = 0; g < G; ++g) {                                                  \
               const int c = c0_ + g < C ? c0_ + g : C - 1;                                                   \
               pc[s][g][e] = corr[((size_t)nb_ * C + c) * HW + off];                                          \
@@ -695,7 +701,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const bool ok = FAST ? (r_ < LH && 4 * c4_ < LW) : (r_ < LH && y_ >= 0 && y_ < H && 4 * c4_ + e < LW && x_ + e >= 0 && x_ + e < W);
-            nsc[e] = ok ? pn[s][e] * 32768.0f : 0.f;
+            nsc[e] = ok ? (unit_norm ? 32768.0f : pn[s][e] * 32768.0f) : 0.f;
           }
 #pragma unroll
           for (int g = 0; g < G; ++g) {
@@ -885,7 +891,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
 template <bool TILED, int KSA = 0, int G = DFT_G>
 DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64][Cout][4][2] (dft_spectra_pair0)
                               const float* bp,       // [3][MTP]: bias | - | 2^out_exp
-                              int MTP, unsigned char* out,   // SHB [NB][Cout / 8][2][PLANE] x 16 B
+                              int MTP, unsigned char* out,   // SHB [NB][Cout / 8][2][PLANE] x 16 B | DFT_OUT_PLANES: float [NB][Cout][H * W]
                               const u32x4* E2, const u32x4* Gq, const DftPlan& pl, int Cout, int NBT, int PLANE, int Ws,
                               int BASE, int iters, DFT_FLAG bad_flag, int zero_borders) {
   unsigned char* smem = DFT_LDS;
@@ -1152,6 +1158,7 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
     // work-group of the neighbouring channel group).  G = 8: rows are (h, img) with 8 images per h, so the lower half-wave holds
     // channels 0 - 3 and the upper one channels 4 - 7 of the SAME cell: they swap halves and each stores one whole unit.
     {
+      const bool planes = zero_borders == DFT_OUT_PLANES;
       float bias[4], osc[4];     // of this lane's 4 channels: o0 + (G = 8: 4 hw) + k
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -1164,7 +1171,7 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
       // the zero border of the two planes (cells in front of the map, the 3 pad cells after every row, the tail), this
       // iteration's 8-byte half of every unit: ~3 stores per thread instead of a launch that writes all borders on its own
       // (9 us per step at 64 classes, 0.2 ms at 1024).  Once per (pair, channel group): by the first tile of a tiled map.
-      if (zero_borders && (!TILED || tile == 0)) {
+      if (zero_borders == DFT_OUT_SHB_BORDERS && (!TILED || tile == 0)) {
         const int rows = H * (Ws - W), tail0 = BASE + H * Ws, npad = BASE + rows + (PLANE - tail0);
         for (int k = tl; k < npad; k += DFT_THR) {
           int cell;
@@ -1200,6 +1207,16 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
               t[g] = fmaxf(pre, 0.f) * osc[g];
               // out of the fp16 range, or NaN: the pre-activation is tested too, fmaxf(NaN, 0) = 0 hid a NaN spectrum
               if (inside && (!(fabsf(t[g]) <= 65504.f) || pre != pre)) bad = true;
+            }
+            if (planes) {
+              // the input form of the forward transform: channel planes without borders, every sample <= 1 (the channel scale
+              // puts the bound of the range plan at <= 2^15)
+              if (inside) {
+                float* dst = reinterpret_cast<float*>(out) + ((size_t)nb * Cout + o0 + (G == 8 ? 4 * hw : 0)) * ((size_t)H * W) + (size_t)h * W + w;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) dst[(size_t)g * H * W] = t[g] * (1.0f / 32768.0f);
+              }
+              continue;
             }
             u32x2 hi, lo;
             dft_split4(t[0], t[1], t[2], t[3], &hi, &lo);

@@ -221,7 +221,8 @@ int os2d_launch_dft_forward(const float* corr, const float* inv, float* X, const
   return os2d_launched("dft_forward");
 }
 
-// zero_borders != 0: the kernel also writes the zero border cells of the planes it fills (no os2d_launch_border_zero_shb_planes)
+// zero_borders: the output form (dft_mfma.h).  DFT_OUT_SHB_BORDERS: the kernel also writes the zero border cells of the planes it fills
+// (no os2d_launch_border_zero_shb_planes); DFT_OUT_PLANES: fp32 planes [NB][Cout][H * W] scaled to <= 1 (the forward kernel's input)
 int os2d_launch_dft_inverse(const float* Y, const float* bp, int MTP, void* out, const void* matrices, int NB, int Cout, int H, int W,
                             Os2dRangeFlag status, int zero_borders, hipStream_t stream) {
   DftPlan pl;

@@ -180,8 +180,10 @@ size_t os2d_dft_matrices_size(int P, int Q);
 int os2d_launch_dft_matrices(const double* twP64, const double* twQ64, int P, int Q, void* out, hipStream_t stream);
 int os2d_launch_dft_forward(const float* corr, const float* inv, float* X, const void* matrices, int NB, int C, int Cpad, int H, int W,
                             hipStream_t stream);
+// form: what the inverse kernel writes (= DFT_OUT_* of dft_mfma.h)
+enum { OS2D_DFT_OUT_SHB = 0, OS2D_DFT_OUT_SHB_BORDERS = 1, OS2D_DFT_OUT_PLANES = 2 };
 int os2d_launch_dft_inverse(const float* Y, const float* bp, int MTP, void* out, const void* matrices, int NB, int Cout, int H, int W,
-                            Os2dRangeFlag status, int zero_borders, hipStream_t stream);
+                            Os2dRangeFlag status, int form, hipStream_t stream);
 // corr_f16x3.hip
 int os2d_corr_groups(int C);  // 8-channel groups of the split correlation operands, padded to whole K chunks
 // clear / clear_words: 64-bit words zeroed by the same launch (the packed correlation kernel's sums; NULL / 0: none)

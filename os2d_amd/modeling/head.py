@@ -461,7 +461,9 @@ class TransformationNet(nn.Module):
         bound2 = torch.minimum(l1, l2) + b2.abs()
         e0 = torch.full((225,), lib.os2d_rnorm_exp(), dtype=torch.int32, device=w1.device)
         e1, e2 = out_exp(bound1), out_exp(bound2)
-        return dict(in_exp=[e0, e1, e2], out_exp=[e1, e2, None],
+        # unit_exp: the layer-1 output exponents in the "<= 1" convention (bound * 2^unit_exp <= 1) - what the inverse transform
+        # writes when the 5x5 layer 128 -> 64 runs in the frequency domain too: its forward transform takes samples in [0, 1]
+        return dict(in_exp=[e0, e1, e2], out_exp=[e1, e2, None], unit_exp=e1 - 15,
                     weight_exp=[weight_exp(w1, e0), weight_exp(w2, e1), weight_exp(w3, e2)], bounds=(bound1, bound2))
 
     def packed(self, precision=None):
@@ -584,6 +586,47 @@ class TransformationNet(nn.Module):
                 t.record_stream(cur)
             store.put(self._net_id, slot, _StreamOrdered(key, result, dev))
         return result
+
+    def spectra2(self, H, W):
+        """Split weight spectra of the 5x5 layer 128 -> 64 for the transform size of an H x W map (precision "fftx3"; the layout
+        of ``spectra(H, W, split=True)[0]`` with 128 input channels), cached next to them in a slot of their own.  A 5x5 filter
+        zero-embedded in the centre of a 7x7 one has exactly the same spectrum, so the 7-tap builder serves; column c carries
+        2^-unit_exp[c] of ``range_plan``: the layer-1 inverse transform stores channel c times 2^unit_exp[c] (<= 1)."""
+        lib = _lib.load()
+        self.check_ready()
+        cP, cQ, cN = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        if lib.os2d_dft_sizes(int(H), int(W), ctypes.byref(cP), ctypes.byref(cQ), ctypes.byref(cN), None) != 0:
+            return None
+        P, Q, nbins = cP.value, cQ.value, cN.value
+        dev = self.linear.weight.device
+        key = self._state_key()
+        slot = (P, Q, True, "conv2")
+        store = _SpectraStore.of(dev)
+        cached = store.get(self._net_id, slot, key)
+        if cached is not None:
+            return cached.get(dev)
+        with torch.cuda.device(dev), torch.no_grad():
+            _, (w2, _), _ = self._folded()                       # float64 [64,128,5,5]: the BatchNorm fold
+            unit_exp = self.range_plan()["unit_exp"].to(w2.device).double()
+            w2 = nn.functional.pad(w2 * torch.exp2(-unit_exp).view(1, -1, 1, 1), (1, 1, 1, 1))
+
+            def table64(n):
+                m = torch.arange(n, dtype=torch.float64)
+                ang = m * (-2.0 * torch.pi / n)
+                return torch.stack([torch.cos(ang), torch.sin(ang)], 1).to(dev).contiguous()
+            wfold = w2.to(dev).contiguous()
+            tp64, tq64 = table64(P), table64(Q)
+            scratch = torch.empty(1024, dtype=torch.uint8, device=dev)
+            stream = _lib.current_stream(dev)
+            wspec = torch.empty(lib.os2d_spectral_weight16_bytes(128, nbins), dtype=torch.uint8, device=dev)
+            _lib.check(lib.os2d_spectral_weights_build_dft(_lib.ptr(wfold), _lib.ptr(tp64), _lib.ptr(tq64), 128, 64, P, Q, nbins,
+                                                           _lib.ptr(wspec), _lib.ptr(scratch), stream),
+                       "os2d_spectral_weights_build_dft")
+            cur = torch.cuda.current_stream(dev)
+            for t in (wfold, tp64, tq64, scratch):
+                t.record_stream(cur)
+            store.put(self._net_id, slot, _StreamOrdered(key, wspec, dev))
+        return wspec
 
     @property
     def _spectra_cache(self):
@@ -938,6 +981,11 @@ class Os2dHead(nn.Module):
             spectra = regressor.spectra(H, W, split=precision == "fftx3") if (pinned or pairs >= FFT_MIN_PAIRS) else None
             if spectra is None:
                 precision = "f32" if precision == "fft32" else "f16x3"       # the direct kernels of the same arithmetic family
+        # the 5x5 layer 128 -> 64 follows the route of the 7x7 layer: in the frequency domain whenever that one is (fftx3 only;
+        # $OS2D_CONV2_FREQ=0: the direct kernel - the library reads the same variable)
+        spectra2 = None
+        if precision == "fftx3" and spectra is not None and not os.environ.get("OS2D_CONV2_FREQ", "1").startswith("0"):
+            spectra2 = regressor.spectra2(H, W)
         self.last_precision = precision          # the arithmetic that actually ran (bench.py / tests)
         w1, b1, w2, b2, w3, b3 = regressor.packed(precision)
         if out is None:
@@ -956,14 +1004,15 @@ class Os2dHead(nn.Module):
         with torch.cuda.device(dev):     # hipFuncSetAttribute / launches act on the CURRENT device
             ws = get_workspace(dev, full.value, one.value)
             status = self._status_word() if precision not in FP32_MODES else None
-            _lib.check(lib.os2d_head_forward_ex(
+            _lib.check(lib.os2d_head_forward_ex2(
                 _lib.ptr(feature_maps), _lib.ptr(self._qp), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2),
                 _lib.ptr(w3), _lib.ptr(b3), A, B, C, H, W, P, 1 if self.aligner.use_inverse_geom_model else 0,
                 self._stride, self._rec_field, _lib.ptr(loc), _lib.ptr(cls), _lib.ptr(corners),
                 _lib.ptr(ws), ws.numel(), _lib.current_stream(dev), PRECISIONS[precision],
                 _lib.ptr(self._split_class_operand()) if precision not in FP32_MODES else None, stage_events, None,
-                _lib.host_ptr(status), *([_lib.ptr(t) for t in spectra[:3]] if spectra is not None else [None, None, None])),
-                "os2d_head_forward_ex")
+                _lib.host_ptr(status), *([_lib.ptr(t) for t in spectra[:3]] if spectra is not None else [None, None, None]),
+                _lib.ptr(spectra2)),
+                "os2d_head_forward_ex2")
         strict = self.strict_range if strict_range is None else strict_range
         if strict and precision not in FP32_MODES:
             torch.cuda.current_stream(dev).synchronize()
