@@ -19,11 +19,11 @@ class maps and every TransformNet weight, bias and BatchNorm affine parameter; B
 reference's training default); maps wider than MAX_W_DIRECT7 columns raise.  ``TransformationNet.forward`` on its own and the
 other precisions stay inference-only.
 """
-import collections
-import itertools
+import copy
 import ctypes
 import logging
 import os
+import weakref
 
 import torch
 import torch.nn as nn
@@ -32,6 +32,10 @@ from .. import _lib
 from ..structures.feature_map import FeatureMapSize
 from .box_coder import BoxGridGenerator
 from . import head_train
+from .device_buffers import (STATUS_SLOTS, _WORKSPACES, device_status_word, get_workspace, release_workspaces,  # noqa: F401
+                             workspace_cap_bytes)
+from .spectra import (_NET_IDS, _SpectraStore, _SpectraView, _StreamOrdered, _drop_spectra_of, build_dft_matrices,  # noqa: F401
+                      build_weight_spectra, spectra_cache_cap_bytes, split_rows_f16, transform_sizes, twiddles64)
 
 TEMPLATE = 15
 QROWS = 256
@@ -79,206 +83,6 @@ def build_os2d_head_creator(do_simple_affine, is_cuda, use_inverse_geom_model, f
     return Os2dHeadCreator(aligner, feature_map_stride, feature_map_receptive_field)
 
 
-# --------------------------------------------------------------------------------------------- workspace
-_WORKSPACES = {}
-
-
-def workspace_cap_bytes():
-    """Upper bound of ONE scratch buffer (classes are processed in chunks that fit).  An MI355X has 288 GB of HBM3E, so
-    the default is generous: 16 GiB holds ~1150 classes at 60x80 in one chunk (all 1024 classes of BASELINE.json's
-    configs[2] in a single pass of large launches)."""
-    return int(float(os.environ.get("OS2D_WORKSPACE_GB", "16")) * (1 << 30))
-
-
-def workspace_total_cap_bytes():
-    """Upper bound of ALL scratch buffers of a device together (one per HIP stream in use: 7 for the pyramid runner)."""
-    return int(float(os.environ.get("OS2D_WORKSPACE_TOTAL_GB", "96")) * (1 << 30))
-
-
-def get_workspace(device, wanted, minimum):
-    """Grow-only scratch buffer, one per (device, stream): concurrent heads on different HIP streams (the pyramid
-    runner) must not share intermediates.  The pyramid runner draws its streams from a fixed pool
-    (os2d_amd/engine/pyramid.py), so the number of buffers is bounded by the number of level slots; their total is kept
-    below ``workspace_total_cap_bytes`` by shrinking what a NEW or growing buffer may take (never below ``minimum``, the
-    footprint of one class)."""
-    index = device.index if device.index is not None else torch.cuda.current_device()
-    key = (device.type, index, torch.cuda.current_stream(device).cuda_stream)
-    buf = _WORKSPACES.get(key)
-    others = sum(b.numel() for k, b in _WORKSPACES.items() if b is not None and k != key and k[1] == index)
-    room = max(workspace_total_cap_bytes() - others, 0)
-    size = max(min(wanted, workspace_cap_bytes(), room), minimum)
-    if buf is None or buf.numel() < size:
-        _WORKSPACES[key] = None
-        buf = torch.empty(size, dtype=torch.uint8, device=device)
-        buf[:4096].zero_()       # the range words of a head call live at the start of its workspace (include/os2d_hip.h)
-        _WORKSPACES[key] = buf
-    return buf
-
-
-def release_workspaces():
-    _WORKSPACES.clear()
-
-
-_STATUS_WORDS = {}
-STATUS_SLOTS = 1024
-
-
-class _StatusSlots(object):
-    """The range-status words of one device: pinned arrays of ``STATUS_SLOTS`` int32 that are never freed, a free list, and
-    one slot per LIVE head."""
-
-    def __init__(self):
-        self.arrays = []
-        self.free = []
-
-    def take(self):
-        if not self.free:
-            words = torch.zeros(STATUS_SLOTS, dtype=torch.int32).pin_memory()
-            self.arrays.append(words)
-            self.free.extend(words[i:i + 1] for i in range(STATUS_SLOTS - 1, -1, -1))
-        word = self.free.pop()
-        word[0] = 0
-        return word
-
-    def give_back(self, word):
-        self.free.insert(0, word)          # reused last: kernels of the head that owned it have long drained by then
-
-
-def device_status_word(device, owner=None):
-    """A sticky range-status word of the split-fp16 kernels for ONE head: an int32 in mapped pinned host memory.  The words
-    of a device live in arrays that are allocated once and kept for the life of the process: kernels in flight store to a
-    word through a raw pointer (only when an activation leaves the fp16 range), so the memory must never go back to the host
-    allocator while any kernel of any head may still run - a per-head tensor (round 2) could be garbage-collected with its
-    head while that head's kernels were still queued.  Every LIVE head owns one word (round 3 shared ONE word
-    between all heads of a device: a flag raised by head A's kernels could be consumed and cleared by head B - ADVICE r3; round 4
-    handed slots out round-robin and zeroed a recycled slot under its live owner after 1024 heads - ADVICE r4): a word returns
-    to the free list when ``owner`` is garbage-collected, goes to the back of that list, and the arrays grow by another
-    ``STATUS_SLOTS`` words when every word is owned."""
-    index = device.index if device.index is not None else torch.cuda.current_device()
-    slots = _STATUS_WORDS.get(index)
-    if slots is None:
-        slots = _STATUS_WORDS[index] = _StatusSlots()
-    word = slots.take()
-    if owner is not None:
-        import weakref
-        weakref.finalize(owner, slots.give_back, word)
-    return word
-
-
-class _StreamOrdered(object):
-    """A cached device operand together with the event that marks the end of the kernels that produced it.  Consumers on
-    OTHER streams (the per-level streams of the pyramid runner) wait for that event before their kernels read the
-    buffers; on the producing stream plain stream order is enough."""
-
-    def __init__(self, key, value, device):
-        self.key, self.value = key, value
-        stream = torch.cuda.current_stream(device)
-        self._stream = stream.cuda_stream
-        self._event = torch.cuda.Event()
-        self._event.record(stream)
-
-    def get(self, device):
-        stream = torch.cuda.current_stream(device)
-        if stream.cuda_stream != self._stream:
-            stream.wait_event(self._event)
-            for t in self._tensors():     # the cache may drop the operand while this stream's kernels still read it
-                t.record_stream(stream)
-        return self.value
-
-    def _tensors(self):
-        values = self.value if isinstance(self.value, (tuple, list)) else (self.value,)
-        return [t for t in values if isinstance(t, torch.Tensor)]
-
-    def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in self._tensors())
-
-
-def spectra_cache_cap_bytes(split=True):
-    """Upper bound for the cached weight spectra of one arithmetic FAMILY of the frequency-domain modes on ONE DEVICE - over all
-    transform sizes and all TransformationNets of the process (least recently used entries are dropped first; 654 MB for the
-    64 x 84 transform of a 60 x 80 map).  $OS2D_FFT_CACHE_BYTES overrides both families.
-      split = True  ("fftx3", the default precision): every map is planned on six canonical transform sizes (overlap-save tiles;
-                    os2d_amd/csrc/dft_mfma.h): 2.4 GB in total, whatever the dataset - an eighth of the device's memory, at
-                    most 8 GiB;
-      split = False ("fft" / "fft32"): one set of spectra per FFT-friendly transform size - 52 sizes = 35.6 GB for a dataset fed
-                    at its own aspect ratios and 7 pyramid scales (reference os2d/data/dataloader.py:326;
-                    tools/bench_size_churn.py) - a quarter of the device's memory, at most 64 GiB (under the 8 GiB
-                    cap of round 4 an LRU cache missed on EVERY call of such a cyclic access pattern)."""
-    env = os.environ.get("OS2D_FFT_CACHE_BYTES")
-    if env:
-        return int(env)
-    total = 64 << 30
-    if torch.cuda.is_available():
-        total = torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory
-    return int(min(8 << 30, total // 8)) if split else int(min(64 << 30, total // 4))
-
-
-class _SpectraStore(object):
-    """The cached weight spectra of one device, shared by every TransformationNet of the process (a per-net cap let N
-    nets pin N times the cap, invisibly to the caching allocator's out-of-memory retry).  Entries are keyed by (net id, slot),
-    least recently used first; a net that goes away takes its entries with it."""
-    _stores = {}
-
-    @classmethod
-    def of(cls, device):
-        index = device.index if device.index is not None else torch.cuda.current_device()
-        store = cls._stores.get(index)
-        if store is None:
-            store = cls._stores[index] = cls()
-        return store
-
-    def __init__(self):
-        self.entries = collections.OrderedDict()
-
-    def get(self, net_id, slot, key):
-        entry = self.entries.get((net_id, slot))
-        if entry is None or entry.key != key:
-            return None
-        self.entries.move_to_end((net_id, slot))
-        return entry
-
-    def drop_stale(self, net_id, key):
-        for k in [k for k, e in self.entries.items() if k[0] == net_id and e.key != key]:
-            del self.entries[k]
-
-    def drop_net(self, net_id):
-        for k in [k for k in self.entries if k[0] == net_id]:
-            del self.entries[k]
-
-    def put(self, net_id, slot, entry):
-        family = bool(slot[2])                                 # slot = (P, Q, split): the two families have caps of their own
-        cap, used = spectra_cache_cap_bytes(family), entry.nbytes()
-        for k in list(self.entries):                          # oldest first, whichever net it belongs to
-            if used + sum(e.nbytes() for kk, e in self.entries.items() if bool(kk[1][2]) == family) <= cap:
-                break
-            if bool(k[1][2]) == family:
-                del self.entries[k]
-        self.entries[(net_id, slot)] = entry
-
-    def slots_of(self, net_id):
-        return [k[1] for k in self.entries if k[0] == net_id]
-
-    def nbytes(self):
-        return sum(e.nbytes() for e in self.entries.values())
-
-
-def split_rows_f16(T):
-    """(float64 MODEL of what spectra_pack.hip does on the device; used by tests/test_range_plan.py.)
-    fp16 hi + lo split of a float64 tensor whose leading dimension indexes rows that get their own power-of-two scale
-    (precision "fftx3": the weight spectra; one row per output channel): row r is multiplied by 2^wexp[r], the largest
-    power of two that keeps its largest |entry| <= 32768 (< 65504: no overflow, also not through rounding), then
-    hi = rn16(v), lo = rn16(v - hi): hi + lo carries 22 bits of v wherever |v| >= 2^-3 and an absolute 2^-25 below (fp16
-    subnormal spacing).  Returns (hi, lo, wexp); works in place on T (which holds the residual afterwards)."""
-    dims = tuple(range(1, T.dim()))
-    amax = T.abs().amax(dim=dims).clamp_min(1e-300)
-    wexp = torch.floor(torch.log2(32768.0 / amax)).clamp(-100, 100)
-    T *= torch.exp2(wexp).view(-1, *([1] * (T.dim() - 1)))
-    hi = T.to(torch.float16)
-    T -= hi.double()
-    lo = T.to(torch.float16)
-    return hi, lo, wexp
-
-
 def _require_device_f32(t, name):
     if not isinstance(t, torch.Tensor):
         raise TypeError("{} must be a torch.Tensor".format(name))
@@ -290,37 +94,7 @@ def _require_device_f32(t, name):
     return t.contiguous()
 
 
-_NET_IDS = itertools.count(1)
-
-
 # --------------------------------------------------------------------------------------------- TransformNet
-class _SpectraView(object):
-    """dict-like access to ONE net's entries of a device store (tests / tools: len, in, clear, values)."""
-
-    def __init__(self, store, net_id):
-        self.store, self.net_id = store, net_id
-
-    def __len__(self):
-        return len(self.store.slots_of(self.net_id))
-
-    def __contains__(self, slot):
-        return (self.net_id, slot) in self.store.entries
-
-    def __iter__(self):
-        return iter(self.store.slots_of(self.net_id))
-
-    def values(self):
-        return [e for k, e in self.store.entries.items() if k[0] == self.net_id]
-
-    def clear(self):
-        self.store.drop_net(self.net_id)
-
-
-def _drop_spectra_of(net_id):
-    for store in _SpectraStore._stores.values():
-        store.drop_net(net_id)
-
-
 class TransformationNet(nn.Module):
     """Parameter container with the reference's layout (head.py:604-646): ``conv`` = Sequential(Conv 225->128 k7,
     BatchNorm, ReLU, Conv 128->64 k5, BatchNorm, ReLU) and ``linear`` = Conv 64->output_dim k5, the latter
@@ -365,14 +139,12 @@ class TransformationNet(nn.Module):
     def _new_net_id(self):
         """Key of this net's entries in the per-device spectra store: a process-wide counter, never reused (``id()`` values
         are, after garbage collection), with a finalizer that drops the entries when the net goes away."""
-        import weakref
         self._net_id = next(_NET_IDS)
         weakref.finalize(self, _drop_spectra_of, self._net_id)
 
     def __deepcopy__(self, memo):
         """A copy is a net of its own: fresh id (sharing the original's made the two evict each other's spectra on every
         alternating call, and the original's finalizer dropped the clone's entries - ADVICE r4), no cached packings."""
-        import copy
         cls = self.__class__
         clone = cls.__new__(cls)
         memo[id(self)] = clone
@@ -519,123 +291,54 @@ class TransformationNet(nn.Module):
             self._packed_cache[precision] = _StreamOrdered(key, result, dev)
         return result
 
-    def spectra(self, H, W, split=False):
-        """Frequency-domain form of the 7x7 layer for an H x W map: (wspec, tables A, tables B, nbins), cached per TRANSFORM
-        size (P, Q) - which the many map sizes of a dataset share - until a parameter changes, least recently used first out
-        above ``spectra_cache_cap_bytes()`` (event-tracked like ``packed``).  None only when the library has no transform
-        plan for the map.
-          ``split`` False (precision "fft" / "fft32"): wspec = complex64 weight spectra for os2d_spectral_gemm, tables = the two
-            twiddle tables (twQ, twP) of the in-LDS FFTs (fft.hip; sizes 2^a 3^b or 42 / 84, maps beyond one in-LDS transform
-            are cut into overlap-save tiles, os2d_fft_tiles);
-          ``split`` True (precision "fftx3"): wspec = the weight spectra pre-split into fp16 hi + lo with per-row power-of-two
-            scales (os2d_spectral_gemm_f16) in the bin order of the matrix-product transforms (os2d_dft_sizes: any P % 4 == 0,
-            even Q; tiles beyond 64 x 94), tables A = the four operand matrices of os2d_dft_matrices_build, tables B = None.
-        The BatchNorm-folded 7x7 filters are centred on the origin of the P x Q grid (tap (t, s) at ((3 - t) mod P, (3 - s) mod
-        Q): the circular convolution then IS the zero-padded correlation of head.py:619 for the first H x W samples) and
-        transformed once in float64 on the device (a 7-term DFT per axis, spectra_pack.hip) from exact float64 tables."""
-        lib = _lib.load()
-        self.check_ready()
-        cP, cQ, cN = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        if split:
-            rc = lib.os2d_dft_sizes(int(H), int(W), ctypes.byref(cP), ctypes.byref(cQ), ctypes.byref(cN), None)
-        else:
-            rc = lib.os2d_fft_sizes(int(H), int(W), ctypes.byref(cP), ctypes.byref(cQ), ctypes.byref(cN))
-        if rc != 0:
+    def _cached_spectra(self, H, W, split, slot_tag, build):
+        """This net's entry of slot (P, Q, split) + ``slot_tag`` in the device's store, built by ``build(P, Q, nbins, dev)`` on a
+        miss; None when the library has no plan for the map.  A changed parameter drops every entry of the net on either path."""
+        dev = self.check_ready()
+        plan = transform_sizes(int(H), int(W), bool(split))
+        if plan is None:
             return None
-        P, Q, nbins = cP.value, cQ.value, cN.value
-        dev = self.linear.weight.device
-        key = self._state_key()
-        slot = (P, Q, bool(split))
-        store = _SpectraStore.of(dev)
+        key, slot, store = self._state_key(), plan[:2] + (bool(split),) + slot_tag, _SpectraStore.of(dev)
         cached = store.get(self._net_id, slot, key)
         if cached is not None:
             return cached.get(dev)
         store.drop_stale(self._net_id, key)                      # a parameter changed: every cached size of this net is stale
         with torch.cuda.device(dev), torch.no_grad():
-            (w1, _), _, _ = self._folded()                       # float64 [128,225,7,7]: the BatchNorm fold
-
-            def table64(n):
-                m = torch.arange(n, dtype=torch.float64)
-                ang = m * (-2.0 * torch.pi / n)
-                return torch.stack([torch.cos(ang), torch.sin(ang)], 1).to(dev).contiguous()
-            wfold = w1.to(dev).contiguous()
-            tp64, tq64 = table64(P), table64(Q)
-            scratch = torch.empty(1024, dtype=torch.uint8, device=dev)
-            stream = _lib.current_stream(dev)
-            if split:
-                wspec = torch.empty(lib.os2d_spectral_weight16_bytes(225, nbins), dtype=torch.uint8, device=dev)
-                _lib.check(lib.os2d_spectral_weights_build_dft(_lib.ptr(wfold), _lib.ptr(tp64), _lib.ptr(tq64), 225, 128, P, Q, nbins,
-                                                               _lib.ptr(wspec), _lib.ptr(scratch), stream),
-                           "os2d_spectral_weights_build_dft")
-                mats = torch.empty(lib.os2d_dft_matrices_bytes(P, Q), dtype=torch.uint8, device=dev)
-                _lib.check(lib.os2d_dft_matrices_build(_lib.ptr(tp64), _lib.ptr(tq64), P, Q, _lib.ptr(mats), stream),
-                           "os2d_dft_matrices_build")
-                result = (wspec, mats, None, nbins)
-            else:
-                wspec = torch.empty(lib.os2d_spectral_weight_bytes(225, 128, nbins) // 4, dtype=torch.float32, device=dev)
-                _lib.check(lib.os2d_spectral_weights_build(_lib.ptr(wfold), _lib.ptr(tp64), _lib.ptr(tq64), 225, 128, P, Q, nbins,
-                                                           0, _lib.ptr(wspec), _lib.ptr(scratch), stream), "os2d_spectral_weights_build")
-
-                def table(n):
-                    m = torch.arange(n, dtype=torch.float64)
-                    ang = -2.0 * torch.pi * m / n
-                    return torch.stack([torch.cos(ang), torch.sin(ang)], 1).float().to(dev).contiguous()
-                result = (wspec, table(Q), table(P), nbins)
-            cur = torch.cuda.current_stream(dev)
-            for t in (wfold, tp64, tq64, scratch):
-                t.record_stream(cur)
+            result = build(*plan[:3], dev)
             store.put(self._net_id, slot, _StreamOrdered(key, result, dev))
         return result
+
+    def spectra(self, H, W, split=False):
+        """Frequency-domain form of the 7x7 layer for an H x W map: (wspec, tables A, tables B, nbins), cached per TRANSFORM size
+        (P, Q) - which the many map sizes of a dataset share - until a parameter changes, least recently used first out above
+        ``spectra_cache_cap_bytes()`` (event-tracked like ``packed``).  None only when the library has no plan for the map.
+          ``split`` False (precision "fft" / "fft32"): complex64 spectra, the fp32 twiddle tables (twQ, twP) of the in-LDS FFTs;
+          ``split`` True (precision "fftx3"): fp16 hi + lo spectra, the four operand matrices of os2d_dft_matrices_build, None.
+        Plans, layouts and builders: ``transform_sizes``, ``build_weight_spectra``, ``build_dft_matrices`` (spectra.py)."""
+        def build(P, Q, nbins, dev):
+            wspec = build_weight_spectra(self._folded()[0][0], 225, 128, P, Q, nbins, split, dev)      # the BatchNorm fold, float64
+            if split:
+                return wspec, build_dft_matrices(P, Q, dev), None, nbins
+            return wspec, twiddles64(Q, dev).float(), twiddles64(P, dev).float(), nbins
+        return self._cached_spectra(H, W, split, (), build)
 
     def spectra2(self, H, W):
         """Split weight spectra of the 5x5 layer 128 -> 64 for the transform size of an H x W map (precision "fftx3"; the layout
         of ``spectra(H, W, split=True)[0]`` with 128 input channels), cached next to them in a slot of their own.  A 5x5 filter
         zero-embedded in the centre of a 7x7 one has exactly the same spectrum, so the 7-tap builder serves; column c carries
         2^-unit_exp[c] of ``range_plan``: the layer-1 inverse transform stores channel c times 2^unit_exp[c] (<= 1)."""
-        lib = _lib.load()
-        self.check_ready()
-        cP, cQ, cN = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        if lib.os2d_dft_sizes(int(H), int(W), ctypes.byref(cP), ctypes.byref(cQ), ctypes.byref(cN), None) != 0:
-            return None
-        P, Q, nbins = cP.value, cQ.value, cN.value
-        dev = self.linear.weight.device
-        key = self._state_key()
-        slot = (P, Q, True, "conv2")
-        store = _SpectraStore.of(dev)
-        cached = store.get(self._net_id, slot, key)
-        if cached is not None:
-            return cached.get(dev)
-        with torch.cuda.device(dev), torch.no_grad():
+        def build(P, Q, nbins, dev):
             _, (w2, _), _ = self._folded()                       # float64 [64,128,5,5]: the BatchNorm fold
             unit_exp = self.range_plan()["unit_exp"].to(w2.device).double()
             w2 = nn.functional.pad(w2 * torch.exp2(-unit_exp).view(1, -1, 1, 1), (1, 1, 1, 1))
-
-            def table64(n):
-                m = torch.arange(n, dtype=torch.float64)
-                ang = m * (-2.0 * torch.pi / n)
-                return torch.stack([torch.cos(ang), torch.sin(ang)], 1).to(dev).contiguous()
-            wfold = w2.to(dev).contiguous()
-            tp64, tq64 = table64(P), table64(Q)
-            scratch = torch.empty(1024, dtype=torch.uint8, device=dev)
-            stream = _lib.current_stream(dev)
-            wspec = torch.empty(lib.os2d_spectral_weight16_bytes(128, nbins), dtype=torch.uint8, device=dev)
-            _lib.check(lib.os2d_spectral_weights_build_dft(_lib.ptr(wfold), _lib.ptr(tp64), _lib.ptr(tq64), 128, 64, P, Q, nbins,
-                                                           _lib.ptr(wspec), _lib.ptr(scratch), stream),
-                       "os2d_spectral_weights_build_dft")
-            cur = torch.cuda.current_stream(dev)
-            for t in (wfold, tp64, tq64, scratch):
-                t.record_stream(cur)
-            store.put(self._net_id, slot, _StreamOrdered(key, wspec, dev))
-        return wspec
+            return build_weight_spectra(w2, 128, 64, P, Q, nbins, True, dev)
+        return self._cached_spectra(H, W, True, ("conv2",), build)
 
     @property
     def _spectra_cache(self):
         """{slot: entry} view of this net's cached weight spectra (the store itself is per device, shared by all nets)."""
         dev = self.linear.weight.device
-        if dev.type != "cuda":
-            return {}
-        store = _SpectraStore.of(dev)
-        return _SpectraView(store, self._net_id)
+        return _SpectraView(_SpectraStore.of(dev), self._net_id) if dev.type == "cuda" else {}
 
     def forward(self, corr_maps, precision="f32"):
         """corr_maps [N,225,H,W] -> transform parameters [N,P,H,W] (reference head.py:648-655): input normalisation + the
@@ -1002,7 +705,7 @@ class Os2dHead(nn.Module):
         _lib.check(lib.os2d_head_workspace_bytes_ex(A, B, C, H, W, P, PRECISIONS[precision], ctypes.byref(full)), "os2d_head_workspace_bytes_ex")
         _lib.check(lib.os2d_head_workspace_bytes_ex(A, 1, C, H, W, P, PRECISIONS[precision], ctypes.byref(one)), "os2d_head_workspace_bytes_ex")
         with torch.cuda.device(dev):     # hipFuncSetAttribute / launches act on the CURRENT device
-            ws = get_workspace(dev, full.value, one.value)
+            ws = get_workspace(dev, min(full.value, workspace_cap_bytes()), one.value)      # (a cap replaced on THIS module is obeyed)
             status = self._status_word() if precision not in FP32_MODES else None
             _lib.check(lib.os2d_head_forward_ex2(
                 _lib.ptr(feature_maps), _lib.ptr(self._qp), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2),

@@ -11,33 +11,12 @@ import ctypes
 
 import torch
 
+from freq_util import dft_sizes, fft_sizes, twiddles
 from os2d_amd import _lib
 from os2d_amd.modeling import head as head_mod
 from os2d_amd.utils import synthetic
 
 NF, NA = 4, 3           # victim streams, aggressor streams
-
-
-def _twiddles(n, device):
-    import numpy as np
-    m = torch.arange(n, dtype=torch.float64)
-    ang = -2.0 * np.pi * m / n
-    return torch.stack([torch.cos(ang), torch.sin(ang)], 1).float().to(device).contiguous()
-
-
-def _fft_sizes(H, W):
-    lib = _lib.load()
-    P, Q, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(lib.os2d_fft_sizes(H, W, ctypes.byref(P), ctypes.byref(Q), ctypes.byref(nb)), "os2d_fft_sizes")
-    return P.value, Q.value, nb.value
-
-
-def _dft_sizes(H, W):
-    """Transform size of the matrix-product transforms (precision "fftx3"): P % 4 == 0, even Q, bins = v * P + u."""
-    lib = _lib.load()
-    P, Q, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(lib.os2d_dft_sizes(H, W, ctypes.byref(P), ctypes.byref(Q), ctypes.byref(nb), None), "os2d_dft_sizes")
-    return P.value, Q.value, nb.value
 
 
 class Harness:
@@ -69,10 +48,10 @@ class Harness:
         if kind in self._victims:
             return self._victims[kind]
         lib, dev, H, W, NB, g = self.lib, self.dev, self.H, self.W, self.NB, self.g
-        P, Q, nbins = _fft_sizes(H, W)
+        P, Q, nbins = fft_sizes(H, W)
         if kind == "fft":
             C, Cout = 225, 128
-            tq, tp = _twiddles(Q, dev), _twiddles(P, dev)
+            tq, tp = twiddles(Q, dev), twiddles(P, dev)
             corr = [torch.randn(NB, C, H * W, generator=g).to(dev) for _ in range(NF)]
             inv = [torch.rand(NB, H * W, generator=g).to(dev) + 0.5 for _ in range(NF)]
             Yin = [torch.randn(NB, Cout, nbins, 2, generator=g).to(dev) for _ in range(NF)]
@@ -91,7 +70,7 @@ class Harness:
         elif kind == "gemm16":
             # the split-half GEMM as the head runs it: spectra in quads of bins x channels on both sides (dft_mfma.hip's layouts)
             w16 = self.net.spectra(H, W, split=True)[0]
-            nb2 = _dft_sizes(H, W)[2]
+            nb2 = dft_sizes(H, W)[2]
             xs = lib.os2d_dft_xscale(H, W)
             cpad = lib.os2d_dft_channel_stride(225)
             X = [(torch.rand(nb2 // 4, NB, cpad, 4, 2, generator=g) * 40.0 - 20.0).to(dev) for _ in range(NF)]
@@ -106,7 +85,7 @@ class Harness:
         elif kind == "dft":
             # the matrix-product transforms (half-precision MFMA + VALU splits, hand-made LDS-only barriers)
             C, Cout = 225, 128
-            nb2 = _dft_sizes(H, W)[2]
+            nb2 = dft_sizes(H, W)[2]
             cpad = lib.os2d_dft_channel_stride(C)
             mats = self.net.spectra(H, W, split=True)[1]
             corr = [torch.randn(NB, C, H * W, generator=g).to(dev) for _ in range(NF)]

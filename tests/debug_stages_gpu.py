@@ -12,14 +12,14 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
 import util  # noqa: E402
+from freq_util import plane_interior  # noqa: E402
 from oracle import head_oracle as O  # noqa: E402
 from os2d_amd import _lib  # noqa: E402
 
 
 def unpad(x, NB, Cst, H, W, plane):
     """plane layout (os2d_common.h): cell(h,w) = BASE + h*(W+3) + w, BASE = round_up(3*(W+3)+3, 4)."""
-    Ws = W + 3
-    base = (3 * Ws + 3 + 3) // 4 * 4
+    Ws, base = plane_interior(H, W)
     x = x.view(NB, Cst, plane)
     data = x[:, :, base:base + H * Ws].reshape(NB, Cst, H, Ws)
     inner = data[:, :, :, :W].contiguous()

@@ -66,17 +66,12 @@ def test_fft_plan_host_logic():
     """os2d_fft_sizes / os2d_fft_tiles are host code: transform sizes of the frequency-domain 7x7 layer for the pyramid
     levels of BASELINE.json configs[4] (the 96 x 128 level is cut into overlap-save tiles), the invariants every plan must
     satisfy for every map (the in-LDS FFTs serve precisions "fft" / "fft32"), and the fp16 scale of the input spectra."""
-    import ctypes
+    from freq_util import fft_sizes, fft_tiles
     from os2d_amd import _lib
     lib = _lib.load()
 
-    def plan(h, w):
-        P, Q, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        ty, tx, th, tw = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        rc = lib.os2d_fft_sizes(h, w, ctypes.byref(P), ctypes.byref(Q), ctypes.byref(nb))
-        rc2 = lib.os2d_fft_tiles(h, w, ctypes.byref(ty), ctypes.byref(tx), ctypes.byref(th), ctypes.byref(tw))
-        assert rc == rc2
-        return (rc, P.value, Q.value, nb.value, ty.value, tx.value, th.value, tw.value)
+    def plan(h, w):          # both calls raise unless they return 0
+        return (0,) + fft_sizes(h, w) + fft_tiles(h, w)
 
     expected = {(30, 40): (36, 48), (38, 50): (42, 54), (48, 64): (54, 72), (60, 80): (64, 84), (72, 96): (84, 108), (84, 112): (96, 128)}
     for (h, w), (p, q) in expected.items():
@@ -109,15 +104,13 @@ def test_dft_plan_host_logic():
     and even Q <= 94 could be a transform size; the default policy plans every map on SIX canonical sizes - the exact transforms
     of the 7-scale pyramid of a 1280 x 960 image - through overlap-save tiles, so that the weight spectra of a whole dataset are
     2.4 GB, not one 0.2 - 0.7 GB set per map shape; every map up to the head's width limit has a plan."""
-    import ctypes
+    from freq_util import dft_sizes
     from os2d_amd import _lib
     lib = _lib.load()
 
-    def plan(h, w):
-        P, Q, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        t = (ctypes.c_int * 6)()
-        rc = lib.os2d_dft_sizes(h, w, ctypes.byref(P), ctypes.byref(Q), ctypes.byref(nb), t)
-        return (rc, P.value, Q.value, nb.value) + tuple(t)
+    def plan(h, w):          # the call raises unless it returns 0
+        P, Q, nb, tiles = dft_sizes(h, w)
+        return (0, P, Q, nb) + tiles
 
     canonical = {(36, 46), (44, 54), (48, 62), (52, 68), (56, 70), (64, 84)}
     assert plan(60, 80) == (0, 64, 84, 2752, 1, 1, 60, 80, 60, 80)

@@ -24,6 +24,7 @@ import ctypes
 import pytest
 import torch
 
+from freq_util import dft_sizes, fft_sizes, matrices, shb_decode, shb_encode, twiddles, weight_spectra
 from os2d_amd import _lib
 from os2d_amd.utils import synthetic
 
@@ -73,18 +74,6 @@ def make_inputs(net, H, W, cout_live, device):
     return stored, pre, torch.relu(pre), bp, w2
 
 
-def decode_shb(out, NBn, C, H, W, out_scale):
-    lib = _lib.load()
-    plane = lib.os2d_plane_floats(H, W)
-    Ws, base = W + 3, (3 * (W + 3) + 3 + 3) // 4 * 4
-    units = out.view(torch.float16).view(NBn, C // 8, 2, plane, 8).double()
-    val = (units[:, :, 0] + units[:, :, 1]).permute(0, 1, 3, 2).reshape(NBn, C, plane)
-    got = val[:, :, base:base + H * Ws].reshape(NBn, C, H, Ws)[..., :W] / out_scale.view(1, -1, 1, 1)
-    border = val.clone()
-    border[:, :, base:base + H * Ws].view(NBn, C, H, Ws)[..., :W] = 0
-    return got, float(border.abs().max())
-
-
 def error_of(got, pre, ref):
     scale = pre.abs().amax(dim=(0, 2, 3)).clamp_min(1e-300)
     return float(((got - ref).abs() / scale.view(1, -1, 1, 1)).max())
@@ -92,24 +81,14 @@ def error_of(got, pre, ref):
 
 def spectra_of(net, w2fold, H, W, device):
     """the layer's split weight spectra as TransformationNet.spectra2 builds them, from the given folded weights"""
-    from test_dft_gpu import table64
-    from test_spectral_gpu import dft_sizes
-    lib = _lib.load()
     P, Q, nbins, _ = dft_sizes(H, W)
     unit_exp = net.range_plan()["unit_exp"].to(device).double()
-    wfold = torch.nn.functional.pad(w2fold * torch.exp2(-unit_exp).view(1, -1, 1, 1), (1, 1, 1, 1)).contiguous()
-    tp, tq = table64(P, device), table64(Q, device)
-    w16 = torch.empty(lib.os2d_spectral_weight16_bytes(128, nbins), dtype=torch.uint8, device=device)
-    scratch = torch.empty(1024, dtype=torch.uint8, device=device)
-    _lib.check(lib.os2d_spectral_weights_build_dft(_lib.ptr(wfold), _lib.ptr(tp), _lib.ptr(tq), 128, 64, P, Q, nbins, _lib.ptr(w16),
-                                                   _lib.ptr(scratch), _lib.current_stream(device)), "os2d_spectral_weights_build_dft")
-    return w16
+    wfold = torch.nn.functional.pad(w2fold * torch.exp2(-unit_exp).view(1, -1, 1, 1), (1, 1, 1, 1))
+    return weight_spectra(wfold, P, Q, nbins, True, device)
 
 
 def run_freq(net, stored, bp, w16, H, W, device):
     """forward transform (unit norms) -> per-bin GEMM 128 -> 64 -> inverse transform with the layer-2 epilogue; SHB bytes + status"""
-    from test_dft_gpu import matrices
-    from test_spectral_gpu import dft_sizes
     lib = _lib.load()
     P, Q, nbins, (TY, TX, TH, TW, LH, LW) = dft_sizes(H, W)
     T = TY * TX
@@ -132,20 +111,11 @@ def run_freq(net, stored, bp, w16, H, W, device):
 def run_direct(net, stored, bp, w2fold, H, W, device):
     """the direct kernel on the same inputs (split-half blocked input with the layer-1 scales); needs unmodified weights"""
     lib = _lib.load()
-    plane = lib.os2d_plane_floats(H, W)
-    Ws, base = W + 3, (3 * (W + 3) + 3 + 3) // 4 * 4
-    v = stored.double() * 32768.0                                                      # 2^out_exp1 = 2^(unit_exp + 15)
-    hi = v.to(torch.float16)
-    lo = (v - hi.double()).to(torch.float16)
-    shb = torch.zeros(NB, 16, 2, plane, 8, dtype=torch.float16, device=device)
-    for part, t in ((0, hi), (1, lo)):
-        cells = torch.zeros(NB, 16, 8, H, Ws, dtype=torch.float16, device=device)
-        cells[..., :W] = t.view(NB, 16, 8, H, W)
-        shb[:, :, part, base:base + H * Ws] = cells.reshape(NB, 16, 8, H * Ws).permute(0, 1, 3, 2)
+    shb = shb_encode(stored, 32768.0)                                                  # 2^out_exp1 = 2^(unit_exp + 15)
     w2p = net.packed("fftx3")[2]
     out = torch.full((NB * lib.os2d_shb_bytes(64, H, W),), 0x5A, dtype=torch.uint8, device=device)
     status = torch.zeros(1, dtype=torch.int32, device=device)
-    _lib.check(lib.os2d_transform_conv_f16x3(2, _lib.ptr(shb.view(torch.uint8).view(-1)), _lib.ptr(w2p), _lib.ptr(bp), _lib.ptr(out), NB, 6,
+    _lib.check(lib.os2d_transform_conv_f16x3(2, _lib.ptr(shb), _lib.ptr(w2p), _lib.ptr(bp), _lib.ptr(out), NB, 6,
                                              H, W, 3, _lib.ptr(status), _lib.current_stream(device)), "os2d_transform_conv_f16x3")
     torch.cuda.synchronize()
     return out, int(status.item())
@@ -159,11 +129,11 @@ def measure(net, name, device, route):
         if cout_live != 64:        # the direct kernel takes the net's own packed weights: dead rows are compared on the live ones only
             pre, ref = pre[:, :cout_live], ref[:, :cout_live]
         out, status = run_direct(net, stored, bp, w2, H, W, device)
-        got, border = decode_shb(out, NB, 64, H, W, out_scale)
-        return error_of(got[:, :cout_live], pre, ref), border, status
+        got, border = shb_decode(out, NB, 64, H, W)
+        return error_of((got / out_scale.view(1, -1, 1, 1))[:, :cout_live], pre, ref), border, status
     out, status = run_freq(net, stored, bp, spectra_of(net, w2, H, W, device), H, W, device)
-    got, border = decode_shb(out, NB, 64, H, W, out_scale)
-    return error_of(got, pre, ref), border, status
+    got, border = shb_decode(out, NB, 64, H, W)
+    return error_of(got / out_scale.view(1, -1, 1, 1), pre, ref), border, status
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -182,11 +152,46 @@ def test_spectra2_of_the_net_are_what_the_stage_test_builds(net, device):
     assert torch.equal(net.spectra2(H, W), spectra_of(net, w2, H, W, device))
 
 
+def test_spectra_of_the_net_are_what_independent_builders_give(net, device):
+    """TransformationNet.spectra - both arithmetic families at 9 x 11 - gives, byte for byte, what the test-side builders of
+    freq_util make from the folded filters: the split spectra and the transform matrices, the complex64 spectra and both fp32
+    twiddle tables."""
+    H, W = 9, 11
+    (w1, _), _, _ = net._folded()
+    P, Q, nbins, _ = dft_sizes(H, W)
+    got = net.spectra(H, W, split=True)
+    assert torch.equal(got[0], weight_spectra(w1, P, Q, nbins, True, device))
+    assert torch.equal(got[1], matrices(P, Q, device))
+    assert got[2] is None and got[3] == nbins
+    P, Q, nbins = fft_sizes(H, W)
+    got = net.spectra(H, W)
+    assert torch.equal(got[0], weight_spectra(w1, P, Q, nbins, False, device))
+    assert torch.equal(got[1], twiddles(Q, device)) and torch.equal(got[2], twiddles(P, device))
+    assert got[3] == nbins
+
+
+def test_spectra2_alone_drops_the_stale_entries_of_a_changed_net(device):
+    """spectra2 on a fresh net BEFORE spectra: after a parameter changes, the next spectra2 call on its own drops the stale
+    layer-1 entry (it used to rely on spectra having run first) and returns new bytes."""
+    from os2d_amd.modeling import head as head_mod
+    H, W = 9, 11
+    fresh = head_mod.TransformationNet(output_dim=6)
+    fresh.load_state_dict(synthetic.make_transform_net_state(6, seed=3))
+    fresh.to(device).eval()
+    P, Q, _, _ = dft_sizes(H, W)
+    old = fresh.spectra2(H, W).clone()
+    fresh.spectra(H, W, split=True)
+    assert sorted(fresh._spectra_cache, key=len) == [(P, Q, True), (P, Q, True, "conv2")]
+    with torch.no_grad():
+        fresh.conv[3].weight.mul_(1.5)
+    new = fresh.spectra2(H, W)
+    assert list(fresh._spectra_cache) == [(P, Q, True, "conv2")]          # the stale layer-1 entry is gone
+    assert not torch.equal(new, old)
+
+
 def test_inverse_planes_are_the_scaled_activations(net, device):
     """os2d_dft_inverse_planes (the layer-1 output form on this route) = the split-half output of os2d_dft_inverse times 2^-15,
     as fp32 planes without borders."""
-    from test_dft_gpu import matrices
-    from test_spectral_gpu import dft_sizes
     lib = _lib.load()
     H, W, Cout = 21, 30, 128
     P, Q, nbins, _ = dft_sizes(H, W)
@@ -205,7 +210,7 @@ def test_inverse_planes_are_the_scaled_activations(net, device):
     _lib.check(lib.os2d_dft_inverse_planes(_lib.ptr(Y), _lib.ptr(bp), _lib.ptr(planes), _lib.ptr(mats), NB, Cout, H, W, _lib.ptr(status), st),
                "inverse planes")
     torch.cuda.synchronize()
-    got, border = decode_shb(shb, NB, Cout, H, W, torch.ones(Cout, dtype=torch.float64, device=device))
+    got, border = shb_decode(shb, NB, Cout, H, W)
     assert border == 0.0 and int(status.item()) == 0
     # hi + lo carries 22 bits of the fp32 value
     assert float((planes.double() * 32768.0 - got).abs().max()) <= 2.0 ** -21 * float(got.abs().max())

@@ -3,35 +3,13 @@
 for the in-LDS FFTs of the fp32 modes: untiled and tiled maps (ragged tiles), widths that are not a multiple of 4, maps wider
 than the direct 7x7 kernels take, the spectra layouts of both sides of the per-bin GEMM (quads of bins x channels,
 bin = v * P + u).  The kernel source itself also runs on the CPU emulator (tests/test_dft_mfma_host.py)."""
-import numpy as np
 import pytest
 import torch
 
+from freq_util import dft_sizes, matrices, shb_decode, windows
 from os2d_amd import _lib
-from test_spectral_gpu import dft_sizes
 
 pytestmark = pytest.mark.gpu
-
-
-def table64(n, device):
-    m = torch.arange(n, dtype=torch.float64)
-    ang = m * (-2.0 * np.pi / n)
-    return torch.stack([torch.cos(ang), torch.sin(ang)], 1).to(device).contiguous()
-
-
-def matrices(P, Q, device):
-    lib = _lib.load()
-    tp, tq = table64(P, device), table64(Q, device)
-    out = torch.empty(lib.os2d_dft_matrices_bytes(P, Q), dtype=torch.uint8, device=device)
-    _lib.check(lib.os2d_dft_matrices_build(_lib.ptr(tp), _lib.ptr(tq), P, Q, _lib.ptr(out), _lib.current_stream(device)), "os2d_dft_matrices_build")
-    torch.cuda.synchronize()
-    return out
-
-
-def windows(H, W):
-    P, Q, nbins, (TY, TX, TH, TW, LH, LW) = dft_sizes(H, W)
-    oy, ox = (3 if TY > 1 else 0), (3 if TX > 1 else 0)
-    return [(ty * TH, tx * TW, oy, ox) for ty in range(TY) for tx in range(TX)], (P, Q, nbins, TY, TX, TH, TW, LH, LW)
 
 
 PYRAMID_LEVELS = [(30, 40), (38, 50), (48, 64), (60, 80), (72, 96), (84, 112), (96, 128)]
@@ -119,17 +97,12 @@ def test_dft_inverse_matches_torch_fft_and_epilogue(H, W, NB, device):
     mats, bpd = matrices(P, Q, device), bp.to(device)
     _lib.check(lib.os2d_dft_inverse(_lib.ptr(Yq), _lib.ptr(bpd), _lib.ptr(out), _lib.ptr(mats), NB, Cout, H, W, _lib.ptr(status),
                                     _lib.current_stream(device)), "os2d_dft_inverse")
-    plane = lib.os2d_plane_floats(H, W)
-    Ws, base = W + 3, (3 * (W + 3) + 3 + 3) // 4 * 4
-    units = out.view(torch.float16).view(NB, Cout // 8, 2, plane, 8).double().cpu()
-    val = (units[:, :, 0] + units[:, :, 1]).permute(0, 1, 3, 2).reshape(NB, Cout, plane)          # [NB,Cout,PLANE] scaled values
-    got = val[:, :, base:base + H * Ws].reshape(NB, Cout, H, Ws)[..., :W] / torch.exp2(oexp).view(1, -1, 1, 1)
+    val, border = shb_decode(out, NB, Cout, H, W)                                                  # scaled values
+    got = val.cpu() / torch.exp2(oexp).view(1, -1, 1, 1)
     ref = torch.relu(y_true + bias.view(1, -1, 1, 1))
     err = ((got - ref).abs() / fmax.view(1, -1, 1, 1)).max()
     assert float(err) < 2e-6, float(err)
-    border = val.clone()
-    border[:, :, base:base + H * Ws].view(NB, Cout, H, Ws)[..., :W] = 0
-    assert float(border.abs().max()) == 0.0
+    assert border == 0.0
     assert int(status.item()) == 0
 
 

@@ -15,8 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+from freq_util import matrices, shb_decode, windows
 from os2d_amd import _lib
-from test_dft_gpu import matrices, windows
 
 pytestmark = pytest.mark.gpu
 
@@ -124,7 +124,6 @@ def inverse_run(H, W, NB, device):
 
 def inverse_case(H, W, NB, device):
     """-> (max |relu(y + bias) - float64|, the activation buffer)"""
-    lib = _lib.load()
     wins, (P, Q, nbins, TY, TX, TH, TW, LH, LW) = check_plan(H, W)
     T, V = TY * TX, Q // 2 + 1
     out, _ = inverse_run(H, W, NB, device)
@@ -139,11 +138,7 @@ def inverse_case(H, W, NB, device):
         th, tw = min(TH, H - y0), min(TW, W - x0)
         ref[:, :, y0:y0 + th, x0:x0 + tw] = full[:, t, :, oy:oy + th, ox:ox + tw]
     ref = np.maximum(ref + bias.double().numpy().reshape(1, -1, 1, 1), 0.0)
-    plane = lib.os2d_plane_floats(H, W)
-    Ws, base = W + 3, (3 * (W + 3) + 3 + 3) // 4 * 4
-    units = out.view(torch.float16).view(NB, COUT // 8, 2, plane, 8).double().cpu()
-    val = (units[:, :, 0] + units[:, :, 1]).permute(0, 1, 3, 2).reshape(NB, COUT, plane)
-    got = (val[:, :, base:base + H * Ws].reshape(NB, COUT, H, Ws)[..., :W] / 4096.0).numpy()
+    got = (shb_decode(out, NB, COUT, H, W)[0].cpu() / 4096.0).numpy()
     return float(np.abs(got - ref).max()), out
 
 

@@ -687,12 +687,9 @@ def test_tiled_frequency_domain_route_matches_oracle_and_direct_kernel(H, W, C, 
     them into overlap-save tiles (os2d_fft_tiles).  Ragged tilings (tile sizes that do not divide the map), a one-axis
     tiling and the widest supported map, against the oracle and against the direct f16x3 kernel on the same inputs."""
     from os2d_amd.utils import synthetic
-    import ctypes
-    from os2d_amd import _lib
-    lib = _lib.load()
-    t4 = [ctypes.c_int() for _ in range(4)]
-    _lib.check(lib.os2d_fft_tiles(H, W, *[ctypes.byref(t) for t in t4]), "os2d_fft_tiles")
-    assert t4[0].value * t4[1].value > 1, "the case is meant to be tiled"
+    from freq_util import fft_tiles
+    TY, TX, _, _ = fft_tiles(H, W)
+    assert TY * TX > 1, "the case is meant to be tiled"
     P, inverse = 6, True
     state = synthetic.make_transform_net_state(P, seed=4)
     fm = synthetic.make_feature_map(C, H, W, seed=H + W, A=A)          # A = 2: two images per call (pair = image x class x tile)
@@ -741,8 +738,8 @@ def test_correlation_stage_matches_reference(name, device):
     (``ref_corr``, the TransformNet input recorded by a forward hook in tests/golden/make_golden.py): os2d_fm_sumsq +
     os2d_corr (fp32 MFMA) and os2d_corr_f16x3 (split-fp16 MFMA, LDS-DMA staging, wide-store epilogue) through the C ABI;
     their normalised outputs (zero-bordered planes / split-half blocked units) against relu + L2 of the same tensor."""
-    import ctypes
     import torch.nn.functional as F
+    from freq_util import plane_interior, shb_decode
     from os2d_amd import _lib
     lib = _lib.load()
     fx = util.load_head_fixture(name)
@@ -759,7 +756,7 @@ def test_correlation_stage_matches_reference(name, device):
     r = F.relu(fx["ref_corr"])
     rn_ref = (r / (r.norm(dim=1, keepdim=True) + 1e-6)).reshape(NB, 225, H, W)
     plane = lib.os2d_plane_floats(H, W)
-    Ws, base = W + 3, (3 * (W + 3) + 3 + 3) // 4 * 4
+    Ws, base = plane_interior(H, W)
     # ---- fp32 kernels
     sumsq = torch.empty(A * HW, device=device)
     corr = torch.empty(NB, 225, HW, device=device)
@@ -779,15 +776,11 @@ def test_correlation_stage_matches_reference(name, device):
                                    _lib.ptr(ws), ws.numel(), st), "os2d_corr_f16x3")
     assert util.maxdiff(corr16, ref) < 2e-6
     # split-half blocked units: [NB][29][hi|lo][PLANE][8 halves], value = (hi + lo) * 2^-rnorm_exp
-    units = rshb.view(torch.float16).view(NB, 29, 2, plane, 8).float()
-    val = (units[:, :, 0] + units[:, :, 1]) * 2.0 ** -lib.os2d_rnorm_exp()                     # [NB,29,PLANE,8]
-    val = val.permute(0, 1, 3, 2).reshape(NB, 232, plane)
-    got16 = val[:, :225, base:base + H * Ws].reshape(NB, 225, H, Ws)[..., :W]
+    val, border = shb_decode(rshb, NB, 232, H, W)
+    got16 = val[:, :225] * 2.0 ** -lib.os2d_rnorm_exp()
     assert util.maxdiff(got16, rn_ref) < 2e-6
     assert float(val[:, 225:].abs().max()) == 0.0                                              # padding channels of the last group
-    border = val.clone()
-    border[:, :, base:base + H * Ws].view(NB, 232, H, Ws)[..., :W] = 0
-    assert float(border.abs().max()) == 0.0                                                    # zero borders baked in
+    assert border == 0.0                                                                       # zero borders baked in
 
 
 def _packed_corr(lib, fm, qs, B, device, form=1):

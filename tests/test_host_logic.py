@@ -364,3 +364,73 @@ def test_fixture_pins_cover_every_head_fixture_and_fp32_equivalent_mode():
         assert sorted(modes) == sorted(util.FP32_EQUIVALENT), name
         for mode, ratios in modes.items():
             assert len(ratios) == 3 and all(0.0 <= r <= 0.25 for r in ratios), (name, mode, ratios)
+
+
+class _Entry(object):
+    """What _SpectraStore holds, without a device: a state key and a size."""
+
+    def __init__(self, key, size):
+        self.key, self._size = key, size
+
+    def nbytes(self):
+        return self._size
+
+
+def test_spectra_store_is_lru_per_family_across_nets(monkeypatch):
+    from os2d_amd.modeling.spectra import _SpectraStore, _SpectraView
+    monkeypatch.setenv("OS2D_FFT_CACHE_BYTES", "100")
+    store = _SpectraStore()
+    a, b, conv2 = (16, 24, True), (24, 36, True), (16, 24, True, "conv2")
+    store.put(1, a, _Entry("k1", 40))
+    store.put(2, a, _Entry("k2", 40))
+    store.put(1, (16, 24, False), _Entry("k1", 90))                      # the other family: counted on its own, evicts nothing
+    assert store.slots_of(1) == [a, (16, 24, False)] and store.slots_of(2) == [a] and store.nbytes() == 170
+    assert store.get(1, a, "k1") is not None                             # refreshes recency: net 2's entry is now the oldest
+    assert store.get(1, a, "other key") is None and store.get(3, a, "k1") is None
+    store.put(1, conv2, _Entry("k1", 40))                                # 120 > 100: the oldest split entry goes, whichever net
+    assert store.slots_of(2) == [] and store.slots_of(1) == [(16, 24, False), a, conv2]
+    store.put(2, b, _Entry("k2", 100))                                   # fills the cap alone: every other split entry goes
+    assert store.slots_of(1) == [(16, 24, False)] and store.slots_of(2) == [b]
+    store.put(2, (24, 36, False), _Entry("k2", 20))                      # 110 > 100 in the fp32 family: net 1's entry goes
+    assert store.slots_of(1) == [] and store.slots_of(2) == [b, (24, 36, False)]
+    # stale entries: only those of the one net whose key differs
+    store.entries.clear()
+    store.put(1, a, _Entry("old", 10))
+    store.put(1, conv2, _Entry("new", 10))
+    store.put(2, a, _Entry("old", 10))
+    store.drop_stale(1, "new")
+    assert store.slots_of(1) == [conv2] and store.slots_of(2) == [a]
+    view = _SpectraView(store, 1)
+    assert len(view) == 1 and conv2 in view and a not in view and list(view) == [conv2]
+    assert [e.key for e in view.values()] == ["new"] and len(_SpectraView(store, 2)) == 1
+    store.drop_net(2)
+    assert store.slots_of(2) == [] and list(view) == [conv2]
+    view.clear()
+    assert len(view) == 0 and store.nbytes() == 0
+
+
+def test_head_module_still_exports_what_moved():
+    from os2d_amd import _lib
+    from os2d_amd.modeling import device_buffers, head, spectra
+    for name in ("release_workspaces", "_WORKSPACES", "STATUS_SLOTS", "workspace_cap_bytes"):
+        assert getattr(head, name) is getattr(device_buffers, name), name
+    for name in ("spectra_cache_cap_bytes", "split_rows_f16"):
+        assert getattr(head, name) is getattr(spectra, name), name
+    assert head._lib is _lib and head.FFT_MIN_PAIRS == 7
+    for name in ("build_os2d_head_creator", "TransformationNet", "Os2dHead", "Os2dHeadCreator", "_prepare_class_maps"):
+        assert getattr(head, name).__module__ == "os2d_amd.modeling.head", name
+
+
+def test_fp32_twiddle_tables_are_the_rounded_float64_ones():
+    """The in-LDS FFTs take fp32 tables that were first built as -2 pi m / n; the product now rounds its float64 table
+    m * (-2 pi / n).  For every size their planner can return (2^a 3^b, 42, 84) the two give the same fp32 bits."""
+    import math
+    from os2d_amd.modeling.spectra import transform_sizes, twiddles64
+    sizes = {2 ** a * 3 ** b for a in range(11) for b in range(7) if 2 ** a * 3 ** b <= 1024} | {42, 84}
+    planned = {n for h in range(1, 330, 3) for w in (1, 40, 80, 131, 209) for n in transform_sizes(h, w, False)[:2]}
+    planned |= {n for w in range(1, 330, 3) for h in (1, 30, 60, 97, 157) for n in transform_sizes(h, w, False)[:2]}
+    assert planned <= sizes
+    for n in sorted(sizes):
+        m = torch.arange(n, dtype=torch.float64)
+        ang = -2.0 * math.pi * m / n
+        assert torch.equal(twiddles64(n, "cpu").float(), torch.stack([torch.cos(ang), torch.sin(ang)], 1).float()), n

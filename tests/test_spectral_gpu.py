@@ -1,8 +1,8 @@
 """GPU: building blocks of the frequency-domain form of the 7x7 TransformNet layer (os2d_amd/csrc/spectral.hip)."""
-import numpy as np
 import pytest
 import torch
 
+from freq_util import dft_sizes, fft_sizes, fft_tiles, shb_decode, twiddles
 from os2d_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -68,29 +68,6 @@ def test_spectral_gemm_full_size_timing(device):
 
 
 # ------------------------------------------------------------------------------------------------ the transforms
-def twiddles(n, device):
-    m = torch.arange(n, dtype=torch.float64)
-    ang = -2.0 * np.pi * m / n
-    return torch.stack([torch.cos(ang), torch.sin(ang)], 1).float().to(device).contiguous()     # exp(-2 pi i m / n)
-
-
-def fft_sizes(H, W):
-    import ctypes
-    lib = _lib.load()
-    P, Q, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(lib.os2d_fft_sizes(H, W, ctypes.byref(P), ctypes.byref(Q), ctypes.byref(nb)), "os2d_fft_sizes")
-    return P.value, Q.value, nb.value
-
-
-def fft_tiles(H, W):
-    """(TY, TX, TH, TW): the overlap-save tiling of maps beyond the in-LDS transform (1, 1, H, W for the others)."""
-    import ctypes
-    lib = _lib.load()
-    v = [ctypes.c_int() for _ in range(4)]
-    _lib.check(lib.os2d_fft_tiles(H, W, *[ctypes.byref(x) for x in v]), "os2d_fft_tiles")
-    return tuple(x.value for x in v)
-
-
 def y_quads_to_rows(Yq, NBT, Cout, nbins):
     """Y [nbins/4, NBT, Cout, 4, 2] (OS2D_SPECTRA_QUADS, what os2d_spectral_gemm_f16 writes) -> [NBT, Cout, nbins, 2]."""
     return Yq.view(nbins // 4, NBT, Cout, 4, 2).permute(1, 2, 0, 3, 4).reshape(NBT, Cout, nbins, 2).contiguous()
@@ -211,16 +188,11 @@ def test_fft_inverse_matches_torch_fft_and_epilogue(H, W, NB, device):
     tq, tp, Yd, bpd = twiddles(Q, device), twiddles(P, device), Y.to(device), bp.to(device)
     _lib.check(lib.os2d_fft_inverse(_lib.ptr(Yd), _lib.ptr(bpd), _lib.ptr(out), _lib.ptr(tq), _lib.ptr(tp), NB, Cout, H, W,
                                     _lib.ptr(status), _lib.current_stream(device)), "os2d_fft_inverse")
-    plane = lib.os2d_plane_floats(H, W)
-    Ws, base = W + 3, (3 * (W + 3) + 3 + 3) // 4 * 4
-    units = out.view(torch.float16).view(NB, Cout // 8, 2, plane, 8).float().cpu()
-    val = (units[:, :, 0] + units[:, :, 1]).permute(0, 1, 3, 2).reshape(NB, Cout, plane)          # [NB,Cout,PLANE] scaled values
-    got = val[:, :, base:base + H * Ws].reshape(NB, Cout, H, Ws)[..., :W] / torch.exp2(oexp.float()).view(1, -1, 1, 1)
+    val, border = shb_decode(out, NB, Cout, H, W)                                                  # scaled values
+    got = val.cpu() / torch.exp2(oexp.double()).view(1, -1, 1, 1)
     ref = torch.relu(y_true + bias.double().view(1, -1, 1, 1))
-    assert float((got.double() - ref).abs().max()) < 2e-6 * fmax
-    border = val.clone()
-    border[:, :, base:base + H * Ws].view(NB, Cout, H, Ws)[..., :W] = 0
-    assert float(border.abs().max()) == 0.0
+    assert float((got - ref).abs().max()) < 2e-6 * fmax
+    assert border == 0.0
     assert int(status.item()) == 0
 
 
@@ -278,10 +250,7 @@ def test_device_built_weight_spectra_match_torch_fft(H, W, device):
     assert float(got[:, :, P * V:].abs().max()) == 0.0 if nbins > P * V else True
     # ---- split-fp16 layout [g][half][ks][j][grp][hi|lo][o][c4, (re, im)] + 128 row scales, for the transform size and the bin
     # order (bin = v * P + u) of the matrix-product transforms (os2d_dft_sizes)
-    import ctypes
-    cP, cQ, cN = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(_lib.load().os2d_dft_sizes(H, W, ctypes.byref(cP), ctypes.byref(cQ), ctypes.byref(cN), None), "os2d_dft_sizes")
-    P, Q, nbins = cP.value, cQ.value, cN.value
+    P, Q, nbins, _ = dft_sizes(H, W)
     V, G = Q // 2 + 1, nbins // 8
     assert P % 4 == 0 and Q % 2 == 0 and nbins % 8 == 0
     k = torch.zeros(128, 225, P, Q, dtype=torch.float64, device=device)
@@ -334,16 +303,6 @@ def test_weight_spectra_miss_cost_is_bounded(device):
     assert torch.equal(rebuilt[0], keep)
     print("weight spectra for 64 x 84: miss {:.1f} ms, hit {:.3f} ms, {:.0f} MB".format(miss * 1e3, hit * 1e3, keep.numel() / 1e6))
     assert miss < 0.5 and hit < 0.002        # a miss builds 654 MB of spectra on the device (~5 - 20 ms), a hit is a dictionary lookup
-
-
-def dft_sizes(H, W):
-    """(P, Q, nbins, (TY, TX, TH, TW, window rows, window columns)) of the matrix-product transforms (precision "fftx3")."""
-    import ctypes
-    lib = _lib.load()
-    P, Q, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    t = (ctypes.c_int * 6)()
-    _lib.check(lib.os2d_dft_sizes(H, W, ctypes.byref(P), ctypes.byref(Q), ctypes.byref(nb), t), "os2d_dft_sizes")
-    return P.value, Q.value, nb.value, tuple(t)
 
 
 @pytest.mark.parametrize("H,W,NB", [(11, 13, 5), (30, 40, 70)])

@@ -23,6 +23,7 @@ REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, REPO)
 from os2d_amd.modeling import head as head_mod  # noqa: E402
 from os2d_amd.modeling.box_coder import feature_map_size_c4  # noqa: E402
+from os2d_amd.modeling.spectra import transform_sizes  # noqa: E402
 from os2d_amd.structures.feature_map import FeatureMapSize  # noqa: E402
 from os2d_amd.utils import synthetic  # noqa: E402
 
@@ -67,14 +68,7 @@ def main():
             fm = feature_map_size_c4(FeatureMapSize(w=int(w * s), h=int(h * s)))
             lv.append((fm.h, fm.w))
         maps.append(lv)
-    lib = head_mod._lib.load()
-    import ctypes
-    tsizes = set()
-    for lv in maps:
-        for h, w in lv:
-            p, q, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-            lib.os2d_dft_sizes(h, w, ctypes.byref(p), ctypes.byref(q), ctypes.byref(nb), None)    # the default precision's planner
-            tsizes.add((p.value, q.value))
+    tsizes = {transform_sizes(h, w, True)[:2] for lv in maps for h, w in lv}          # the default precision's planner
     # features per distinct map size (the content does not matter for the timing)
     feats = {}
     for lv in maps:

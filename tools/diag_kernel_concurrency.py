@@ -4,13 +4,13 @@ with the same launches run one after the other."""
 import os, sys, ctypes
 import torch
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
+sys.path.insert(0, REPO)
 from os2d_amd import _lib
-from test_spectral_gpu import twiddles, fft_sizes
+from os2d_amd.modeling.spectra import transform_sizes, twiddles64
 lib = _lib.load(); dev = torch.device("cuda:0")
 H, W, NB, C, Cout, NS = 48, 64, 128, 225, 128, 7
-P, Q, nbins = fft_sizes(H, W)
-tq, tp = twiddles(Q, dev), twiddles(P, dev)
+P, Q, nbins, _ = transform_sizes(H, W, False)
+tq, tp = twiddles64(Q, dev).float(), twiddles64(P, dev).float()
 g = torch.Generator().manual_seed(0)
 streams = [torch.cuda.Stream(device=dev) for _ in range(NS)]
 corr = [torch.randn(NB, C, H * W, generator=g).to(dev) for _ in range(NS)]

@@ -9,6 +9,7 @@ sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
 import util
 from os2d_amd import _lib
 from os2d_amd.engine.pyramid import level_stream
+from os2d_amd.modeling.spectra import transform_sizes
 from os2d_amd.utils import synthetic
 lib = _lib.load(); dev = torch.device("cuda:0")
 H, W, NS, B = 48, 64, 7, 128
@@ -16,10 +17,9 @@ state = synthetic.make_transform_net_state(6, seed=1)
 fm = synthetic.make_feature_map(1024, H, W, seed=102).to(dev)
 base = [c.to(dev) for c in synthetic.make_class_feature_maps(8, 1024, seed=7000)]
 creator = util.make_head_creator(6, True, state, dev)
-P_, Q_, nb_ = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-lib.os2d_fft_sizes(H, W, ctypes.byref(P_), ctypes.byref(Q_), ctypes.byref(nb_))
+nb_ = transform_sizes(H, W, False)[2]
 plane = lib.os2d_plane_floats(H, W)
-sizes = {0: B * 225 * H * W * 4, 1: B * H * W * 4, 2: B * 225 * nb_.value * 8, 3: B * 128 * nb_.value * 8, 4: B * 128 * plane * 4, 5: B * 64 * plane * 4, 6: B * 6 * H * W * 4}
+sizes = {0: B * 225 * H * W * 4, 1: B * H * W * 4, 2: B * 225 * nb_ * 8, 3: B * 128 * nb_ * 8, 4: B * 128 * plane * 4, 5: B * 64 * plane * 4, 6: B * 6 * H * W * 4}
 names = {0: "corr", 1: "invn", 2: "xspec", 3: "yspec", 4: "h1", 5: "h2", 6: "params"}
 with torch.no_grad():
     head = creator.create_os2d_head([base[b % 8] for b in range(B)])

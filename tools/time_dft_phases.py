@@ -12,10 +12,8 @@ import torch
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
 from os2d_amd import _lib  # noqa: E402
-from test_dft_gpu import matrices  # noqa: E402
-from test_spectral_gpu import dft_sizes  # noqa: E402
+from os2d_amd.modeling.spectra import build_dft_matrices, transform_sizes  # noqa: E402
 
 NB = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 H = int(sys.argv[2]) if len(sys.argv) > 2 else 60
@@ -23,10 +21,10 @@ W = int(sys.argv[3]) if len(sys.argv) > 3 else 80
 lib = _lib.load()
 raw = ctypes.CDLL(_lib.lib_path())
 dev = torch.device("cuda:0")
-P, Q, nbins, tiles = dft_sizes(H, W)
+P, Q, nbins, tiles = transform_sizes(H, W, True)
 T = tiles[0] * tiles[1]
 cpad = lib.os2d_dft_channel_stride(225)
-mats = matrices(P, Q, dev)
+mats = build_dft_matrices(P, Q, dev)
 corr = torch.rand(NB, 225, H, W, device=dev)
 inv = torch.rand(NB, H, W, device=dev) * 0.1
 X = torch.empty(nbins // 4, NB * T, cpad, 4, 2, device=dev)

@@ -3,14 +3,14 @@
 import os, sys, time
 import torch
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, "tests"))
+sys.path.insert(0, REPO)
 from os2d_amd import _lib
-from test_spectral_gpu import twiddles, fft_sizes
+from os2d_amd.modeling.spectra import transform_sizes, twiddles64
 lib = _lib.load(); dev = torch.device("cuda:0")
 NB = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 H, W, C, Cout = 60, 80, 225, 128
-P, Q, nbins = fft_sizes(H, W)
-tq, tp = twiddles(Q, dev), twiddles(P, dev)
+P, Q, nbins, _ = transform_sizes(H, W, False)
+tq, tp = twiddles64(Q, dev).float(), twiddles64(P, dev).float()
 corr = torch.randn(NB, C, H * W, device=dev); inv = torch.rand(NB, H * W, device=dev)
 X = torch.empty(C, NB, nbins, 2, device=dev); Y = torch.randn(NB, Cout, nbins, 2, device=dev)
 Wsp = torch.randn(lib.os2d_spectral_weight_bytes(C, Cout, nbins) // 4, device=dev)

@@ -12,6 +12,7 @@ import torch
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, REPO)
 import bench  # noqa: E402
+from os2d_amd.modeling.spectra import transform_sizes  # noqa: E402
 from os2d_amd.utils import synthetic  # noqa: E402
 
 classes = int(sys.argv[1]) if len(sys.argv) > 1 else 128
@@ -23,9 +24,7 @@ names = ["corr", "conv1", "conv2", "conv3", "sample", "fwd", "gemm", "inv"]
 rows = []
 for i, (h, wd) in enumerate(bench.LEVEL_HW):
     fm = synthetic.make_feature_map(bench.C_FEAT, h, wd, seed=100 + i).to(dev)
-    P, Q, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    t6 = (ctypes.c_int * 6)()
-    lib.os2d_dft_sizes(h, wd, ctypes.byref(P), ctypes.byref(Q), ctypes.byref(nb), t6)
+    P, Q, nb, t6 = transform_sizes(h, wd, True)
     with torch.no_grad():
         for _ in range(2):
             w.head(fm)
@@ -42,7 +41,7 @@ for i, (h, wd) in enumerate(bench.LEVEL_HW):
             L.check(lib.os2d_prof_event_elapsed_ms(evs[a], evs[b], ctypes.byref(ms)), "elapsed")
             acc[k] += ms.value / steps
     total = sum(acc[:5])
-    rows.append({"level": [h, wd], "locations": h * wd, "transform": [P.value, Q.value], "tiles": [t6[0], t6[1]], "bins_total": nb.value * t6[0] * t6[1],
+    rows.append({"level": [h, wd], "locations": h * wd, "transform": [P, Q], "tiles": [t6[0], t6[1]], "bins_total": nb * t6[0] * t6[1],
                  "ms": {n: round(v, 4) for n, v in zip(names, acc)}, "total_ms": round(total, 4)})
 ref = next(r for r in rows if r["level"] == [60, 80])
 print("level      loc  transform tiles   total | corr   fwd    gemm   inv    conv2  conv3  sample | per-location cost relative to 60x80: total corr fwd gemm inv conv2")
