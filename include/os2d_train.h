@@ -138,6 +138,53 @@ int os2d_train_objective_backward(const float* grad_loss, const float* loc_preds
                                   float localization_weight, float* dloc_preds, float* dcls_preds, float* dcls_preds_for_neg,
                                   void* stream);
 
+/* ---- os2d_train_assign_targets with a box transform chain (hard-patch mining: the level's anchors are compared with ground
+ * truth given in the original image).  The chain is op_kinds [nops], op_args [nops][2] on the HOST, OS2D_BOX_OP_* of os2d_hip.h
+ * (1 scale, 2 horizontal flip, 3 vertical flip, 4 shift), at most OS2D_BOX_MAX_OPS (6) entries, applied op by op with one
+ * rounding per product / difference.
+ *   mode 0 (reference box_coder.py:352-354): the anchor goes through the chain before the IoU, clip_to_min_size(1) and encode_boxes;
+ *   mode 1 (reference box_coder.py:250-254): the box is decoded from loc_scores against the plain anchor, then the decoded box
+ *           and the anchor both go through the chain.
+ * Everything else as os2d_train_assign_targets, whose kernel this shares.                                                  */
+int os2d_train_assign_targets_ops(int mode, const float* gt_boxes, const int* gt_labels, const unsigned char* gt_difficult,
+                                  const int* image_offsets, int num_boxes, const float* loc_scores, int A, int B, int H, int W, int stride,
+                                  int rec_field, float iou_high, float iou_low, int nops, const int* op_kinds, const float* op_args,
+                                  float* loc_targets, long long* cls_targets, float* ious_anchor, float* ious_anchor_corrected,
+                                  void* stream);
+
+/* ==== Hard-patch mining (csrc_train/mining.hip; reference os2d/modeling/box_coder.py:78-166 and os2d/engine/train.py:240-325). */
+#define OS2D_MINE_MAX_LEVELS 8
+#define OS2D_MINE_MAX_K 64
+#define OS2D_MINE_INDEX_INTS 3     /* level, label, anchor */
+#define OS2D_MINE_VALUE_FLOATS 19  /* crop xyxy, anchor xyxy, 8 corner values, cls_loss, loc_loss, cls_pred */
+
+/* ---- get_box_to_cut_anchor for one level of H x W anchors (row-major, stride `stride`, size `box_size`) on an image of
+ * img_w x img_h: per anchor the stride-aligned crop window of crop_w x crop_h around it (floored to the stride where its corner
+ * is positive, else 0; shifted left / up by a whole number of strides when it leaves the image and that fits, else the full width
+ * / height from 0) and the anchor box, both through the chain (as above; nops = 0: none).  crop_boxes, anchor_boxes [H*W,4] xyxy. */
+int os2d_train_crop_boxes(int H, int W, int stride, int box_size, int img_w, int img_h, int crop_w, int crop_h, int nops,
+                          const int* op_kinds, const float* op_args, float* crop_boxes, float* anchor_boxes, void* stream);
+
+/* ---- the K hardest patches per (image, role) over a pyramid of L <= OS2D_MINE_MAX_LEVELS levels.  HOST arrays: level_hw [L][2]
+ * (H, W), level_img [L][2] (w, h), level_row_stride [L], op_counts [L], op_kinds [L][OS2D_BOX_MAX_OPS], op_args
+ * [L][OS2D_BOX_MAX_OPS][2], and five arrays of L DEVICE pointers: cls_loss, loc_loss, flags (rows of HW_l elements, one per
+ * (image, label), level_row_stride[l] >= HW_l elements apart: the level's slice of what os2d_train_objective_forward wrote for
+ * the merged pyramid, or a dense [A,B,HW_l]), cls_preds [A,B,HW_l] and corners [A,B,8,HW_l] (dense; `corners` may be NULL).
+ * Roles: 0 neg (flag 2, score cls_loss), 1 pos (flag 1, cls_loss), 2 pos_loc (flag 4, loc_loss).  For every (image, role): greedy
+ * NMS at iou_thr over the crop windows (os2d_train_crop_boxes) of the flagged candidates by decreasing score, equal scores in
+ * increasing (level, label, anchor) order, stopped after K <= OS2D_MINE_MAX_K kept; a candidate whose score is not finite is
+ * never selected.  This is greedy NMS over ALL candidates at once, at any number of them.
+ * Outputs: out_count [A,3]; out_index [A,3,K,3] (level, label, anchor; -1 in unused records); out_values [A,3,K,19]: crop xyxy,
+ * anchor xyxy, the 8 corner values taken as two boxes through the level's chain (zeros without `corners`), cls_loss, loc_loss
+ * and cls_preds of the element (zeros in unused records).  workspace: os2d_train_mine_select_workspace_bytes bytes (0 = bad
+ * shape), 16-byte aligned.  One launch, A * 3 work-groups; no atomics: two runs give the same bits.                         */
+size_t os2d_train_mine_select_workspace_bytes(int A, int B, int L, const int* level_hw);
+int os2d_train_mine_select(int A, int B, int L, const int* level_hw, const int* level_img, const int* level_row_stride, int stride,
+                           int box_size, const int* op_counts, const int* op_kinds, const float* op_args, const float* const* cls_loss,
+                           const float* const* loc_loss, const unsigned char* const* flags, const float* const* cls_preds,
+                           const float* const* corners, int crop_w, int crop_h, float iou_thr, int K, int* out_count, int* out_index,
+                           float* out_values, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

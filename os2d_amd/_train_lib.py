@@ -30,6 +30,10 @@ SIGNATURES = {
     "os2d_train_corr_backward": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "os2d_train_class_backward": (_i, [_p, _p, _i, _i, _p, _p, _p, _sz, _p]),
     "os2d_train_assign_targets": (_i, [_i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p]),
+    "os2d_train_assign_targets_ops": (_i, [_i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "os2d_train_crop_boxes": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "os2d_train_mine_select_workspace_bytes": (_sz, [_i, _i, _i, _p]),
+    "os2d_train_mine_select": (_i, [_i, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _p, _p, _p, _p, _sz, _p]),
     "os2d_train_objective_workspace_floats": (_sz, [_i, _i, _i]),
     "os2d_train_objective_forward": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _f, _d, _p, _p, _p, _p, _p,
                                           _p, _sz, _p]),

@@ -2,6 +2,7 @@
 //
 //   os2d_train_assign_targets      reference box_coder.py encode (mode 0) / remap_anchor_targets (mode 1): one thread per
 //                                  (image, label, anchor) walks the boxes of its image that carry its label.
+//   os2d_train_assign_targets_ops  the same kernel body with a box transform chain on the anchors (hard-patch mining).
 //   os2d_train_objective_forward   reference objective.py:141-277 as a short chain of launches (see the ABI function).
 //   os2d_train_objective_backward  one kernel: d loc_preds, d cls_preds, d cls_preds_for_neg.
 //
@@ -18,6 +19,7 @@
 #include <stdio.h>
 
 #include "../../include/os2d_train.h"
+#include "../csrc/detect_common.h"
 #include "../csrc_shared/abi_common.h"
 
 namespace {
@@ -156,6 +158,9 @@ __device__ __forceinline__ int match_index(float best, int best_i, bool difficul
   return idx;
 }
 
+// OPS: the anchor (mode 0), or the decoded box and the anchor (mode 1), go through the box-op chain `ops` before anything is
+// compared (os2d_train_assign_targets_ops); without it the chain is never touched and the code is what it was.
+template <bool OPS>
 __global__ __launch_bounds__(OBJ_THREADS) void assign_targets_kernel(int mode, const float* __restrict__ gt_boxes,
                                                                     const int* __restrict__ gt_labels,
                                                                     const unsigned char* __restrict__ gt_difficult,
@@ -163,7 +168,7 @@ __global__ __launch_bounds__(OBJ_THREADS) void assign_targets_kernel(int mode, c
                                                                     const float* __restrict__ loc_scores, int B, int H, int W, float stride,
                                                                     float box_size, float high, float low, float* __restrict__ loc_targets,
                                                                     long long* __restrict__ cls_targets, float* __restrict__ ious_anchor,
-                                                                    float* __restrict__ ious_corrected) {
+                                                                    float* __restrict__ ious_corrected, Os2dBoxOps ops) {
   const int HW = H * W;
   const int p = blockIdx.x * OBJ_THREADS + threadIdx.x;
   if (p >= HW) return;
@@ -172,8 +177,13 @@ __global__ __launch_bounds__(OBJ_THREADS) void assign_targets_kernel(int mode, c
   const size_t l0 = ((size_t)ab * 4) * HW + p;
   // the anchor, closed form (row-major cells, centre (x+0.5)*stride)
   const float cx = ((float)(p % W) + 0.5f) * stride, cy = ((float)(p / W) + 0.5f) * stride;
-  const float ax1 = cx - 0.5f * box_size, ay1 = cy - 0.5f * box_size, ax2 = cx + 0.5f * box_size, ay2 = cy + 0.5f * box_size;
-  const float area_anchor = (ax2 - ax1) * (ay2 - ay1);
+  float ax1 = cx - 0.5f * box_size, ay1 = cy - 0.5f * box_size, ax2 = cx + 0.5f * box_size, ay2 = cy + 0.5f * box_size;
+  if constexpr (OPS) {
+    if (mode == 0) {   // reference box_coder.py:352-354: the transformed anchors are matched, clipped and encoded
+      const float4 t = os2d_apply_box_ops(make_float4(ax1, ay1, ax2, ay2), ops);
+      ax1 = t.x, ay1 = t.y, ax2 = t.z, ay2 = t.w;
+    }
+  }
   float dx1 = 0.f, dy1 = 0.f, dx2 = 0.f, dy2 = 0.f, area_dec = 0.f;
   if (mode == 1) {   // BoxCoder.decode_single, weights (10, 10, 5, 5)
     const float clipv = 4.135166556742356f;   // log(1000 / 16)
@@ -187,8 +197,15 @@ __global__ __launch_bounds__(OBJ_THREADS) void assign_targets_kernel(int mode, c
     dy1 = pcy - 0.5f * ph;
     dx2 = pcx + 0.5f * pw;
     dy2 = pcy + 0.5f * ph;
+    if constexpr (OPS) {   // reference box_coder.py:250-254: decoded against the plain anchor, then both through the chain
+      const float4 d = os2d_apply_box_ops(make_float4(dx1, dy1, dx2, dy2), ops);
+      dx1 = d.x, dy1 = d.y, dx2 = d.z, dy2 = d.w;
+      const float4 t = os2d_apply_box_ops(make_float4(ax1, ay1, ax2, ay2), ops);
+      ax1 = t.x, ay1 = t.y, ax2 = t.z, ay2 = t.w;
+    }
     area_dec = (dx2 - dx1) * (dy2 - dy1);
   }
+  const float area_anchor = (ax2 - ax1) * (ay2 - ay1);
   int lo = image_offsets[a], hi = image_offsets[a + 1];
   lo = max(0, min(lo, num_boxes));
   hi = max(lo, min(hi, num_boxes));
@@ -608,6 +625,44 @@ bool dims_ok(int A, int B, int HW) {
   return A >= 1 && B >= 1 && HW >= 1 && (long long)A * B <= 65535 && (long long)A * B * HW <= (1ll << 28);
 }
 
+// both entry points: `ops` NULL = the plain anchors (os2d_train_assign_targets)
+int assign_targets(const char* what, int mode, const float* gt_boxes, const int* gt_labels, const unsigned char* gt_difficult,
+                   const int* image_offsets, int num_boxes, const float* loc_scores, int A, int B, int H, int W, int stride, int rec_field,
+                   float iou_high, float iou_low, const Os2dBoxOps* ops, float* loc_targets, long long* cls_targets, float* ious_anchor,
+                   float* ious_anchor_corrected, void* stream) {
+  if (mode != 0 && mode != 1) {
+    os2d_set_error("%s: unknown mode %d (0 = encode, 1 = remap)", what, mode);
+    return -1;
+  }
+  if (H < 1 || W < 1 || (long long)H * W > (1ll << 28) || !dims_ok(A, B, H * W)) {
+    os2d_set_error("%s: bad shape A=%d B=%d H=%d W=%d", what, A, B, H, W);
+    return -1;
+  }
+  if (stride < 1 || rec_field + 14 * stride < 1 || num_boxes < 0) {
+    os2d_set_error("%s: bad stride=%d rec_field=%d num_boxes=%d", what, stride, rec_field, num_boxes);
+    return -1;
+  }
+  if (!image_offsets || !cls_targets || (num_boxes > 0 && (!gt_boxes || !gt_labels || !gt_difficult))) {
+    os2d_set_error("%s: null pointer", what);
+    return -1;
+  }
+  if (mode == 0 ? !loc_targets : (!loc_scores || !ious_anchor || !ious_anchor_corrected)) {
+    os2d_set_error("%s: null pointer for mode %d", what, mode);
+    return -1;
+  }
+  const int HW = H * W;
+  const dim3 grid((HW + OBJ_THREADS - 1) / OBJ_THREADS, A * B);
+  const float fs = (float)stride, box = (float)(rec_field + 14 * stride);
+  if (ops)
+    assign_targets_kernel<true><<<grid, OBJ_THREADS, 0, os2d_stream(stream)>>>(mode, gt_boxes, gt_labels, gt_difficult, image_offsets, num_boxes,
+                                                                    loc_scores, B, H, W, fs, box, iou_high, iou_low, loc_targets,
+                                                                    cls_targets, ious_anchor, ious_anchor_corrected, *ops);
+  else
+    assign_targets_kernel<false><<<grid, OBJ_THREADS, 0, os2d_stream(stream)>>>(mode, gt_boxes, gt_labels, gt_difficult, image_offsets, num_boxes,
+                                                                     loc_scores, B, H, W, fs, box, iou_high, iou_low, loc_targets,
+                                                                     cls_targets, ious_anchor, ious_anchor_corrected, Os2dBoxOps{});
+  return os2d_launched(what);
+}
 }  // namespace
 
 extern "C" {
@@ -616,32 +671,22 @@ int os2d_train_assign_targets(int mode, const float* gt_boxes, const int* gt_lab
                               const int* image_offsets, int num_boxes, const float* loc_scores, int A, int B, int H, int W, int stride,
                               int rec_field, float iou_high, float iou_low, float* loc_targets, long long* cls_targets,
                               float* ious_anchor, float* ious_anchor_corrected, void* stream) {
-  if (mode != 0 && mode != 1) {
-    os2d_set_error("os2d_train_assign_targets: unknown mode %d (0 = encode, 1 = remap)", mode);
+  return assign_targets("os2d_train_assign_targets", mode, gt_boxes, gt_labels, gt_difficult, image_offsets, num_boxes, loc_scores, A, B, H, W,
+                        stride, rec_field, iou_high, iou_low, nullptr, loc_targets, cls_targets, ious_anchor, ious_anchor_corrected, stream);
+}
+
+int os2d_train_assign_targets_ops(int mode, const float* gt_boxes, const int* gt_labels, const unsigned char* gt_difficult,
+                                  const int* image_offsets, int num_boxes, const float* loc_scores, int A, int B, int H, int W, int stride,
+                                  int rec_field, float iou_high, float iou_low, int nops, const int* op_kinds, const float* op_args,
+                                  float* loc_targets, long long* cls_targets, float* ious_anchor, float* ious_anchor_corrected,
+                                  void* stream) {
+  Os2dBoxOps ops;
+  if (!os2d_box_ops_from(op_kinds, op_args, nops, &ops)) {
+    os2d_set_error("os2d_train_assign_targets_ops: bad box-op chain (nops=%d, at most %d ops of kind 1..4)", nops, OS2D_BOX_MAX_OPS);
     return -1;
   }
-  if (H < 1 || W < 1 || (long long)H * W > (1ll << 28) || !dims_ok(A, B, H * W)) {
-    os2d_set_error("os2d_train_assign_targets: bad shape A=%d B=%d H=%d W=%d", A, B, H, W);
-    return -1;
-  }
-  if (stride < 1 || rec_field + 14 * stride < 1 || num_boxes < 0) {
-    os2d_set_error("os2d_train_assign_targets: bad stride=%d rec_field=%d num_boxes=%d", stride, rec_field, num_boxes);
-    return -1;
-  }
-  if (!image_offsets || !cls_targets || (num_boxes > 0 && (!gt_boxes || !gt_labels || !gt_difficult))) {
-    os2d_set_error("os2d_train_assign_targets: null pointer");
-    return -1;
-  }
-  if (mode == 0 ? !loc_targets : (!loc_scores || !ious_anchor || !ious_anchor_corrected)) {
-    os2d_set_error("os2d_train_assign_targets: null pointer for mode %d", mode);
-    return -1;
-  }
-  const int HW = H * W;
-  const dim3 grid((HW + OBJ_THREADS - 1) / OBJ_THREADS, A * B);
-  assign_targets_kernel<<<grid, OBJ_THREADS, 0, os2d_stream(stream)>>>(mode, gt_boxes, gt_labels, gt_difficult, image_offsets, num_boxes, loc_scores,
-                                                            B, H, W, (float)stride, (float)(rec_field + 14 * stride), iou_high,
-                                                            iou_low, loc_targets, cls_targets, ious_anchor, ious_anchor_corrected);
-  return os2d_launched("os2d_train_assign_targets");
+  return assign_targets("os2d_train_assign_targets_ops", mode, gt_boxes, gt_labels, gt_difficult, image_offsets, num_boxes, loc_scores, A, B, H,
+                        W, stride, rec_field, iou_high, iou_low, &ops, loc_targets, cls_targets, ious_anchor, ious_anchor_corrected, stream);
 }
 
 size_t os2d_train_objective_workspace_floats(int A, int B, int HW) {

@@ -76,6 +76,12 @@ class _ObjectiveFunction(torch.autograd.Function):
         return None, None, dloc, None, dcls, None, None, (dneg if need_neg else None)
 
 
+class PerAnchorLosses(OrderedDict):
+    """The reference's per-anchor dictionary of the patch-mining mode; ``flags`` carries the kernel's flag bytes (bits F_POS,
+    F_NEG, F_POSREG) the masks were made from, split like them - what os2d_train_mine_select reads."""
+    flags = None
+
+
 def _apply(*args):
     return _ObjectiveFunction.apply(*args)
 
@@ -165,7 +171,8 @@ class Os2dObjective(nn.Module):
         losses[neg_name] = detached[4]
         if not patch_mining_mode:
             return losses
-        per_anchor = OrderedDict()
+        per_anchor = PerAnchorLosses()
+        per_anchor.flags = torch.split(flags, pyramid_sizes, dim=2) if pyramid_sizes else flags
         per_anchor["pos_mask"] = (flags & F_POS) != 0
         per_anchor["neg_mask"] = (flags & F_NEG) != 0
         per_anchor["cls_loss"] = cls_loss

@@ -1,6 +1,7 @@
 """The training step on the HIP head (reference os2d/engine/train.py:47-113 and os2d/modeling/model.py:262-276): the forward
 with autograd through the head (os2d_amd/modeling/head_train.py), target remapping, the objective and the optimiser step.
-Data loading, hard-patch mining and the gradient all-reduce of a multi-device run are out of scope."""
+Hard-patch mining, which the reference's V2 recipe alternates with this step, is os2d_amd/engine/mining.py.  Data loading and the
+gradient all-reduce of a multi-device run are out of scope."""
 import math
 
 import torch

@@ -8,8 +8,15 @@
     Os2dBoxCoder.encode / encode_pyramid / encode_batch   reference box_coder.py:332-421   (os2d_train_assign_targets, mode 0)
     Os2dBoxCoder.remap_anchor_targets                     reference box_coder.py:234-300   (os2d_train_assign_targets, mode 1)
 
+    BoxGridGenerator.get_box_to_cut_anchor                reference box_coder.py:78-166    (os2d_train_crop_boxes)
+    Os2dBoxCoder.encode_transformed / encode_pyramid_transformed / remap_anchor_targets_transformed
+                                                          the same with the reference's box transforms (hard-patch mining,
+                                                          reference box_coder.py:250-254, 352-354; os2d_train_assign_targets_ops)
+
 The target side runs as one launch per call over every (image, label, anchor); the BoxLists are packed into four arrays on
-the host once per batch.  Box transforms in the target code (hard-patch mining) are out of scope.
+the host once per batch.  A box transform reaches the kernels as the chain ``trace_box_transform`` records; the reference-named
+``encode`` / ``encode_pyramid`` / ``remap_anchor_targets`` refuse transforms and name the ``_transformed`` methods
+(INTEGRATION.md section 7b).
 """
 import collections
 import weakref
@@ -228,6 +235,39 @@ class BoxGridGenerator(object):
 
     def create_strided_boxes_columnfirst(self, fm_size):
         return create_strided_boxes_columnfirst(fm_size, self.box_size, self.box_stride)
+
+    def get_box_to_cut_anchor(self, img_size, crop_size, fm_size, default_box_transform=None, device=None):
+        """reference box_coder.py:78-166 with os2d_train_crop_boxes: per anchor of the level the stride-aligned crop window of
+        ``crop_size`` around it that stays inside ``img_size``, and the anchor box, both through ``default_box_transform``.
+        -> (crop_boxes BoxList, anchor_boxes BoxList, anchor_index int64 [H*W]) on the HIP device (``device``: default the
+        current one).  A transform that is not a chain of BoxList.resize / transpose / crop raises ValueError."""
+        if self.box_size.w != self.box_size.h or self.box_stride.w != self.box_stride.h:
+            raise RuntimeError("anisotropic anchors are not supported")
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("get_box_to_cut_anchor runs on the HIP device only (no CPU fallback), got {}".format(device))
+        ops, out_size = traced_box_ops(default_box_transform, img_size)
+        tl = _train_lib.load()
+        HW = fm_size.h * fm_size.w
+        crops = torch.empty(HW, 4, dtype=torch.float32, device=device)
+        anchors = torch.empty(HW, 4, dtype=torch.float32, device=device)
+        _, kinds, args = _ops_tables([ops])
+        with torch.cuda.device(device):
+            _train_lib.check(tl.os2d_train_crop_boxes(fm_size.h, fm_size.w, int(self.box_stride.w), int(self.box_size.w), int(img_size.w),
+                                                      int(img_size.h), int(crop_size.w), int(crop_size.h), len(ops), kinds, args,
+                                                      _lib.ptr(crops), _lib.ptr(anchors), _lib.current_stream(device)),
+                             "os2d_train_crop_boxes")
+        return BoxList(crops, out_size), BoxList(anchors, out_size), torch.arange(HW, device=device)
+
+
+def traced_box_ops(transform, img_size):
+    """-> (box-op chain, output image size) of a box transform of the target / mining code, recorded by ``trace_box_transform``;
+    ValueError when the transform is not a chain of at most MAX_BOX_OPS BoxList.resize / transpose / crop calls."""
+    traced = trace_box_transform(transform, img_size)
+    if traced is None:
+        raise ValueError("the box transform is not a chain of at most {} BoxList.resize / transpose / crop calls: the HIP kernels "
+                         "cannot express it".format(MAX_BOX_OPS))
+    return traced[0], traced[2]
 
 
 def feature_map_size_c4(img_size):
@@ -690,7 +730,8 @@ class Os2dBoxCoder(object):
                   torch.tensor(offsets, dtype=torch.int32))
         return tuple(t.to(device, non_blocking=True) for t in packed) + (n,)
 
-    def _assign(self, mode, batch_boxes, fm, num_labels, device, loc_scores=None):
+    def _assign(self, mode, batch_boxes, fm, num_labels, device, loc_scores=None, ops=None):
+        """``ops``: None = the plain anchors (os2d_train_assign_targets), else a box-op chain (os2d_train_assign_targets_ops)."""
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("target assignment runs on the HIP device only (no CPU fallback), got {}".format(device))
@@ -705,12 +746,19 @@ class Os2dBoxCoder(object):
             outs = (None, torch.empty(A, num_labels, HW, dtype=torch.float32, device=device),
                     torch.empty(A, num_labels, HW, dtype=torch.float32, device=device))
             high, low = self.remap_classification_targets_iou_pos, self.remap_classification_targets_iou_neg
-        with torch.cuda.device(device):
-            _train_lib.check(tl.os2d_train_assign_targets(
-                mode, _lib.ptr(gt_boxes) if n else None, _lib.ptr(gt_labels) if n else None, _lib.ptr(gt_difficult) if n else None,
+        head = (mode, _lib.ptr(gt_boxes) if n else None, _lib.ptr(gt_labels) if n else None, _lib.ptr(gt_difficult) if n else None,
                 _lib.ptr(offsets), n, _lib.ptr(loc_scores), A, num_labels, fm.h, fm.w, self._stride, self._rec_field,
-                ctypes.c_float(high), ctypes.c_float(low), _lib.ptr(outs[0]), _lib.ptr(cls_targets), _lib.ptr(outs[1]),
-                _lib.ptr(outs[2]), _lib.current_stream(device)), "os2d_train_assign_targets")
+                ctypes.c_float(high), ctypes.c_float(low))
+        tail = (_lib.ptr(outs[0]), _lib.ptr(cls_targets), _lib.ptr(outs[1]), _lib.ptr(outs[2]), _lib.current_stream(device))
+        with torch.cuda.device(device):
+            if ops is None:
+                _train_lib.check(tl.os2d_train_assign_targets(*(head + tail)), "os2d_train_assign_targets")
+            else:
+                if len(ops) > MAX_BOX_OPS:
+                    raise ValueError("a box-op chain of {} entries: at most {} are supported".format(len(ops), MAX_BOX_OPS))
+                _, kinds, args = _ops_tables([ops])
+                _train_lib.check(tl.os2d_train_assign_targets_ops(*(head + (len(ops), kinds, args) + tail)),
+                                 "os2d_train_assign_targets_ops")
         return cls_targets, outs
 
     def encode_batch(self, batch_boxes, img_size, num_labels, device):
@@ -723,7 +771,7 @@ class Os2dBoxCoder(object):
         """reference box_coder.py:332-389: -> loc_targets [num_labels,4,HW] float32, cls_targets [num_labels,HW] int64 (1
         positive, 0 negative, -1 ignored), on the HIP device (that of ``boxes`` when it is there already)."""
         if default_box_transform is not None:
-            raise NotImplementedError("default_box_transform is not supported (hard-patch mining is out of scope)")
+            raise NotImplementedError("default_box_transform is not supported here: use encode_transformed")
         dev = boxes.bbox_xyxy.device if boxes.bbox_xyxy.is_cuda else torch.device("cuda", torch.cuda.current_device())
         loc_targets, cls_targets = self.encode_batch([boxes], img_size, num_labels, dev)
         return loc_targets[0], cls_targets[0]
@@ -731,7 +779,7 @@ class Os2dBoxCoder(object):
     def encode_pyramid(self, boxes, img_size_pyramid, num_labels, default_box_transform_pyramid=None):
         """reference box_coder.py:391-421: ``encode`` per pyramid level -> (list of loc_targets, list of cls_targets)."""
         if default_box_transform_pyramid is not None and any(t is not None for t in default_box_transform_pyramid):
-            raise NotImplementedError("default_box_transform_pyramid is not supported (hard-patch mining is out of scope)")
+            raise NotImplementedError("default_box_transform_pyramid is not supported here: use encode_pyramid_transformed")
         levels = [self.encode(boxes, img_size, num_labels) for img_size in img_size_pyramid]
         return [l[0] for l in levels], [l[1] for l in levels]
 
@@ -740,7 +788,7 @@ class Os2dBoxCoder(object):
         device -> cls_targets_remapped [A,B,HW] int64, ious_anchor, ious_anchor_corrected [A,B,HW] float32.  One launch,
         no host synchronisation.  The images of a batch share one size (they are one tensor)."""
         if box_reverse_transform is not None:
-            raise NotImplementedError("box_reverse_transform is not supported (hard-patch mining is out of scope)")
+            raise NotImplementedError("box_reverse_transform is not supported here: use remap_anchor_targets_transformed")
         if not (loc_scores.is_cuda and loc_scores.dtype == torch.float32):
             raise RuntimeError("remap_anchor_targets runs on the HIP device only (no CPU fallback)")
         A, B = loc_scores.shape[0], loc_scores.shape[1]
@@ -751,6 +799,64 @@ class Os2dBoxCoder(object):
             raise ValueError("the images of a batch must share one feature map size that matches loc_scores")
         cls_targets, outs = self._assign(1, batch_boxes, fm, B, loc_scores.device, loc_scores.detach().contiguous())
         return cls_targets, outs[1], outs[2]
+
+    # ---------------------------------------------------------------- targets under a box transform (hard-patch mining)
+    def encode_transformed(self, boxes, img_size, num_labels, default_box_transform=None, device=None):
+        """reference ``encode(..., default_box_transform=...)`` (box_coder.py:332-394): the anchors of ``img_size`` go through
+        the transform before they are matched with ``boxes``, clipped to a minimal size and encoded.  The transform is a chain
+        of BoxList.resize / transpose / crop calls (the reference's ``TransformList``) or a recorded chain of
+        (kind, ax, ay) tuples; anything else raises ValueError.  -> loc_targets [num_labels,4,HW], cls_targets [num_labels,HW]."""
+        ops = self._chain(default_box_transform, img_size)
+        if device is None:
+            device = boxes.bbox_xyxy.device if boxes.bbox_xyxy.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        cls_targets, outs = self._assign(0, [boxes], self.get_feature_map_size(img_size), num_labels, device, ops=ops)
+        return outs[0][0], cls_targets[0]
+
+    def encode_pyramid_transformed(self, boxes, img_size_pyramid, num_labels, default_box_transform_pyramid=None, device=None):
+        """reference ``encode_pyramid(..., default_box_transform_pyramid=...)`` (box_coder.py:396-422)."""
+        ts = default_box_transform_pyramid if default_box_transform_pyramid is not None else [None] * len(img_size_pyramid)
+        levels = [self.encode_transformed(boxes, s, num_labels, t, device=device) for s, t in zip(img_size_pyramid, ts)]
+        return [l[0] for l in levels], [l[1] for l in levels]
+
+    def remap_anchor_targets_transformed(self, loc_scores, batch_img_size, class_image_sizes, batch_boxes, box_reverse_transform=None):
+        """reference ``remap_anchor_targets(..., box_reverse_transform=...)`` (box_coder.py:234-303): the box decoded from
+        ``loc_scores`` against the plain anchor and the anchor itself go through the image's transform before they meet the
+        ground truth.  ``box_reverse_transform``: one entry per image.  One launch when the images share a chain (mining
+        handles one image at a time), else one per image; no host synchronisation."""
+        if not (loc_scores.is_cuda and loc_scores.dtype == torch.float32):
+            raise RuntimeError("remap_anchor_targets_transformed runs on the HIP device only (no CPU fallback)")
+        A, B = loc_scores.shape[0], loc_scores.shape[1]
+        if len(batch_boxes) != A or len(batch_img_size) != A:
+            raise ValueError("batch_boxes / batch_img_size must have one entry per image ({})".format(A))
+        ts = box_reverse_transform if box_reverse_transform is not None else [None] * A
+        if len(ts) != A:
+            raise ValueError("box_reverse_transform must have one entry per image ({})".format(A))
+        fm = self.get_feature_map_size(batch_img_size[0])
+        if any(self.get_feature_map_size(s) != fm for s in batch_img_size[1:]) or fm.h * fm.w != loc_scores.shape[3]:
+            raise ValueError("the images of a batch must share one feature map size that matches loc_scores")
+        chains = [self._chain(t, s) for t, s in zip(ts, batch_img_size)]
+        loc_scores = loc_scores.detach().contiguous()
+        if all(c == chains[0] for c in chains[1:]):
+            cls_targets, outs = self._assign(1, batch_boxes, fm, B, loc_scores.device, loc_scores, ops=chains[0])
+            return cls_targets, outs[1], outs[2]
+        parts = [self._assign(1, [batch_boxes[a]], fm, B, loc_scores.device, loc_scores[a:a + 1], ops=chains[a]) for a in range(A)]
+        return (torch.cat([p[0] for p in parts]), torch.cat([p[1][1] for p in parts]), torch.cat([p[1][2] for p in parts]))
+
+    @staticmethod
+    def _chain(transform, img_size):
+        """A transform of the target code as a box-op chain: a callable is traced, a sequence of (kind, ax, ay) is taken as it is."""
+        if isinstance(transform, (tuple, list)):
+            ops = tuple((int(k), float(ax), float(ay)) for k, ax, ay in transform)
+            if len(ops) > MAX_BOX_OPS or any(k not in (OP_SCALE, OP_HFLIP, OP_VFLIP, OP_SHIFT) for k, _, _ in ops):
+                raise ValueError("a box-op chain has at most {} entries of kind 1..4, got {}".format(MAX_BOX_OPS, ops))
+            return ops
+        return traced_box_ops(transform, img_size)[0]
+
+    @staticmethod
+    def apply_transform_to_corners(masked_transform_corners, transform, img_size):
+        """reference box_coder.py:439-446: corners [n,8] (x,y,x,y,x,y,x,y) go through the transform as two boxes each."""
+        ops = Os2dBoxCoder._chain(transform, img_size)
+        return apply_box_ops(masked_transform_corners.contiguous().view(-1, 4), ops).contiguous().view(-1, 8)
 
     @staticmethod
     def build_loc_targets(class_boxes, default_boxes):
