@@ -21,7 +21,7 @@ import torch
 
 from .. import _lib
 from .. import _train_lib
-from ..modeling.box_coder import MAX_BOX_OPS, Os2dBoxCoder, _ops_tables
+from ..modeling.box_ops import MAX_BOX_OPS, as_box_ops, ops_tables
 from ..structures.bounding_box import BoxList
 from ..structures.feature_map import FeatureMapSize
 
@@ -78,7 +78,7 @@ def mine_select(per_anchor, cls_scores_pyramid, corners_pyramid, img_size_pyrami
     if not (len(fm_sizes) == L and len(cls_scores_pyramid) == L and len(per_anchor["cls_loss"]) == L and len(per_anchor["loc_loss"]) == L):
         raise ValueError("every pyramid argument needs one entry per level ({})".format(L))
     transforms = list(box_transforms) if box_transforms is not None else [None] * L
-    chains = [Os2dBoxCoder._chain(t, s) for t, s in zip(transforms, img_size_pyramid)]     # ValueError for what cannot be expressed
+    chains = [as_box_ops(t, s) for t, s in zip(transforms, img_size_pyramid)]     # ValueError for what cannot be expressed
     flags_l = per_anchor["flags"] if "flags" in per_anchor else getattr(per_anchor, "flags", None)
     if flags_l is None:
         flags_l = _flags_of(per_anchor)
@@ -116,7 +116,7 @@ def mine_select(per_anchor, cls_scores_pyramid, corners_pyramid, img_size_pyrami
     c_hw = (ctypes.c_int * (2 * L))(*[v for fm in fm_sizes for v in (fm.h, fm.w)])
     c_img = (ctypes.c_int * (2 * L))(*[int(v) for s in img_size_pyramid for v in (s.w, s.h)])
     c_rows = (ctypes.c_int * L)(*rows)
-    c_counts, c_kinds, c_args = _ops_tables(chains, MAX_BOX_OPS)
+    c_counts, c_kinds, c_args = ops_tables(chains, MAX_BOX_OPS)
     arrays = {k: (ctypes.c_void_p * L)(*v) if v else None for k, v in ptrs.items()}
     nbytes = int(tl.os2d_train_mine_select_workspace_bytes(A, B, L, c_hw))
     if nbytes == 0:

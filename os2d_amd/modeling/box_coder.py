@@ -1,8 +1,10 @@
-"""Anchor grids and the decode side of the reference's box coder (os2d/modeling/box_coder.py) on the HIP library.
+"""Anchor grids and the reference's box coder (os2d/modeling/box_coder.py) on the HIP libraries: decode + NMS for inference,
+target assignment for training.
 
     create_strided_boxes_columnfirst / BoxGridGenerator   reference box_coder.py:16-76
     Os2dBoxCoder.build_boxes_from_loc_scores              reference box_coder.py:319-330   (os2d_decode_boxes)
     Os2dBoxCoder.decode_pyramid                           reference box_coder.py:448-536   (os2d_detect_level for one level,
+                                                                                            os2d_detect_pyramid for several,
                                                                                             os2d_decode_boxes + os2d_nms otherwise)
 
     Os2dBoxCoder.encode / encode_pyramid / encode_batch   reference box_coder.py:332-421   (os2d_train_assign_targets, mode 0)
@@ -14,12 +16,10 @@
                                                           reference box_coder.py:250-254, 352-354; os2d_train_assign_targets_ops)
 
 The target side runs as one launch per call over every (image, label, anchor); the BoxLists are packed into four arrays on
-the host once per batch.  A box transform reaches the kernels as the chain ``trace_box_transform`` records; the reference-named
-``encode`` / ``encode_pyramid`` / ``remap_anchor_targets`` refuse transforms and name the ``_transformed`` methods
-(INTEGRATION.md section 7b).
+the host once per batch.  A box transform reaches the kernels as the chain that box_ops.py records (its names are re-exported
+here); the reference-named ``encode`` / ``encode_pyramid`` / ``remap_anchor_targets`` refuse transforms and name the
+``_transformed`` methods.
 """
-import collections
-import weakref
 import ctypes
 from functools import lru_cache
 
@@ -28,12 +28,13 @@ import torch
 from .. import _lib
 from .. import _train_lib
 from ..structures.feature_map import FeatureMapSize
-from ..structures.bounding_box import BoxList, FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM
+from ..structures.bounding_box import BoxList, FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM          # noqa: F401 (the flips: re-exported)
+from .box_ops import (OP_SCALE, OP_HFLIP, OP_VFLIP, OP_SHIFT, MAX_BOX_OPS, MAX_DEFAULT_BOX_OPS,          # noqa: F401 (re-exported)
+                      ResizeBoxes, _BoxTrace, apply_box_ops, _PROBE_BOXES, transform_level_boxes, trace_box_transform,
+                      _TRACE_CACHE, _trace_chains, _probe_check, _trace_box_transform, ops_tables, _ops_tables,
+                      traced_box_ops, as_box_ops)
 
 BOX_ENCODING_WEIGHTS = (10.0, 10.0, 5.0, 5.0)   # reference box_coder.py:13
-OP_SCALE, OP_HFLIP, OP_VFLIP, OP_SHIFT = 1, 2, 3, 4   # OS2D_BOX_OP_* of include/os2d_hip.h
-MAX_BOX_OPS = 6                                       # OS2D_BOX_MAX_OPS
-MAX_DEFAULT_BOX_OPS = 12                              # OS2D_BOX_MAX_DEFAULT_OPS
 
 
 @lru_cache()
@@ -46,184 +47,6 @@ def create_strided_boxes_columnfirst(grid_size, box_size, box_stride):
     cy = cy.view(-1, 1).expand(grid_size.h, grid_size.w).reshape(-1)
     hw, hh = box_size.w / 2.0, box_size.h / 2.0
     return torch.stack([cx - hw, cy - hh, cx + hw, cy + hh], dim=1)
-
-
-class ResizeBoxes(object):
-    """``inverse_box_transforms`` entry that maps a level's boxes to ``target_size`` (what the reference's
-    ``TransformList`` inverse amounts to for a resized image, box_coder.py:499-503): ``boxlist.resize(target_size)``.
-    (Any entry made of BoxList.resize / transpose / crop calls - this class, the reference's ``TransformList`` of lambdas -
-    reaches the fused decode kernels: ``trace_box_transform`` records the chain.)"""
-
-    def __init__(self, target_size):
-        self.target_size = target_size
-
-    def __call__(self, boxlist):
-        return boxlist.resize(self.target_size)
-
-    def ratios(self, img_size):
-        return float(self.target_size.w) / img_size.w, float(self.target_size.h) / img_size.h
-
-
-class _BoxTrace(object):
-    """Stand-in for a ``BoxList`` that RECORDS what an ``inverse_box_transforms`` entry does to it.  The reference hands
-    ``decode_pyramid`` one ``TransformList`` of closures per level (os2d/structures/transforms.py:12-27; the closures are
-    ``lambda boxes: boxes.resize(size)`` / ``boxes.transpose(FLIP_*)`` / ``boxes.crop(uncrop_xyxy)``, appended by
-    transforms.py:32-52, 78-79, 188-191 from os2d/data/dataloader.py:286-336) and calls it on BoxLists
-    (os2d/modeling/box_coder.py:499-503).  Called on this object instead, the same closures leave the exact sequence of
-    operations with their parameters - which the fused decode kernels then apply op by op with the reference's roundings
-    (a numerical probe could only recover the composite map, not where it rounds).  Anything else a closure might touch
-    (``bbox_xyxy``, fields, ...) is not defined here: the AttributeError sends the caller to the generic chain."""
-
-    def __init__(self, image_size, ops=(), fields=None):
-        self.image_size = image_size
-        self.ops = tuple(ops)
-        self.extra_fields = dict(fields or {})     # name -> _BoxTrace (BoxList-valued fields: "default_boxes")
-
-    def add_field(self, field, field_data):
-        self.extra_fields[field] = field_data
-
-    def get_field(self, field):
-        return self.extra_fields[field]
-
-    def has_field(self, field):
-        return field in self.extra_fields
-
-    def resize(self, target_size):                      # BoxList.resize, reference bounding_box.py:138-163
-        op = (OP_SCALE, float(target_size.w) / self.image_size.w, float(target_size.h) / self.image_size.h)
-        return _BoxTrace(target_size, self.ops + (op,), self.extra_fields)          # fields are copied AS THEY ARE (:162)
-
-    def transpose(self, method):                        # reference bounding_box.py:165-200
-        if method == FLIP_LEFT_RIGHT:
-            op = (OP_HFLIP, float(self.image_size.w), 0.0)
-        elif method == FLIP_TOP_BOTTOM:
-            op = (OP_VFLIP, 0.0, float(self.image_size.h))
-        else:
-            raise NotImplementedError("Only FLIP_LEFT_RIGHT and FLIP_TOP_BOTTOM implemented")
-        # BoxList-valued fields are flipped too, each inside ITS OWN image (:196-199)
-        return _BoxTrace(self.image_size, self.ops + (op,), {k: v.transpose(method) for k, v in self.extra_fields.items()})
-
-    def crop(self, box):                                # reference bounding_box.py:202-226
-        size = FeatureMapSize(w=box[2] - box[0], h=box[3] - box[1])
-        return _BoxTrace(size, self.ops + ((OP_SHIFT, float(box[0]), float(box[1])),),
-                         {k: v.crop(box) for k, v in self.extra_fields.items()})
-
-
-def apply_box_ops(boxes, ops):
-    """The recorded chain on a [n,4] xyxy tensor with the arithmetic of the BoxList methods (one float32 rounding per
-    product / difference) - what os2d_apply_box_ops does on the device."""
-    x1, y1, x2, y2 = boxes.unbind(1)
-    for kind, ax, ay in ops:
-        if kind == OP_SCALE:
-            x1, y1, x2, y2 = x1 * ax, y1 * ay, x2 * ax, y2 * ay
-        elif kind == OP_HFLIP:
-            x1, x2 = ax - x2, ax - x1
-        elif kind == OP_VFLIP:
-            y1, y2 = ay - y2, ay - y1
-        else:
-            x1, y1, x2, y2 = x1 - ax, y1 - ay, x2 - ax, y2 - ay
-    return torch.stack([x1, y1, x2, y2], dim=1)
-
-
-_PROBE_BOXES = ((0.0, 0.0, 1.0, 1.0), (13.25, 7.5, 211.0, 95.75), (3.0, 250.5, 640.125, 479.0))
-
-
-def transform_level_boxes(transform, boxes, default_boxes, corners, img_size):
-    """What reference box_coder.py:509-521 does with a level's ``inverse_box_transforms`` entry, on plain tensors:
-    boxes [n,4] -> transform(boxes); the anchors ride along as the BoxList FIELD "default_boxes" (BoxList.transpose / crop
-    transform BoxList-valued fields as well, each inside its own image; resize copies them as they are) and the transform is
-    applied to that field once more afterwards; the corners [m,4] go through as boxes of their own.  For a resize-only chain
-    (the evaluation's) all three see the same map; with flips / crops the anchors see them twice - reproduced as is, so that
-    a caller of the reference gets the reference's numbers.  Returns (boxes, default_boxes, corners or None, output size)."""
-    bl = BoxList(boxes, img_size)
-    bl.add_field("default_boxes", BoxList(default_boxes, img_size))
-    out = transform(bl)
-    dflt = transform(out.get_field("default_boxes"))
-    cor = transform(BoxList(corners, img_size)).bbox_xyxy if corners is not None else None
-    return out.bbox_xyxy, dflt.bbox_xyxy, cor, out.image_size
-
-
-def trace_box_transform(transform, img_size):
-    """-> (box ops, anchor ops, output image size) of one ``inverse_box_transforms`` entry applied to a level on an image of
-    ``img_size`` (see ``transform_level_boxes`` for why the anchors have a chain of their own), or None when the entry is not a
-    chain of BoxList.resize / transpose / crop - then only the generic decode can run it.  ``None`` entries trace to empty
-    chains.  The recorded chains are checked against the entry itself on three probe boxes (unit, generic, near the border):
-    bit-equal coordinates and the same output size, or they are not used."""
-    if transform is None:
-        return (), (), img_size
-    # Two steps: the TRACE (the closures run on _BoxTrace objects: no tensors, a few Python calls) is made on every call, the
-    # PROBE CHECK (three closure runs on CPU BoxLists) only once per (callable, image size, traced chains).  Keyed on the chains
-    # themselves, a hit cannot be stale: a TransformList that was appended to (whatever the attribute its list lives in - the
-    # reference keeps it in ``_transforms``, structures/transforms.py:18-22), or a closure whose captured state changed, traces to
-    # other chains and is probed again (ADVICE r5; round 5 keyed on object identity + an attribute named ``transforms`` only).
-    # The cache holds WEAK references: it keeps no transform (nor what it captured) alive, a dead entry's id may be reused and
-    # is then not a hit; callables that cannot be weakly referenced are not cached.
-    traced = _trace_chains(transform, img_size)
-    if traced is None:
-        return None
-    try:
-        ref = weakref.ref(transform)
-    except TypeError:
-        return traced if _probe_check(transform, img_size, traced) else None
-    ckey = (id(transform), int(img_size.w), int(img_size.h), traced[0], traced[1], int(traced[2].w), int(traced[2].h))
-    hit = _TRACE_CACHE.get(ckey)
-    if hit is not None and hit[0]() is transform:
-        _TRACE_CACHE.move_to_end(ckey)
-        return traced if hit[1] else None
-    ok = _probe_check(transform, img_size, traced)
-    _TRACE_CACHE[ckey] = (ref, ok)
-    while len(_TRACE_CACHE) > 64:
-        _TRACE_CACHE.popitem(last=False)
-    return traced if ok else None
-
-
-_TRACE_CACHE = collections.OrderedDict()
-
-
-def _trace_chains(transform, img_size):
-    """(box ops, anchor ops, output size) recorded by running the entry on _BoxTrace objects, or None."""
-    try:
-        root = _BoxTrace(img_size)
-        root.add_field("default_boxes", _BoxTrace(img_size))
-        traced = transform(root)
-        if not isinstance(traced, _BoxTrace) or len(traced.ops) > MAX_BOX_OPS:
-            return None
-        anchors = transform(traced.get_field("default_boxes"))
-        if not isinstance(anchors, _BoxTrace) or len(anchors.ops) > MAX_DEFAULT_BOX_OPS:
-            return None
-    except Exception:   # noqa: BLE001 - a closure that does anything else than the three BoxList operations
-        return None
-    return traced.ops, anchors.ops, traced.image_size
-
-
-def _probe_check(transform, img_size, traced):
-    """The recorded chains against the entry itself on the probe boxes: bit-equal coordinates and the same output size."""
-    try:
-        probe = torch.tensor(_PROBE_BOXES, dtype=torch.float32)
-        b, d, c, size = transform_level_boxes(transform, probe.clone(), probe.clone() + 0.5, probe.clone(), img_size)
-        return bool(size == traced[2] and torch.equal(b, apply_box_ops(probe, traced[0])) and torch.equal(c, b)
-                    and torch.equal(d, apply_box_ops(probe + 0.5, traced[1])))
-    except Exception:   # noqa: BLE001
-        return False
-
-
-def _trace_box_transform(transform, img_size):
-    """Uncached trace + probe check (tests)."""
-    traced = _trace_chains(transform, img_size)
-    return traced if traced is not None and _probe_check(transform, img_size, traced) else None
-
-
-def _ops_tables(ops_per_level, width=MAX_BOX_OPS):
-    """ctypes tables (counts [L], kinds [L][width], args [L][width][2]) of os2d_detect_level_ops / os2d_detect_pyramid_ops."""
-    L = len(ops_per_level)
-    counts = (ctypes.c_int * L)(*[len(o) for o in ops_per_level])
-    kinds = (ctypes.c_int * (L * width))()
-    args = (ctypes.c_float * (L * width * 2))()
-    for l, ops in enumerate(ops_per_level):
-        for k, (kind, ax, ay) in enumerate(ops):
-            kinds[l * width + k] = kind
-            args[(l * width + k) * 2] = ax
-            args[(l * width + k) * 2 + 1] = ay
-    return counts, kinds, args
 
 
 class BoxGridGenerator(object):
@@ -243,7 +66,7 @@ class BoxGridGenerator(object):
         current one).  A transform that is not a chain of BoxList.resize / transpose / crop raises ValueError."""
         if self.box_size.w != self.box_size.h or self.box_stride.w != self.box_stride.h:
             raise RuntimeError("anisotropic anchors are not supported")
-        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        device = _hip_device() if device is None else torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("get_box_to_cut_anchor runs on the HIP device only (no CPU fallback), got {}".format(device))
         ops, out_size = traced_box_ops(default_box_transform, img_size)
@@ -251,23 +74,13 @@ class BoxGridGenerator(object):
         HW = fm_size.h * fm_size.w
         crops = torch.empty(HW, 4, dtype=torch.float32, device=device)
         anchors = torch.empty(HW, 4, dtype=torch.float32, device=device)
-        _, kinds, args = _ops_tables([ops])
+        _, kinds, args = ops_tables([ops])
         with torch.cuda.device(device):
             _train_lib.check(tl.os2d_train_crop_boxes(fm_size.h, fm_size.w, int(self.box_stride.w), int(self.box_size.w), int(img_size.w),
                                                       int(img_size.h), int(crop_size.w), int(crop_size.h), len(ops), kinds, args,
                                                       _lib.ptr(crops), _lib.ptr(anchors), _lib.current_stream(device)),
                              "os2d_train_crop_boxes")
         return BoxList(crops, out_size), BoxList(anchors, out_size), torch.arange(HW, device=device)
-
-
-def traced_box_ops(transform, img_size):
-    """-> (box-op chain, output image size) of a box transform of the target / mining code, recorded by ``trace_box_transform``;
-    ValueError when the transform is not a chain of at most MAX_BOX_OPS BoxList.resize / transpose / crop calls."""
-    traced = trace_box_transform(transform, img_size)
-    if traced is None:
-        raise ValueError("the box transform is not a chain of at most {} BoxList.resize / transpose / crop calls: the HIP kernels "
-                         "cannot express it".format(MAX_BOX_OPS))
-    return traced[0], traced[2]
 
 
 def feature_map_size_c4(img_size):
@@ -292,6 +105,50 @@ class Matcher(object):
         best, index = ious.max(dim=0)
         index = torch.where(best < self.high_threshold, torch.full_like(index, self.BETWEEN_THRESHOLDS), index)
         return torch.where(best < self.low_threshold, torch.full_like(index, self.BELOW_LOW_THRESHOLD), index)
+
+
+def _hip_device(boxes=None):
+    """The device of these boxes when they are on one already, else the current HIP device."""
+    on_device = boxes is not None and boxes.bbox_xyxy.is_cuda
+    return boxes.bbox_xyxy.device if on_device else torch.device("cuda", torch.cuda.current_device())
+
+
+def _label_rows(class_ids):
+    """-> (ids, labels, rows_of): the class id of every head row, the labels in the order of the result, and per label the
+    head rows that carry it, in row order (several for class-image views, reference box_coder.py:483-487)."""
+    ids = [int(c) for c in class_ids]
+    labels = list(set(ids))   # the reference iterates ``set(class_ids)`` (box_coder.py:483): same order, whatever it is
+    rows_of = {l: [] for l in labels}
+    for i, c in enumerate(ids):
+        rows_of[c].append(i)
+    return ids, labels, rows_of
+
+
+def _require_device(loc, cls=None):
+    """The decode kernels read float32 loc_scores (and the cls_scores, where they get them) on the HIP device."""
+    if not (loc.is_cuda and (cls is None or cls.is_cuda) and loc.dtype == torch.float32):
+        raise RuntimeError("decode runs on the HIP device only (no CPU fallback)")
+
+
+def _level_inputs(loc, cls, B, hw, dev):
+    """A level's loc_scores [B,4,hw] and cls_scores [B,hw] as the fused kernels get them: checked, contiguous, float32."""
+    _require_device(loc, cls)
+    assert loc.device == dev and cls.device == dev, "scores and boxes should be on the same device"
+    loc, cls = loc.contiguous(), cls.float().contiguous()
+    assert tuple(loc.shape) == (B, 4, hw) and tuple(cls.shape) == (B, hw), "level tensors do not match class_ids / feature map"
+    return loc, cls
+
+
+def _detections(boxes, scores, labels, default_boxes, corners, out_size):
+    """What ``decode_pyramid`` returns, whichever route made it: boxes [n,4] on an image of ``out_size`` with the fields scores
+    [n], labels [n] int64, default_boxes (a BoxList of the anchors) and, where corners [n,8] are given, transform_corners."""
+    result = BoxList(boxes, out_size)
+    result.add_field("scores", scores)
+    result.add_field("labels", labels)
+    result.add_field("default_boxes", BoxList(default_boxes, out_size))
+    if corners is not None:
+        result.add_field("transform_corners", corners)
+    return result
 
 
 class Os2dBoxCoder(object):
@@ -327,12 +184,12 @@ class Os2dBoxCoder(object):
         fm = self.get_feature_map_size(img_size)
         return BoxList(self.output_box_grid_generator.create_strided_boxes_columnfirst(fm), image_size=img_size)
 
+    # ------------------------------------------------------------------ decode of one level (os2d_decode_boxes)
     def decode_level(self, loc_scores, img_size):
         """loc_scores [NB,4,HW] device tensor -> boxes [NB,HW,4] xyxy clipped to the level image
         (reference box_coder.py:319-330 + bounding_box.py:261-265) with os2d_decode_boxes."""
         lib = _lib.load()
-        if not (loc_scores.is_cuda and loc_scores.dtype == torch.float32):
-            raise RuntimeError("decode runs on the HIP device only (no CPU fallback)")
+        _require_device(loc_scores)
         loc_scores = loc_scores.contiguous()
         fm = self.get_feature_map_size(img_size)
         NB, four, HW = loc_scores.shape
@@ -425,6 +282,7 @@ class Os2dBoxCoder(object):
         alive.scatter_(1, torch.where(pos < cnt.unsqueeze(1), ids, torch.full_like(ids, N)), True)
         return alive[:, :N]
 
+    # ------------------------------------------------------------------ decode + NMS of a pyramid: three routes to one result
     def decode_pyramid(self, loc_scores_pyramid, cls_scores_pyramid, img_size_pyramid, class_ids,
                        nms_score_threshold=0.0, nms_iou_threshold=0.3, inverse_box_transforms=None,
                        transform_corners_pyramid=None):
@@ -479,13 +337,9 @@ class Os2dBoxCoder(object):
         dflt = torch.cat(dflt_l, 1)
         corners = torch.cat(corners_l, 1) if corners_l else None
         # merge rows that share a real label
-        ids = [int(c) for c in class_ids]
-        by_label = {}
-        for i, c in enumerate(ids):
-            by_label.setdefault(c, []).append(i)
-        labels_sorted = list(set(ids))   # the reference iterates ``set(class_ids)`` (box_coder.py:483): same order, whatever it is
-        groups = [by_label[l] for l in labels_sorted]
-        if len(labels_sorted) != len(ids) or labels_sorted != ids:
+        ids, labels_sorted, rows_of = _label_rows(class_ids)
+        groups = [rows_of[l] for l in labels_sorted]
+        if labels_sorted != ids:
             width = max(len(g) for g in groups) * boxes.size(1)
 
             def merge(t, fill):
@@ -518,13 +372,9 @@ class Os2dBoxCoder(object):
         out_size = img_size_pyramid[0]
         if inverse_box_transforms is not None:
             out_size = inverse_box_transforms[0](BoxList(torch.zeros(1, 4, device=dev), img_size_pyramid[0])).image_size
-        result = BoxList(boxes.reshape(-1, 4)[flat], out_size)
-        result.add_field("scores", scores.reshape(-1)[flat])
         lab = torch.tensor(labels_sorted, dtype=torch.long, device=dev).unsqueeze(1).expand(-1, order.size(1)).reshape(-1)
-        result.add_field("labels", lab[sel])
-        result.add_field("default_boxes", BoxList(dflt.reshape(-1, 4)[flat], out_size))
-        if corners is not None:
-            result.add_field("transform_corners", corners.reshape(-1, 8)[flat])
+        result = _detections(boxes.reshape(-1, 4)[flat], scores.reshape(-1)[flat], lab[sel], dflt.reshape(-1, 4)[flat],
+                             corners.reshape(-1, 8)[flat] if corners is not None else None, out_size)
         return self._nms_across_classes(result, nms_iou_threshold)
 
     def _nms_across_classes(self, result, nms_iou_threshold):
@@ -543,8 +393,8 @@ class Os2dBoxCoder(object):
         the whole per-class chain runs in ONE launch (os2d_detect_level); None when the generic path has to be used."""
         if not self.use_fused_level_kernel or len(loc_pyr) != 1:
             return None
-        ids = [int(c) for c in class_ids]
-        if len(set(ids)) != len(ids):
+        ids, labels, rows_of = _label_rows(class_ids)
+        if len(labels) != len(ids):
             return None
         loc, cls, img_size = loc_pyr[0], cls_pyr[0], size_pyr[0]
         traced = trace_box_transform(inverse[0] if inverse is not None else None, img_size)
@@ -555,14 +405,10 @@ class Os2dBoxCoder(object):
         lib = _lib.load()
         if not lib.os2d_detect_level_supported(fm.h, fm.w):
             return None
-        if not (loc.is_cuda and cls.is_cuda and loc.dtype == torch.float32):
-            raise RuntimeError("decode runs on the HIP device only (no CPU fallback)")
         dev = cls.device
         B, HW = len(ids), fm.h * fm.w
-        loc = loc.contiguous()
-        cls = cls.float().contiguous()
-        assert tuple(loc.shape) == (B, 4, HW) and tuple(cls.shape) == (B, HW), "level tensors do not match class_ids / feature map"
-        counts_c, kinds_c, args_c = _ops_tables([ops])
+        loc, cls = _level_inputs(loc, cls, B, HW, dev)
+        counts_c, kinds_c, args_c = ops_tables([ops])
         out_boxes = torch.empty(B, HW, 4, dtype=torch.float32, device=dev)
         out_scores = torch.empty(B, HW, dtype=torch.float32, device=dev)
         out_index = torch.empty(B, HW, dtype=torch.int32, device=dev)
@@ -573,32 +419,26 @@ class Os2dBoxCoder(object):
                                                  ctypes.c_float(score_thr), ctypes.c_float(iou_thr),
                                                  _lib.ptr(out_boxes), _lib.ptr(out_scores), _lib.ptr(out_index),
                                                  _lib.ptr(out_count), _lib.current_stream(dev)), "os2d_detect_level_ops")
-        # rows in the label order of the reference (iteration order of ``set(class_ids)``), survivors of a row by score
-        rank = {l: k for k, l in enumerate(set(ids))}      # the reference iterates ``set(class_ids)`` (box_coder.py:483)
-        order = sorted(range(B), key=lambda i: rank[ids[i]])
-        counts = out_count
-        if order != list(range(B)):
-            perm = torch.tensor(order, dtype=torch.long, device=dev)
-            counts = out_count[perm]
-        else:
-            perm = None
+        # rows in the label order of the reference, survivors of a row by score
+        order = [rows_of[l][0] for l in labels]
+        perm = torch.tensor(order, dtype=torch.long, device=dev) if order != list(range(B)) else None
+        counts = out_count[perm] if perm is not None else out_count
         mask = torch.arange(HW, device=dev).unsqueeze(0) < counts.unsqueeze(1)
         row, pos = mask.nonzero(as_tuple=True)                   # the one host synchronisation: sizes the result
         src_row = perm[row] if perm is not None else row
         flat = src_row * HW + pos
-        result = BoxList(out_boxes.view(-1, 4)[flat], out_size)
-        result.add_field("scores", out_scores.view(-1)[flat])
-        result.add_field("labels", torch.tensor([ids[i] for i in order], dtype=torch.long, device=dev)[row])
+        boxes, scores = out_boxes.view(-1, 4)[flat], out_scores.view(-1)[flat]
+        lab = torch.tensor(labels, dtype=torch.long, device=dev)[row]
         loc_idx = out_index.view(-1)[flat].long()
         dflt = apply_box_ops(self._get_default_boxes(img_size).bbox_xyxy.to(dev)[loc_idx], default_ops)
-        result.add_field("default_boxes", BoxList(dflt, out_size))
+        corners = None
         if corners_pyr is not None:
             corners = corners_pyr[0][src_row, :, loc_idx]                                   # [n, 8]
             # like the reference, the corners go through the level's transform as the two "boxes" (x0, y0, x1, y1), (x2, y2, x3, y3)
-            result.add_field("transform_corners", apply_box_ops(corners.reshape(-1, 4), ops).view(-1, 8))
-        return result
+            corners = apply_box_ops(corners.reshape(-1, 4), ops).view(-1, 8)
+        return _detections(boxes, scores, lab, dflt, corners, out_size)
 
-    def _slot_rows(self, ids, labels, V, dev):
+    def _slot_rows(self, ids, labels, rows_of, V, dev):
         """Device table [G][V] of the head rows of every label (-1: no such view), cached per (class ids, device): the rows of
         an evaluation's class batch are the same for every image, and building the table is a blocking host-to-device copy
         from pageable memory on the per-image path."""
@@ -607,9 +447,6 @@ class Os2dBoxCoder(object):
         stream = torch.cuda.current_stream(dev)
         entry = cache.get(key)
         if entry is None:
-            rows_of = {}
-            for i, c in enumerate(ids):
-                rows_of.setdefault(c, []).append(i)
             host = torch.tensor([(rows_of[l] + [-1] * V)[:V] for l in labels], dtype=torch.int32).pin_memory()
             table = host.to(dev, non_blocking=True)
             event = torch.cuda.Event()
@@ -632,8 +469,6 @@ class Os2dBoxCoder(object):
         chunk-and-repeat NMS for lists longer than ``nms_max_batch``, runs on the device (os2d_detect_pyramid /
         os2d_detect_pyramid_merged: one launch per NMS pass, a work-group per (chunk, label)); None when the generic path has
         to be used."""
-        ids = [int(c) for c in class_ids]
-        merged = len(set(ids)) != len(ids)
         if not self.use_fused_level_kernel:
             return None
         # (a single level with one row per label normally took os2d_detect_level before this is called; levels beyond that
@@ -649,9 +484,7 @@ class Os2dBoxCoder(object):
         fms = [self.get_feature_map_size(s) for s in size_pyr]
         hws = [fm.h * fm.w for fm in fms]
         N1 = sum(hws)                                         # candidates per head row
-        # labels in the reference's iteration order (``set(class_ids)``, box_coder.py:483), each with its rows in row order
-        labels = list(set(ids))
-        rows_of = {l: [i for i, c in enumerate(ids) if c == l] for l in labels}
+        ids, labels, rows_of = _label_rows(class_ids)
         G, V = len(labels), max(len(r) for r in rows_of.values())
         N = N1 * V                                            # candidates per label
         if N > (1 << 22) or not lib.os2d_detect_pyramid_supported(L, N, int(self.nms_max_batch)):
@@ -660,16 +493,12 @@ class Os2dBoxCoder(object):
         B = len(ids)
         locs, clss = [], []
         for loc, cls, hw in zip(loc_pyr, cls_pyr, hws):
-            if not (loc.is_cuda and cls.is_cuda and loc.dtype == torch.float32):
-                raise RuntimeError("decode runs on the HIP device only (no CPU fallback)")
-            assert loc.device == dev and cls.device == dev, "scores and boxes should be on the same device"
-            loc, cls = loc.contiguous(), cls.float().contiguous()
-            assert tuple(loc.shape) == (B, 4, hw) and tuple(cls.shape) == (B, hw), "level tensors do not match class_ids / feature map"
+            loc, cls = _level_inputs(loc, cls, B, hw, dev)
             locs.append(loc)
             clss.append(cls)
         out_size = traced[0][2]
-        c_counts, c_kinds, c_args = _ops_tables([t_[0] for t_ in traced])
-        d_counts, d_kinds, d_args = _ops_tables([t_[1] for t_ in traced], MAX_DEFAULT_BOX_OPS)
+        c_counts, c_kinds, c_args = ops_tables([t_[0] for t_ in traced])
+        d_counts, d_kinds, d_args = ops_tables([t_[1] for t_ in traced], MAX_DEFAULT_BOX_OPS)
         passes = int(self.fused_pyramid_passes)
         nbytes = ctypes.c_size_t()
         _lib.check(lib.os2d_detect_pyramid_workspace_bytes(G, N, passes, ctypes.byref(nbytes)), "os2d_detect_pyramid_workspace_bytes")
@@ -689,9 +518,9 @@ class Os2dBoxCoder(object):
             out_corners = torch.empty(G, N, 8, dtype=torch.float32, device=dev)
         c_hw = (ctypes.c_int * (2 * L))(*[v for fm in fms for v in (fm.h, fm.w)])
         c_img = (ctypes.c_float * (2 * L))(*[float(v) for s_ in size_pyr for v in (s_.w, s_.h)])
-        identity = not merged and labels == ids          # one row per label, already in the reference's label order
+        identity = labels == ids                         # one row per label, already in the reference's label order
         with torch.cuda.device(dev):
-            slot_rows = None if identity else self._slot_rows(tuple(ids), tuple(labels), V, dev)
+            slot_rows = None if identity else self._slot_rows(tuple(ids), tuple(labels), rows_of, V, dev)
             _lib.check(lib.os2d_detect_pyramid_ops(c_loc, c_cls, c_cor, B, L, c_hw, self._stride, self._rec_field, c_img,
                                                    c_counts, c_kinds, c_args, d_counts, d_kinds, d_args,
                                                    ctypes.c_float(score_thr), ctypes.c_float(iou_thr),
@@ -705,13 +534,8 @@ class Os2dBoxCoder(object):
         if int(unfinished.item()) != 0:
             return None          # some label needs more NMS passes than were launched: generic path (exact, slower)
         flat = row * N + pos
-        result = BoxList(out_boxes.view(-1, 4)[flat], out_size)
-        result.add_field("scores", out_scores.view(-1)[flat])
-        result.add_field("labels", torch.tensor(labels, dtype=torch.long, device=dev)[row])
-        result.add_field("default_boxes", BoxList(out_default.view(-1, 4)[flat], out_size))
-        if out_corners is not None:
-            result.add_field("transform_corners", out_corners.view(-1, 8)[flat])
-        return result
+        return _detections(out_boxes.view(-1, 4)[flat], out_scores.view(-1)[flat], torch.tensor(labels, dtype=torch.long, device=dev)[row],
+                           out_default.view(-1, 4)[flat], out_corners.view(-1, 8)[flat] if out_corners is not None else None, out_size)
 
     # ------------------------------------------------------------------------------------------------ training targets
     @staticmethod
@@ -756,7 +580,7 @@ class Os2dBoxCoder(object):
             else:
                 if len(ops) > MAX_BOX_OPS:
                     raise ValueError("a box-op chain of {} entries: at most {} are supported".format(len(ops), MAX_BOX_OPS))
-                _, kinds, args = _ops_tables([ops])
+                _, kinds, args = ops_tables([ops])
                 _train_lib.check(tl.os2d_train_assign_targets_ops(*(head + (len(ops), kinds, args) + tail)),
                                  "os2d_train_assign_targets_ops")
         return cls_targets, outs
@@ -772,8 +596,7 @@ class Os2dBoxCoder(object):
         positive, 0 negative, -1 ignored), on the HIP device (that of ``boxes`` when it is there already)."""
         if default_box_transform is not None:
             raise NotImplementedError("default_box_transform is not supported here: use encode_transformed")
-        dev = boxes.bbox_xyxy.device if boxes.bbox_xyxy.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        loc_targets, cls_targets = self.encode_batch([boxes], img_size, num_labels, dev)
+        loc_targets, cls_targets = self.encode_batch([boxes], img_size, num_labels, _hip_device(boxes))
         return loc_targets[0], cls_targets[0]
 
     def encode_pyramid(self, boxes, img_size_pyramid, num_labels, default_box_transform_pyramid=None):
@@ -789,16 +612,21 @@ class Os2dBoxCoder(object):
         no host synchronisation.  The images of a batch share one size (they are one tensor)."""
         if box_reverse_transform is not None:
             raise NotImplementedError("box_reverse_transform is not supported here: use remap_anchor_targets_transformed")
+        A, B, fm = self._remap_args("remap_anchor_targets", loc_scores, batch_img_size, batch_boxes)
+        cls_targets, outs = self._assign(1, batch_boxes, fm, B, loc_scores.device, loc_scores.detach().contiguous())
+        return cls_targets, outs[1], outs[2]
+
+    def _remap_args(self, name, loc_scores, batch_img_size, batch_boxes):
+        """The argument checks of ``remap_anchor_targets`` and its ``_transformed`` twin -> (A images, B labels, feature map size)."""
         if not (loc_scores.is_cuda and loc_scores.dtype == torch.float32):
-            raise RuntimeError("remap_anchor_targets runs on the HIP device only (no CPU fallback)")
+            raise RuntimeError("{} runs on the HIP device only (no CPU fallback)".format(name))
         A, B = loc_scores.shape[0], loc_scores.shape[1]
         if len(batch_boxes) != A or len(batch_img_size) != A:
             raise ValueError("batch_boxes / batch_img_size must have one entry per image ({})".format(A))
         fm = self.get_feature_map_size(batch_img_size[0])
         if any(self.get_feature_map_size(s) != fm for s in batch_img_size[1:]) or fm.h * fm.w != loc_scores.shape[3]:
             raise ValueError("the images of a batch must share one feature map size that matches loc_scores")
-        cls_targets, outs = self._assign(1, batch_boxes, fm, B, loc_scores.device, loc_scores.detach().contiguous())
-        return cls_targets, outs[1], outs[2]
+        return A, B, fm
 
     # ---------------------------------------------------------------- targets under a box transform (hard-patch mining)
     def encode_transformed(self, boxes, img_size, num_labels, default_box_transform=None, device=None):
@@ -806,9 +634,8 @@ class Os2dBoxCoder(object):
         the transform before they are matched with ``boxes``, clipped to a minimal size and encoded.  The transform is a chain
         of BoxList.resize / transpose / crop calls (the reference's ``TransformList``) or a recorded chain of
         (kind, ax, ay) tuples; anything else raises ValueError.  -> loc_targets [num_labels,4,HW], cls_targets [num_labels,HW]."""
-        ops = self._chain(default_box_transform, img_size)
-        if device is None:
-            device = boxes.bbox_xyxy.device if boxes.bbox_xyxy.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        ops = as_box_ops(default_box_transform, img_size)
+        device = _hip_device(boxes) if device is None else device
         cls_targets, outs = self._assign(0, [boxes], self.get_feature_map_size(img_size), num_labels, device, ops=ops)
         return outs[0][0], cls_targets[0]
 
@@ -823,18 +650,11 @@ class Os2dBoxCoder(object):
         ``loc_scores`` against the plain anchor and the anchor itself go through the image's transform before they meet the
         ground truth.  ``box_reverse_transform``: one entry per image.  One launch when the images share a chain (mining
         handles one image at a time), else one per image; no host synchronisation."""
-        if not (loc_scores.is_cuda and loc_scores.dtype == torch.float32):
-            raise RuntimeError("remap_anchor_targets_transformed runs on the HIP device only (no CPU fallback)")
-        A, B = loc_scores.shape[0], loc_scores.shape[1]
-        if len(batch_boxes) != A or len(batch_img_size) != A:
-            raise ValueError("batch_boxes / batch_img_size must have one entry per image ({})".format(A))
+        A, B, fm = self._remap_args("remap_anchor_targets_transformed", loc_scores, batch_img_size, batch_boxes)
         ts = box_reverse_transform if box_reverse_transform is not None else [None] * A
         if len(ts) != A:
             raise ValueError("box_reverse_transform must have one entry per image ({})".format(A))
-        fm = self.get_feature_map_size(batch_img_size[0])
-        if any(self.get_feature_map_size(s) != fm for s in batch_img_size[1:]) or fm.h * fm.w != loc_scores.shape[3]:
-            raise ValueError("the images of a batch must share one feature map size that matches loc_scores")
-        chains = [self._chain(t, s) for t, s in zip(ts, batch_img_size)]
+        chains = [as_box_ops(t, s) for t, s in zip(ts, batch_img_size)]
         loc_scores = loc_scores.detach().contiguous()
         if all(c == chains[0] for c in chains[1:]):
             cls_targets, outs = self._assign(1, batch_boxes, fm, B, loc_scores.device, loc_scores, ops=chains[0])
@@ -844,18 +664,14 @@ class Os2dBoxCoder(object):
 
     @staticmethod
     def _chain(transform, img_size):
-        """A transform of the target code as a box-op chain: a callable is traced, a sequence of (kind, ax, ay) is taken as it is."""
-        if isinstance(transform, (tuple, list)):
-            ops = tuple((int(k), float(ax), float(ay)) for k, ax, ay in transform)
-            if len(ops) > MAX_BOX_OPS or any(k not in (OP_SCALE, OP_HFLIP, OP_VFLIP, OP_SHIFT) for k, _, _ in ops):
-                raise ValueError("a box-op chain has at most {} entries of kind 1..4, got {}".format(MAX_BOX_OPS, ops))
-            return ops
-        return traced_box_ops(transform, img_size)[0]
+        """``box_ops.as_box_ops`` under the coder's name for it."""
+        return as_box_ops(transform, img_size)
 
+    # ---------------------------------------------------------------- the reference's public helpers (plain tensors, no kernel)
     @staticmethod
     def apply_transform_to_corners(masked_transform_corners, transform, img_size):
         """reference box_coder.py:439-446: corners [n,8] (x,y,x,y,x,y,x,y) go through the transform as two boxes each."""
-        ops = Os2dBoxCoder._chain(transform, img_size)
+        ops = as_box_ops(transform, img_size)
         return apply_box_ops(masked_transform_corners.contiguous().view(-1, 4), ops).contiguous().view(-1, 8)
 
     @staticmethod

@@ -542,3 +542,52 @@ def test_untraceable_transform_falls_back_to_the_generic_chain(device):
     res = coder.decode_pyramid(locs, clss, sizes, [0, 1], nms_score_threshold=0.0, inverse_box_transforms=shift)
     plain = coder.decode_pyramid(locs, clss, sizes, [0, 1], nms_score_threshold=0.0)
     assert len(res) == len(plain) and torch.equal(res.bbox_xyxy, plain.bbox_xyxy + 2.0)
+
+
+# ------------------------------------------------------------------------------------- one result contract, three routes
+def _contract_inputs(levels, B):
+    """CPU inputs of the result-contract test: (H, W) levels at stride 16, scores in (0, 1), fixed seed."""
+    from os2d_amd.structures.feature_map import FeatureMapSize
+    rs = np.random.RandomState(2024)
+    sizes = [FeatureMapSize(w=16 * w, h=16 * h) for h, w in levels]
+    locs = [torch.from_numpy((rs.standard_normal((B, 4, h * w)) * 1.2).astype(np.float32)) for h, w in levels]
+    for loc in locs:
+        loc[:, 2:] += 5.0 * float(np.log(12.0 / 240.0))      # boxes of about 12 px, not the anchors' 240: several survive NMS
+    clss = [torch.from_numpy(rs.uniform(1e-3, 1.0, size=(B, h * w)).astype(np.float32)) for h, w in levels]
+    corners = [torch.from_numpy(rs.uniform(0, 300, size=(B, 8, h * w)).astype(np.float32)) for h, w in levels]
+    return sizes, locs, clss, corners
+
+
+@pytest.mark.parametrize("levels,ids,route", [([(2, 3), (3, 4)], [7, 3, 7], "_decode_pyramid_fused"),
+                                              ([(3, 4)], [7, 3], "_decode_single_level_fused")])
+def test_the_three_routes_return_one_result_contract(levels, ids, route, device):
+    """What ``decode_pyramid`` returns does not depend on the route that made it: the generic chain, os2d_detect_pyramid (two
+    levels on images of 48x32 and 64x48, i.e. 3x2 and 4x3 locations, both resized to one frame, label 7 merged from two head
+    rows) and os2d_detect_level (the 4x3 level alone, one row per label) give the same image size, the same fields, and in each
+    of them the same values, dtype and device.  Scores in (0, 1) against a score threshold of 0 and boxes of about 12 px: every label keeps
+    4 to 12 boxes (counted for this seed with the decode oracle on the CPU), so no field is compared empty."""
+    from os2d_amd.modeling.box_coder import ResizeBoxes
+    from os2d_amd.structures.feature_map import FeatureMapSize
+    sizes, locs, clss, corners = _contract_inputs(levels, len(ids))
+    locs, clss, corners = [[t.to(device) for t in ts] for ts in (locs, clss, corners)]
+    common = FeatureMapSize(w=100, h=70)
+    inverse = [ResizeBoxes(common) for _ in levels]
+    coder = _coder()
+    assert getattr(coder, route)(locs, clss, sizes, ids, 0.0, 0.3, inverse, corners) is not None, "fused route not taken"
+    results = []
+    for fused in (False, True):
+        coder.use_fused_level_kernel = fused
+        results.append(coder.decode_pyramid(locs, clss, sizes, ids, nms_score_threshold=0.0, nms_iou_threshold=0.3,
+                                            inverse_box_transforms=inverse, transform_corners_pyramid=corners))
+    generic, fused = results
+    assert generic.image_size == fused.image_size == common
+    assert set(generic.fields()) == set(fused.fields()) == {"scores", "labels", "default_boxes", "transform_corners"}
+    assert set(generic.get_field("labels").tolist()) == set(ids)
+
+    def tensors(r):
+        return [r.bbox_xyxy, r.get_field("scores"), r.get_field("labels"), r.get_field("default_boxes").bbox_xyxy,
+                r.get_field("transform_corners")]
+    assert generic.get_field("default_boxes").image_size == fused.get_field("default_boxes").image_size == common
+    for g, f in zip(tensors(generic), tensors(fused)):
+        assert g.dtype == f.dtype and g.device == f.device
+        assert torch.equal(g, f)

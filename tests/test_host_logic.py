@@ -194,7 +194,7 @@ def test_trace_cache_sees_a_transform_list_that_grew_after_it_was_traced():
     import gc
     import weakref
     import util
-    from os2d_amd.modeling import box_coder as bc
+    from os2d_amd.modeling import box_ops as bc        # the module whose ``_probe_check`` the trace looks up
     size, orig = FeatureMapSize(w=320, h=272), FeatureMapSize(w=500, h=380)
     chain = util.InverseTransformList()
     assert not hasattr(chain, "transforms")            # the list lives in an attribute the round-5 key did not look at
@@ -223,6 +223,58 @@ def test_trace_cache_sees_a_transform_list_that_grew_after_it_was_traced():
     del chain
     gc.collect()
     assert ref() is None
+
+
+def test_box_coder_re_exports_the_box_op_module():
+    """The box-op chain code lives in box_ops.py; every name that used to be imported from box_coder.py is still there and is
+    the SAME object (no wrappers), and box_ops.py does not import box_coder.py back."""
+    import types
+    from os2d_amd.modeling import box_coder, box_ops
+    names = ("OP_SCALE", "OP_HFLIP", "OP_VFLIP", "OP_SHIFT", "MAX_BOX_OPS", "MAX_DEFAULT_BOX_OPS", "ResizeBoxes", "_BoxTrace",
+             "apply_box_ops", "_PROBE_BOXES", "transform_level_boxes", "trace_box_transform", "_TRACE_CACHE", "_trace_chains",
+             "_probe_check", "_trace_box_transform", "ops_tables", "_ops_tables", "traced_box_ops", "as_box_ops")
+    for name in names:
+        assert getattr(box_coder, name) is getattr(box_ops, name), name
+    assert box_coder._ops_tables is box_ops.ops_tables
+    from os2d_amd.structures import bounding_box          # the flips a traced closure names were reachable from box_coder too
+    assert (box_coder.FLIP_LEFT_RIGHT, box_coder.FLIP_TOP_BOTTOM) == (bounding_box.FLIP_LEFT_RIGHT, bounding_box.FLIP_TOP_BOTTOM)
+    assert not any(v is box_coder for v in vars(box_ops).values())
+    assert not any(isinstance(v, types.ModuleType) and v.__name__.endswith("box_coder") for v in vars(box_ops).values())
+
+
+@pytest.mark.parametrize("ids", [[1000, 3, 70], [5, 2, 5, 9, 2], [0, 1, 2, 3], [42]])
+def test_label_rows_follow_set_iteration_and_row_order(ids):
+    """reference box_coder.py:483 iterates ``set(class_ids)``: the labels come in that order, each with its head rows in
+    ascending row order, every row once."""
+    from os2d_amd.modeling.box_coder import _label_rows
+    got_ids, labels, rows_of = _label_rows(torch.tensor(ids))
+    assert got_ids == ids and all(type(c) is int for c in got_ids)
+    assert labels == list(set(ids)) and list(rows_of) == labels
+    for label in labels:
+        assert rows_of[label] == [i for i, c in enumerate(ids) if c == label]
+    assert sorted(i for rows in rows_of.values() for i in rows) == list(range(len(ids)))
+
+
+def test_as_box_ops_takes_recorded_chains_and_traces_callables():
+    from os2d_amd.modeling.box_coder import Os2dBoxCoder
+    from os2d_amd.modeling.box_ops import OP_HFLIP, OP_SCALE, OP_SHIFT, as_box_ops, traced_box_ops
+    from os2d_amd.structures.bounding_box import FLIP_LEFT_RIGHT
+    size, orig = FeatureMapSize(w=208, h=144), FeatureMapSize(w=500, h=380)
+    recorded = [[OP_SCALE, 2, 0.5], (OP_HFLIP, 416.0, 0.0), (OP_SHIFT, 3.0, 4.0)]
+    ops = as_box_ops(recorded, size)
+    assert ops == ((OP_SCALE, 2.0, 0.5), (OP_HFLIP, 416.0, 0.0), (OP_SHIFT, 3.0, 4.0))
+    assert isinstance(ops, tuple) and all(type(o) is tuple and [type(v) for v in o] == [int, float, float] for o in ops)
+    assert as_box_ops(ops, size) == ops and as_box_ops((), size) == ()
+    with pytest.raises(ValueError) as err:
+        as_box_ops([(1, 1.0, 1.0)] * 7, size)
+    assert str(err.value) == "a box-op chain has at most 6 entries of kind 1..4, got {}".format(((1, 1.0, 1.0),) * 7)
+    with pytest.raises(ValueError) as err:
+        as_box_ops([(5, 1.0, 1.0)], size)
+    assert str(err.value) == "a box-op chain has at most 6 entries of kind 1..4, got ((5, 1.0, 1.0),)"
+    flip_resize = lambda b: b.transpose(FLIP_LEFT_RIGHT).resize(orig)      # noqa: E731
+    assert as_box_ops(flip_resize, size) == traced_box_ops(flip_resize, size)[0] and len(as_box_ops(flip_resize, size)) == 2
+    assert as_box_ops(None, size) == ()
+    assert Os2dBoxCoder._chain(flip_resize, size) == as_box_ops(flip_resize, size)       # the coder's name for it
 
 
 def test_fixed_point_norm_sums_of_the_correlation_kernels():
