@@ -1,10 +1,11 @@
-"""In-tree build of the four HIP libraries for gfx950 with hipcc (no JIT cache: the .so files travel with the tree).
+"""In-tree build of the five HIP libraries for gfx950 with hipcc (no JIT cache: the .so files travel with the tree).
 
     python -m os2d_amd.build                      # build what is stale
     python -m os2d_amd.build --force
     python -m os2d_amd.build --train              # only libos2d_train.so (the head's backward pass)
     python -m os2d_amd.build --eval               # only libos2d_eval.so (the VOC detection metric)
     python -m os2d_amd.build --image              # only libos2d_image.so (the image pyramid from uint8 images)
+    python -m os2d_amd.build --augment            # only libos2d_augment.so (padded crops and colour distortion of training images)
     python -m os2d_amd.build --variant TAG [--packed on|off|fft] [-DFLAG ...]
                                                   # diagnostic copy under tools/diag_libs/TAG/ (run with OS2D_HIP_LIB=...)
 """
@@ -65,17 +66,26 @@ EVAL_CSRC = os.path.join(HERE, "csrc_eval")
 EVAL = Library("libos2d_eval.so", EVAL_CSRC, ["match.hip", "sort.hip", "metric.hip"], FLAGS + PACKED_OFF + ["-ffp-contract=off"], {},
                [EVAL_CSRC, CSRC, SHARED], "os2d_eval.h", "OS2D_EVAL_LIB")
 # The image pyramid from uint8 images (include/os2d_image.h).  Integer arithmetic and a table lookup: no floating-point
-# operation whose rounding a flag could change.  Its units include none of csrc/*.h.
+# operation whose rounding a flag could change.  Its units include none of csrc/*.h.  The kernel is a template in
+# csrc_image/resample_kernel.h, instantiated here for windows inside the image.
 IMAGE_CSRC = os.path.join(HERE, "csrc_image")
 IMAGE = Library("libos2d_image.so", IMAGE_CSRC, ["resample.hip"], FLAGS + PACKED_OFF, {}, [IMAGE_CSRC, SHARED], "os2d_image.h", "OS2D_IMAGE_LIB")
-LIBRARIES = [HIP, TRAIN, EVAL, IMAGE]
+# The training images (include/os2d_augment.h): the same resample template instantiated for windows that leave the image, and
+# PIL's colour operations.  A fifth library, because the kernel set and the ABI of libos2d_image.so are what they are (its two
+# kernels are pinned by its tests).  color.hip restates PIL's float arithmetic and every function of it that rounds switches
+# contraction off itself; the units include csrc_image/*.h and none of csrc/*.h.
+AUGMENT_CSRC = os.path.join(HERE, "csrc_augment")
+AUGMENT = Library("libos2d_augment.so", AUGMENT_CSRC, ["resample_padded.hip", "color.hip"], FLAGS + PACKED_OFF, {}, [AUGMENT_CSRC, IMAGE_CSRC, SHARED],
+                  "os2d_augment.h", "OS2D_AUGMENT_LIB")
+LIBRARIES = [HIP, TRAIN, EVAL, IMAGE]          # forward, backward, evaluation, image pyramid
+ALL_LIBRARIES = LIBRARIES + [AUGMENT]          # what build() makes
 
 
 def lib_path(lib):
     return os.path.join(LIB_DIR, lib.name)
 
 
-LIB_PATH, TRAIN_LIB_PATH, EVAL_LIB_PATH, IMAGE_LIB_PATH = [lib_path(lib) for lib in LIBRARIES]
+LIB_PATH, TRAIN_LIB_PATH, EVAL_LIB_PATH, IMAGE_LIB_PATH, AUGMENT_LIB_PATH = [lib_path(lib) for lib in ALL_LIBRARIES]
 
 
 def headers(lib=HIP):
@@ -188,14 +198,14 @@ def build_library(lib, force=False, verbose=True):
 
 def build(force=False, verbose=True):
     """Build every library that is stale (force: all of them).  Returns the forward library's path."""
-    for lib in LIBRARIES:
+    for lib in ALL_LIBRARIES:
         build_library(lib, force=force, verbose=verbose)
     return LIB_PATH
 
 
 # The names the per-library test fixtures call: each is the record's field or the one function bound to the record.
-TRAIN_SOURCES, EVAL_SOURCES, IMAGE_SOURCES = TRAIN.sources, EVAL.sources, IMAGE.sources
-build_train, build_eval, build_image = [functools.partial(build_library, lib) for lib in (TRAIN, EVAL, IMAGE)]
+TRAIN_SOURCES, EVAL_SOURCES, IMAGE_SOURCES, AUGMENT_SOURCES = TRAIN.sources, EVAL.sources, IMAGE.sources, AUGMENT.sources
+build_train, build_eval, build_image, build_augment = [functools.partial(build_library, lib) for lib in (TRAIN, EVAL, IMAGE, AUGMENT)]
 train_up_to_date = functools.partial(up_to_date, TRAIN)
 
 
@@ -222,7 +232,7 @@ if __name__ == "__main__":
         packed = argv[argv.index("--packed") + 1] if "--packed" in argv else None
         print(build_variant(tag, packed, [a for a in argv if a.startswith("-D")], verbose=True))
     else:
-        only = [lib for lib, switch in ((TRAIN, "--train"), (EVAL, "--eval"), (IMAGE, "--image")) if switch in argv]
+        only = [lib for lib, switch in ((TRAIN, "--train"), (EVAL, "--eval"), (IMAGE, "--image"), (AUGMENT, "--augment")) if switch in argv]
         if only:
             print(build_library(only[0], force="--force" in argv))
         else:

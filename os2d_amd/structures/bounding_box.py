@@ -104,6 +104,15 @@ class BoxList(object):
             return self[~self.get_mask_empty_boxes()]
         return self
 
+    def area(self):
+        """reference bounding_box.py:283-284 (torchvision's published ``box_area``)."""
+        b = self.bbox_xyxy
+        return (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+
+    @staticmethod
+    def create_empty(image_size):
+        return BoxList(torch.zeros(0, 4), image_size)
+
     def get_mask_empty_boxes(self):
         """reference bounding_box.py:278-280."""
         b = self.bbox_xyxy
@@ -123,3 +132,16 @@ def cat_boxlist(bboxes):
     for f in bboxes[0].fields():
         out.add_field(f, torch.cat([b.get_field(f) for b in bboxes], 0))
     return out
+
+
+def box_intersection_over_reference(boxes_reference, boxes):
+    """[N,M]: the share of every reference box's area that each of ``boxes`` covers (reference bounding_box.py:324-342, its
+    tensor expressions: on the CPU they give its bits)."""
+    if boxes_reference.image_size != boxes.image_size:
+        raise RuntimeError("boxlists should have same image size, got {}, {}".format(boxes_reference.image_size, boxes.image_size))
+    area_ref = boxes_reference.area()
+    box1, box2 = boxes_reference.bbox_xyxy, boxes.bbox_xyxy
+    lt = torch.max(box1[:, None, :2], box2[:, :2])
+    rb = torch.min(box1[:, None, 2:], box2[:, 2:])
+    wh = (rb - lt).clamp(min=0)
+    return wh[:, :, 0] * wh[:, :, 1] / area_ref[:, None]
