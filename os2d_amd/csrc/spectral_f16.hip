@@ -30,6 +30,14 @@
 //     X [c][pair][bin]: in quads this kernel's loads were 0.03 ms cheaper per 64 pairs, but the forward transform's stores
 //     (688 pieces of 32 bytes per image, 460 KB apart) 0.04 ms dearer (profiles/r03_spectral_layouts.txt).
 // XCD-aware order: the pair tiles of a bin group (which share the weight spectra) run on one XCD at about the same time.
+//
+// Layers of at most 64 outputs (the frequency-domain 5x5 layer 128 -> 64) run the same kernel in a 64-ROW SHAPE
+// (template parameter R64 of the kernel's body, picked by the kernel argument rows64, which the launcher sets for Cout <= 64;
+// $OS2D_GEMM_ROWS64=0 keeps the 128-row shape, for A/B timing):
+// 4 bins x 64 rows x 64 pairs per work-group, 2 bins per wave, 64 KB of LDS, and only output-channel half 0 of the packed weights
+// is ever addressed - the layout, the export and its size are unchanged, half 1 (zero rows) is allocated and not read.  At 64
+// pairs and 2752 bins the launch moves 451 instead of 631 MB and issues half the matrix instructions: 139 -> 107 us
+// (profiles/gemm_rows64/; an 8 bins x 64 rows decomposition was measured next to it: 115 us at 64 pairs, 1 % faster at 1024).
 #include "tile_common.h"
 
 namespace {
@@ -53,16 +61,29 @@ __device__ __forceinline__ void sh_lds_barrier() { asm volatile("s_waitcnt lgkmc
 // dft_mfma.hip writes, 4 channels x 4 bins = 128 contiguous bytes per work-group iteration): a k-step of 8 channels of one pair
 // is ONE 256-byte run, 8 lanes of a wave walk it in two 16-byte loads each - instead of the 32-byte pieces 22 KB apart of the
 // row layout X [C][NB][NBINS] (round 3: 2.5 of the kernel's 5.6 ms at 1024 pairs were spent on those).
-template <bool XQ>
-__global__ __launch_bounds__(SH_THR, 1) void spectral_gemm_f16_kernel(const u32x4* w16,            // [G][2][KS][8][2][2][64] units
-                                                                      const float* __restrict__ wscale,  // [128] 2^-wexp[o]
-                                                                      const f32x2* __restrict__ X,       // [C][NB][NBINS] | quads
-                                                                      f32x2* __restrict__ Y,             // [NBINS/4][NB][Cout][4] (XQ: blocked)
-                                                                      int NB, int C, int Cpad, int Cout, int NBINS, int G, float xscale,
-                                                                      int nunits) {
+//
+// R64: the 64-row shape for layers of at most 64 outputs (the 5x5 layer 128 -> 64: rows 64 .. 127 of its weight spectra are zero, and
+// the 128-row shape fetches, stores and multiplies them).  Only output-channel half 0 of the packed weights is addressed - the 2048
+// units of bin group g and k-step s at w16 + ((g * 2 + 0) * KS + s) * 2048 are exactly 8 bins x 64 rows, half 1 lies in the next
+// KS * 32 KB and is never read.  Work-group = 4 bins x 64 rows x 64 pairs: waves ot = wv & 1, pt = (wv >> 1) & 1, wv >> 2 = bin PAIR
+// 0-1 | 2-3 of the 4 bins: 2 bins per wave (half the accumulators), one 16-byte store per (pair, row); weight stage 16 KB (2
+// requests per thread and k-step instead of 4), spectra stage 16 KB as before: 64 KB of LDS.  Per output element the same three
+// products in the same k order as the 128-row shape: the same bits (tests/test_spectral_rows64_gpu.py).
+// Both shapes are ONE kernel per XQ (the library's kernel list, tests/golden/kernels.txt, is unchanged): the shape is a template
+// parameter of the body, the kernel picks the body by its uniform argument rows64 (which took the place of an argument G that
+// nothing read).
+template <bool XQ, bool R64>
+__device__ __forceinline__ void spectral_gemm_f16_body(const u32x4* w16,            // [G][2][KS][8][2][2][64] units
+                                                       const float* __restrict__ wscale,  // [128] 2^-wexp[o]
+                                                       const f32x2* __restrict__ X,       // [C][NB][NBINS] | quads
+                                                       f32x2* __restrict__ Y,             // [NBINS/4][NB][Cout][4] (XQ: blocked)
+                                                       int NB, int C, int Cpad, int Cout, int NBINS, float xscale, int nunits) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  u32x4* ldsW = reinterpret_cast<u32x4*>(smem);                 // [SH_WRING][SH_WSTAGE]
-  u32x4* ldsX = ldsW + SH_WRING * SH_WSTAGE;                    // [2][SH_STAGE]
+  constexpr int JB = R64 ? SH_WB / 2 : SH_WB;                  // bins per wave
+  constexpr int WSTAGE = R64 ? SH_STAGE : SH_WSTAGE;           // units of a weight stage
+  constexpr int NWL = WSTAGE / SH_THR, NXL = SH_STAGE / SH_THR;   // requests per thread and k-step: weights 4 | 2, spectra 2
+  u32x4* ldsW = reinterpret_cast<u32x4*>(smem);                 // [SH_WRING][WSTAGE]
+  u32x4* ldsX = ldsW + SH_WRING * WSTAGE;                       // [2][SH_STAGE]
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hw = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lidx = os2d_xcd_logical(blockIdx.x, gridDim.x);
@@ -73,12 +94,14 @@ __global__ __launch_bounds__(SH_THR, 1) void spectral_gemm_f16_kernel(const u32x
   const int bt = lg % nbt, g = lg / nbt;
   const int nb0 = bt * SH_NB, bin0 = g * SH_BINS + bh * SH_WB;
   const int KS = (C + SH_KC - 1) / SH_KC;
-  const int ot = wv & 3, pt = wv >> 2;        // the wave's tile: output channels 32 ot .., pairs 32 pt ..
+  // the wave's tile: output channels 32 ot .., pairs 32 pt ..; R64: of bin pair wbp of the work-group's 4 bins
+  const int ot = R64 ? wv & 1 : wv & 3, pt = R64 ? (wv >> 1) & 1 : wv >> 2;
+  const int wbp = R64 ? wv >> 2 : 0;
   const int wq = wv & 3, wh = wv >> 2;        // its share of the staging: quarter wq of output-channel half wh / channels 2 wh ..
 
-  f32x16 yr[SH_WB], yi[SH_WB];
+  f32x16 yr[JB], yi[JB];
 #pragma unroll
-  for (int j = 0; j < SH_WB; ++j)
+  for (int j = 0; j < JB; ++j)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       yr[j][r] = 0.f;
@@ -86,8 +109,10 @@ __global__ __launch_bounds__(SH_THR, 1) void spectral_gemm_f16_kernel(const u32x
     }
 
   // weights of k-step s for this work-group's 4 bins: 1024 contiguous units per output-channel half (waves 0-3 stage half 0,
-  // waves 4-7 half 1)
-  const u32x4* wbase = w16 + ((size_t)(g * 2 + wh) * KS) * (SH_BINS * 256) + bh * SH_STAGE;
+  // waves 4-7 half 1).  R64: half 0 only, wave wv stages eighth wv of its 1024 units
+  const u32x4* wbase = w16 + ((size_t)(g * 2 + (R64 ? 0 : wh)) * KS) * (SH_BINS * 256) + bh * SH_STAGE;
+#define SH_WRUN(K) (R64 ? wv * 2 + (K) : wq * 4 + (K))   // the thread's K-th 64-unit run of the stage (R64) | of its half
+#define SH_WPART (R64 ? 0 : wh * SH_STAGE)               // where that half starts in the LDS stage
   // REGISTER staging (round 4).  The LDS-DMA of round 3 (global_load_lds) looked like a 2-step-deep pipeline and was none: the
   // compiler treats a FLAT-encoded instruction that may touch LDS as returning out of order, and from the first DMA on every
   // vmcnt wait it inserts is vmcnt(0).  The one wait this loop needs - for the spectra registers before their conversion - thus
@@ -97,17 +122,18 @@ __global__ __launch_bounds__(SH_THR, 1) void spectral_gemm_f16_kernel(const u32x
   // spectra of step S + 2 into one of two register sets, multiplies step S, then moves the set requested a step ago (S + 1)
   // into the other LDS stage - vmcnt(6): this step's 4 + 2 requests stay in flight through the barrier and the next k-step's
   // matrix work.  Costs 32 registers and 4 LDS stores per thread and k-step; the LDS ring shrinks to 2 stages (96 KB in all).
-  u32x4 wra[4], wrb[4];
+  // (R64: 2 + 2 requests per k-step, vmcnt(4), 16 registers, 64 KB.)
+  u32x4 wra[NWL], wrb[NWL];
 #define SH_LOAD_W(S, wr)                                                                                            \
   {                                                                                                                 \
     const u32x4* src_ = wbase + (size_t)(S) * (SH_BINS * 256);                                                      \
-    _Pragma("unroll") for (int k_ = 0; k_ < 4; ++k_) wr[k_] = src_[(wq * 4 + k_) * 64 + lane];                      \
+    _Pragma("unroll") for (int k_ = 0; k_ < NWL; ++k_) wr[k_] = src_[SH_WRUN(k_) * 64 + lane];                      \
   }
-#define SH_LOAD_W1(S, wr, K) wr[K] = (wbase + (size_t)(S) * (SH_BINS * 256))[(wq * 4 + (K)) * 64 + lane];
+#define SH_LOAD_W1(S, wr, K) wr[K] = (wbase + (size_t)(S) * (SH_BINS * 256))[SH_WRUN(K) * 64 + lane];
 #define SH_STORE_W(S, wr)                                                                                           \
   {                                                                                                                 \
-    _Pragma("unroll") for (int k_ = 0; k_ < 4; ++k_)                                                                \
-        ldsW[((S) % SH_WRING) * SH_WSTAGE + wh * SH_STAGE + (wq * 4 + k_) * 64 + lane] = wr[k_];                    \
+    _Pragma("unroll") for (int k_ = 0; k_ < NWL; ++k_)                                                              \
+        ldsW[((S) % SH_WRING) * WSTAGE + SH_WPART + SH_WRUN(k_) * 64 + lane] = wr[k_];                             \
   }
   // spectra of k-step s: this thread owns pair xn, bins 2 xj / 2 xj + 1 and TWO channels (xg * 4 + wh * 2 + {0, 1}).  A wave
   // covers 16 pairs x (2 bin pairs x 2 channel groups): with one pair per lane a load instruction would touch 64 rows 5 MB
@@ -167,34 +193,43 @@ __global__ __launch_bounds__(SH_THR, 1) void spectral_gemm_f16_kernel(const u32x
   // instruction occupies its wave's issue slot for 60 - 180 cycles (MI355X guide, LDS-DMA issue cost), and as one burst in front of
   // the k-step - rounds 4 - 5 - all eight waves paid that with the matrix pipes idle (0.270 against 0.279 ms at 64 pairs, 2.76
   // against 2.81 at 1024: profiles/r06/gemm_burst_vs_spread_requests.txt).  Same order as the burst: the wait in front of the
-  // stores stays vmcnt(6).
+  // stores stays vmcnt(6).  Every request carries a LITERAL index (request R of NWL weight runs + NXL spectra pieces): computed from
+  // the unrolled bin index the 128-row shape got another schedule (profiles/gemm_rows64/static_checks.txt).  R64: two bins, so
+  // weights behind bin 0 and spectra behind bin 1.
+#define SH_REQUEST1(SN, WN, PN, R) /* request R of the k-step: the NWL weight runs, then the NXL spectra pieces */ \
+  if constexpr ((R) < NWL) {                                                                                        \
+    SH_LOAD_W1(SN, WN, R)                                                                                           \
+  } else if constexpr ((R) < NWL + NXL) {                                                                           \
+    SH_LOAD_X1(SN, PN, (R)-NWL)                                                                                     \
+  }
+#define SH_REQUEST2(SN, WN, PN, R)                                                                                  \
+  if constexpr ((R) < NWL + NXL) {                                                                                  \
+    SH_REQUEST1(SN, WN, PN, R)                                                                                      \
+    SH_REQUEST1(SN, WN, PN, (R) + 1)                                                                                \
+    __builtin_amdgcn_sched_barrier(0);                                                                              \
+  }
 #define SH_REQUESTS_HOOK(SN, WN, PN, J)                                                                             \
   if ((J) == 0) {                                                                                                   \
-    SH_LOAD_W1(SN, WN, 0)                                                                                           \
-    SH_LOAD_W1(SN, WN, 1)                                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                                                              \
+    SH_REQUEST2(SN, WN, PN, 0)                                                                                      \
   } else if ((J) == 1) {                                                                                            \
-    SH_LOAD_W1(SN, WN, 2)                                                                                           \
-    SH_LOAD_W1(SN, WN, 3)                                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                                                              \
+    SH_REQUEST2(SN, WN, PN, 2)                                                                                      \
   } else if ((J) == 2) {                                                                                            \
-    SH_LOAD_X1(SN, PN, 0)                                                                                           \
-    SH_LOAD_X1(SN, PN, 1)                                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                                                              \
+    SH_REQUEST2(SN, WN, PN, 4)                                                                                      \
   }
 #define SH_COMPUTE(S, SN, WN, PN)                                                                                         \
   {                                                                                                                 \
     /* [half][bin][group = hw][hi|lo][o 64] and [bin][group][hi|lo][pair 64] */                                     \
-    const u32x4* aB = ldsW + ((S) % SH_WRING) * SH_WSTAGE + (ot >> 1) * SH_STAGE + (hw * 2) * 64 + (ot & 1) * 32 + l31; \
-    const u32x4* bB = ldsX + ((S)&1) * SH_STAGE + (hw * 2) * 64 + pt * 32 + l31;                                    \
+    const u32x4* aB = ldsW + ((S) % SH_WRING) * WSTAGE + (R64 ? wbp * JB * 256 : (ot >> 1) * SH_STAGE) +            \
+                      (hw * 2) * 64 + (ot & 1) * 32 + l31;                                                          \
+    const u32x4* bB = ldsX + ((S)&1) * SH_STAGE + wbp * JB * 256 + (hw * 2) * 64 + pt * 32 + l31;                   \
     half8 bq[2][2];                                                                                                 \
     u32x4 kq[2][2];                                                                                                 \
     bq[0][0] = *reinterpret_cast<const half8*>(bB);                                                                 \
     bq[0][1] = *reinterpret_cast<const half8*>(bB + 64);                                                            \
     kq[0][0] = aB[0];                                                                                               \
     kq[0][1] = aB[64];                                                                                              \
-    _Pragma("unroll") for (int j = 0; j < SH_WB; ++j) {                                                             \
-      if (j + 1 < SH_WB) {                                                                                          \
+    _Pragma("unroll") for (int j = 0; j < JB; ++j) {                                                                \
+      if (j + 1 < JB) {                                                                                             \
         bq[(j + 1) & 1][0] = *reinterpret_cast<const half8*>(bB + (j + 1) * 256);                                   \
         bq[(j + 1) & 1][1] = *reinterpret_cast<const half8*>(bB + (j + 1) * 256 + 64);                              \
         kq[(j + 1) & 1][0] = aB[(j + 1) * 256];                                                                     \
@@ -252,6 +287,10 @@ __global__ __launch_bounds__(SH_THR, 1) void spectral_gemm_f16_kernel(const u32x
   if (s < KS) SH_STEP(s, wra, pfa, wrb, pfb)
 #undef SH_STEP
 #undef SH_REQUESTS_HOOK
+#undef SH_REQUEST1
+#undef SH_REQUEST2
+#undef SH_WRUN
+#undef SH_WPART
 #undef SH_LOAD_W1
 #undef SH_LOAD_X1
 #undef SH_LOAD_W
@@ -272,11 +311,26 @@ __global__ __launch_bounds__(SH_THR, 1) void spectral_gemm_f16_kernel(const u32x
       if (nb < NB) {
         float4* dst = XQ ? reinterpret_cast<float4*>(Y + ((qblk + (nb - nb0)) * Cout + o) * 4)
                          : reinterpret_cast<float4*>(Y + (((size_t)(bin0 >> 2) * NB + nb) * Cout + o) * 4);
-        dst[0] = make_float4(yr[0][r] * sc, yi[0][r] * sc, yr[1][r] * sc, yi[1][r] * sc);
-        dst[1] = make_float4(yr[2][r] * sc, yi[2][r] * sc, yr[3][r] * sc, yi[3][r] * sc);
+        if constexpr (R64) {
+          dst[wbp] = make_float4(yr[0][r] * sc, yi[0][r] * sc, yr[1][r] * sc, yi[1][r] * sc);
+        } else {
+          dst[0] = make_float4(yr[0][r] * sc, yi[0][r] * sc, yr[1][r] * sc, yi[1][r] * sc);
+          dst[1] = make_float4(yr[2][r] * sc, yi[2][r] * sc, yr[3][r] * sc, yi[3][r] * sc);
+        }
       }
     }
   }
+}
+
+template <bool XQ>
+__global__ __launch_bounds__(SH_THR, 1) void spectral_gemm_f16_kernel(const u32x4* w16, const float* __restrict__ wscale,
+                                                                      const f32x2* __restrict__ X, f32x2* __restrict__ Y, int NB, int C,
+                                                                      int Cpad, int Cout, int NBINS, int rows64, float xscale,
+                                                                      int nunits) {
+  if (rows64)
+    spectral_gemm_f16_body<XQ, true>(w16, wscale, X, Y, NB, C, Cpad, Cout, NBINS, xscale, nunits);
+  else
+    spectral_gemm_f16_body<XQ, false>(w16, wscale, X, Y, NB, C, Cpad, Cout, NBINS, xscale, nunits);
 }
 
 }  // namespace
@@ -300,20 +354,26 @@ int os2d_launch_spectral_gemm_f16(const void* w16, const float* X, float* Y, int
     os2d_set_error("spectral_gemm_f16: NBINS %d must be a multiple of %d and Cout %d <= %d", NBINS, SH_BINS, Cout, 2 * SH_OH);
     return -3;
   }
-  const int G = NBINS / SH_BINS, nbt = (NB + SH_NB - 1) / SH_NB;
-  const size_t lds = (size_t)(SH_WRING * SH_WSTAGE + 2 * SH_STAGE) * 16;
   if (x_quads && Cpad < C) {
     os2d_set_error("spectral_gemm_f16: channel stride %d < C %d", Cpad, C);
     return -1;
   }
-  auto kern = x_quads ? spectral_gemm_f16_kernel<true> : spectral_gemm_f16_kernel<false>;
-  if (int rc = os2d_set_dynamic_lds(kern, lds, "spectral_gemm_f16")) return rc;
-  const long long units = (long long)G * nbt * (SH_BINS / SH_WB);
+  // up to 64 output rows: the 64-row shape ($OS2D_GEMM_ROWS64=0, read once: the 128-row shape for all, for A/B timing)
+  static const bool rows64_env = [] {
+    const char* e = getenv("OS2D_GEMM_ROWS64");
+    return !(e && e[0] == '0');
+  }();
+  const bool r64 = Cout <= SH_OH && rows64_env;
+  const int G = NBINS / SH_BINS, nbt = (NB + SH_NB - 1) / SH_NB;
   const size_t KS = (size_t)(C + SH_KC - 1) / SH_KC;
   const float* wscale = reinterpret_cast<const float*>(static_cast<const char*>(w16) + (size_t)G * 2 * KS * SH_BINS * 256 * 16);
+  const size_t lds = (size_t)(SH_WRING * (r64 ? SH_STAGE : SH_WSTAGE) + 2 * SH_STAGE) * 16;      // 64 | 96 KB
+  const long long units = (long long)G * nbt * (SH_BINS / SH_WB);
   unsigned grid;
   if (int rc = os2d_xcd_grid(units, "spectral_gemm_f16", &grid)) return rc;
+  auto kern = x_quads ? spectral_gemm_f16_kernel<true> : spectral_gemm_f16_kernel<false>;
+  if (int rc = os2d_set_dynamic_lds(kern, lds, "spectral_gemm_f16")) return rc;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(SH_THR), lds, stream, static_cast<const u32x4*>(w16), wscale,
-                     reinterpret_cast<const f32x2*>(X), reinterpret_cast<f32x2*>(Y), NB, C, Cpad, Cout, NBINS, G, xscale, (int)units);
+                     reinterpret_cast<const f32x2*>(X), reinterpret_cast<f32x2*>(Y), NB, C, Cpad, Cout, NBINS, (int)r64, xscale, (int)units);
   return os2d_launched("spectral_gemm_f16");
 }
