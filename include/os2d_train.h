@@ -12,7 +12,7 @@
  * negative on error (-1 bad argument, -2 workspace too small, -3 unsupported shape, -4 HIP runtime error), described by
  * os2d_train_last_error() on the calling thread.  Arguments are checked before anything is launched.
  *
- * Arithmetic: fp32 throughout.  The matrix-shaped work (the transposed convolutions, the weight gradients, the two
+ * Arithmetic: fp32 throughout, unless a caller asks the *_ex entry points for the split-fp16 GEMMs.  The matrix-shaped work (the transposed convolutions, the weight gradients, the two
  * correlation GEMMs) runs on v_mfma_f32_16x16x4_f32.  Weight gradients reduce over NB * PLANE positions in split-K partial
  * sums that a second kernel adds in a fixed order: deterministic.  The resampling backward scatters into d corr with fp32
  * atomicAdd: the order of those additions is not fixed (as in torch's own grid_sample backward).                         */
@@ -78,6 +78,26 @@ int os2d_train_norm225_backward(const float* corr, const float* dxn, int NB, int
 size_t os2d_train_corr_workspace_floats(int A, int C, int H, int W);
 int os2d_train_corr_backward(const float* fm, const float* qp, const float* dcorr, int A, int B, int C, int H, int W, float* dfm,
                              float* dq, float* workspace, size_t workspace_floats, void* stream);
+
+/* ---- The same three GEMM-shaped entry points with a choice of arithmetic: arith 0 = fp32 (the functions above, bit for bit),
+ * 1 = "f16x3": every operand value is multiplied by a power of two, split into fp16 hi + lo where it is staged on chip, and
+ * the products hi*hi + hi*lo + lo*hi run on v_mfma_f32_32x32x16_f16 with fp32 accumulation; the result is within fp32
+ * rounding of the fp32 route.  The power of two comes from the operand's largest magnitude, found on the device by a short
+ * maxima pass per call (no host synchronisation): one per operand a GEMM reduces over as a whole (filters, qp, the normalised
+ * image map, both operands of a weight gradient), one per pair for the dy of a data gradient, one per image / per class for the
+ * dcorr of the two correlation GEMMs.  An all-zero operand gives exact zeros; a non-finite value reaches every output that
+ * depends on it as a non-finite value (with the whole of its slice: the slice is then converted unscaled).  Tensors, layouts
+ * and outputs (exact zeros at pad cells; split-K slices added in a fixed order) as above.  The f16x3 route keeps its maxima in
+ * the workspace: size it with the _ex functions (arith 0: the sizes above; 0 = bad argument).  Any other arith: -1.         */
+size_t os2d_train_conv_data_workspace_floats_ex(int arith, int layer, int P, int NB);
+int os2d_train_conv_backward_data_ex(int arith, int layer, int P, const float* w, const float* dy, int NB, int H, int W, float* dx,
+                                     float* workspace, size_t workspace_floats, void* stream);
+size_t os2d_train_conv_weight_slice_floats_ex(int arith, int layer, int P);
+int os2d_train_conv_backward_weight_ex(int arith, int layer, int P, const float* x, const float* dy, int NB, int H, int W, float* dw,
+                                       float* workspace, size_t workspace_floats, void* stream);
+size_t os2d_train_corr_workspace_floats_ex(int arith, int A, int B, int C, int H, int W);
+int os2d_train_corr_backward_ex(int arith, const float* fm, const float* qp, const float* dcorr, int A, int B, int C, int H, int W,
+                                float* dfm, float* dq, float* workspace, size_t workspace_floats, void* stream);
 
 /* ---- class map backward, the inverse of os2d_class_prepare_batch (head.py:241-268): q15 [B,C,225] the resized, NOT normalised
  * maps (cell order i*15 + j; os2d_class_prepare_batch with normalize = 0), dq [B,C,225] from os2d_train_corr_backward.  L2 over

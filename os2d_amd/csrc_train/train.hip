@@ -1,4 +1,5 @@
-// libos2d_train.so (include/os2d_train.h): the backward pass of the OS2D head on gfx950, fp32 throughout.
+// libos2d_train.so (include/os2d_train.h): the backward pass of the OS2D head on gfx950, fp32 throughout (the *_ex entry points
+// take the GEMMs to the split-fp16 kernel of gemm_f16x3.hip at arith = 1).
 //
 // Matrix-shaped work goes through ONE tiled GEMM kernel on v_mfma_f32_16x16x4_f32 (gemm16_kernel): 64 x 64 output tile per
 // 256-thread work-group (4 waves, each 2 x 2 blocks of 16 x 16), k-steps of 16 staged in LDS.  Operands are read through small
@@ -13,6 +14,9 @@
 #include "../../include/os2d_train.h"
 #include "../csrc/os2d_common.h"
 #include "../csrc/sample_decode.h"
+#include "train_gemm.h"     // the operand loaders and result stores of the GEMMs; the launchers of gemm_f16x3.hip
+
+using namespace os2d_train_gemm;
 
 namespace {
 
@@ -104,113 +108,6 @@ int gemm(LA la, LB lb, ST st, int M, int N, int K, int Z, int ksplit, hipStream_
   hipLaunchKernelGGL((gemm16_kernel<LA, LB, ST, B_KFAST>), grid, dim3(256), 0, stream, la, lb, st, M, N, K, ksplit);
   return os2d_launched(what);
 }
-
-// tap offset of the zero-bordered plane layout: flat distance of tap t = (dy, dx) of a KS x KS kernel
-struct Taps {
-  int ks, r, ws, t2;
-  __device__ __forceinline__ int off(int t) const {
-    const int dy = t / ks, dx = t - dy * ks;
-    return (dy - r) * ws + (dx - r);
-  }
-};
-
-// A(m, k) = w[m][k], row-major K columns
-struct LdRows {
-  const float* w;
-  int K;
-  __device__ __forceinline__ float operator()(int, int m, int k) const { return w[(size_t)m * K + k]; }
-};
-// B(k = (c, t), n) = x[z][c][n + off(t)] (zero outside the plane)
-struct LdShifted {
-  const float* x;
-  size_t zstride;
-  int PL;
-  Taps tp;
-  __device__ __forceinline__ float operator()(int z, int k, int n) const {
-    const int c = k / tp.t2, t = k - c * tp.t2;
-    const int idx = n + tp.off(t);
-    return (idx >= 0 && idx < PL) ? x[z * zstride + (size_t)c * PL + idx] : 0.f;
-  }
-};
-// out[z][m][n] of a plane buffer, zero at the pad cells
-struct StPlane {
-  float* out;
-  size_t zstride;
-  int PL, H, W;
-  __device__ __forceinline__ void operator()(int z, int m, int n, float v) const {
-    out[z * zstride + (size_t)m * PL + n] = os2d_interior(n, H, W) ? v : 0.f;
-  }
-};
-// weight gradient: A(o, k = (pair, n)) = dy[pair][o][n]
-struct LdPairRows {
-  const float* dy;
-  size_t zstride;
-  int PL;
-  __device__ __forceinline__ float operator()(int, int m, int k) const {
-    const int nb = k / PL, n = k - nb * PL;
-    return dy[nb * zstride + (size_t)m * PL + n];
-  }
-};
-// B(k = (pair, n), j = (c, t)) = x[pair][c][n + off(t)]
-struct LdPairShifted {
-  const float* x;
-  size_t zstride;
-  int PL;
-  Taps tp;
-  __device__ __forceinline__ float operator()(int, int k, int j) const {
-    const int nb = k / PL, n = k - nb * PL;
-    const int c = j / tp.t2, t = j - c * tp.t2;
-    const int idx = n + tp.off(t);
-    return (idx >= 0 && idx < PL) ? x[nb * zstride + (size_t)c * PL + idx] : 0.f;
-  }
-};
-struct StSlice {
-  float* part;
-  int M, N;
-  __device__ __forceinline__ void operator()(int z, int m, int n, float v) const {
-    part[((size_t)z * M + m) * N + n] = v;
-  }
-};
-// correlation backward, image side (z = image a): A(c, k = (b, p)) = qp[b][c][p], B(k, n) = dcorr[a*B*225 + k][n]
-struct LdClassT {
-  const float* qp;
-  int C;
-  __device__ __forceinline__ float operator()(int, int c, int k) const {
-    const int b = k / OS2D_K, p = k - b * OS2D_K;
-    return qp[((size_t)b * C + c) * OS2D_QROWS + p];
-  }
-};
-struct LdCorrRows {
-  const float* dcorr;
-  int B, HW;
-  __device__ __forceinline__ float operator()(int z, int k, int n) const {
-    return dcorr[((size_t)z * B * OS2D_K + k) * HW + n];
-  }
-};
-struct StDense {
-  float* out;
-  int M, N;
-  __device__ __forceinline__ void operator()(int z, int m, int n, float v) const { out[((size_t)z * M + m) * N + n] = v; }
-};
-// correlation backward, class side (z = class b): A(c, k = (a, n)) = fm[a][c][n] / (|fm[a][:,n]| + 1e-5),
-// B(k = (a, n), p) = dcorr[a*B + b][p][n]
-struct LdImageNorm {
-  const float* fm;
-  const float* rinv;
-  int C, HW;
-  __device__ __forceinline__ float operator()(int, int c, int k) const {
-    const int a = k / HW, n = k - a * HW;
-    return fm[((size_t)a * C + c) * HW + n] * rinv[(size_t)a * HW + n];
-  }
-};
-struct LdCorrCols {
-  const float* dcorr;
-  int B, HW;
-  __device__ __forceinline__ float operator()(int z, int k, int p) const {
-    const int a = k / HW, n = k - a * HW;
-    return dcorr[(((size_t)a * B + z) * OS2D_K + p) * HW + n];
-  }
-};
 
 // ------------------------------------------------------------------------------------------------ small kernels
 // Wt[c][o*T2 + t] = w[o][c][T2-1-t]: the filters of the transposed convolution
@@ -661,10 +558,21 @@ size_t os2d_train_conv_data_workspace_floats(int layer, int P) {
   return (size_t)L.cout * L.cin * L.ks * L.ks;
 }
 
-int os2d_train_conv_backward_data(int layer, int P, const float* w, const float* dy, int NB, int H, int W, float* dx,
-                                  float* workspace, size_t workspace_floats, void* stream) {
+size_t os2d_train_conv_data_workspace_floats_ex(int arith, int layer, int P, int NB) {
+  const size_t wf = os2d_train_conv_data_workspace_floats(layer, P);
+  if (arith == 0 || wf == 0) return arith == 0 ? wf : 0;
+  if (arith != 1 || NB < 1) return 0;
+  return wf + 1 + (size_t)NB;                 // the flipped filters, then the maxima words: the filters', one per pair of dy
+}
+
+int os2d_train_conv_backward_data_ex(int arith, int layer, int P, const float* w, const float* dy, int NB, int H, int W, float* dx,
+                                     float* workspace, size_t workspace_floats, void* stream) {
   os2d_clear_error();
   Layer L;
+  if (arith != 0 && arith != 1) {
+    os2d_set_error("os2d_train_conv_backward_data: bad arith %d (0 = fp32, 1 = f16x3)", arith);
+    return -1;
+  }
   if (!layer_shape(layer, P, &L)) {
     os2d_set_error("os2d_train_conv_backward_data: bad layer %d / P %d", layer, P);
     return -1;
@@ -679,13 +587,17 @@ int os2d_train_conv_backward_data(int layer, int P, const float* w, const float*
   }
   const int T2 = L.ks * L.ks;
   const size_t wf = (size_t)L.cout * L.cin * T2;
-  if (workspace_floats < wf) {
-    os2d_set_error("os2d_train_conv_backward_data: workspace %zu floats < %zu", workspace_floats, wf);
+  const size_t need = arith ? wf + 1 + (size_t)NB : wf;
+  if (workspace_floats < need) {
+    os2d_set_error("os2d_train_conv_backward_data: workspace %zu floats < %zu", workspace_floats, need);
     return -2;
   }
   hipLaunchKernelGGL(flip_weights_kernel, dim3(blocks(wf)), dim3(256), 0, os2d_stream(stream), w, L.cout, L.cin, T2, workspace);
   int rc = os2d_launched("flip_weights_kernel");
   if (rc) return rc;
+  if (arith)
+    return os2d_f16x3_conv_data(workspace, dy, dx, L.cout, L.cin, L.ks, NB, H, W, reinterpret_cast<unsigned*>(workspace + wf),
+                                os2d_stream(stream));
   const int PL = os2d_plane(H, W);
   const Taps tp{L.ks, L.ks / 2, os2d_ws(W), T2};
   const int K = L.cout * T2;
@@ -693,12 +605,29 @@ int os2d_train_conv_backward_data(int layer, int P, const float* w, const float*
                      PL, K, NB, 0, os2d_stream(stream), "conv data gradient");
 }
 
+int os2d_train_conv_backward_data(int layer, int P, const float* w, const float* dy, int NB, int H, int W, float* dx,
+                                  float* workspace, size_t workspace_floats, void* stream) {
+  return os2d_train_conv_backward_data_ex(0, layer, P, w, dy, NB, H, W, dx, workspace, workspace_floats, stream);
+}
+
 size_t os2d_train_conv_weight_slice_floats(int layer, int P) { return os2d_train_conv_data_workspace_floats(layer, P); }
 
-int os2d_train_conv_backward_weight(int layer, int P, const float* x, const float* dy, int NB, int H, int W, float* dw,
-                                    float* workspace, size_t workspace_floats, void* stream) {
+// f16x3: every slice of room carries WEIGHT_WORDS floats more; the maxima words take the first WEIGHT_WORDS floats of the workspace
+constexpr size_t WEIGHT_WORDS = 16;
+size_t os2d_train_conv_weight_slice_floats_ex(int arith, int layer, int P) {
+  const size_t slice = os2d_train_conv_weight_slice_floats(layer, P);
+  if (arith == 0 || slice == 0) return arith == 0 ? slice : 0;
+  return arith == 1 ? slice + WEIGHT_WORDS : 0;
+}
+
+int os2d_train_conv_backward_weight_ex(int arith, int layer, int P, const float* x, const float* dy, int NB, int H, int W, float* dw,
+                                       float* workspace, size_t workspace_floats, void* stream) {
   os2d_clear_error();
   Layer L;
+  if (arith != 0 && arith != 1) {
+    os2d_set_error("os2d_train_conv_backward_weight: bad arith %d (0 = fp32, 1 = f16x3)", arith);
+    return -1;
+  }
   if (!layer_shape(layer, P, &L)) {
     os2d_set_error("os2d_train_conv_backward_weight: bad layer %d / P %d", layer, P);
     return -1;
@@ -719,22 +648,36 @@ int os2d_train_conv_backward_weight(int layer, int P, const float* x, const floa
     os2d_set_error("os2d_train_conv_backward_weight: NB * PLANE = %lld positions exceed the 32-bit index", K);
     return -3;
   }
-  long long splits = (long long)(workspace_floats / slice);
+  const size_t room = arith ? slice + WEIGHT_WORDS : slice;
+  const int kstep = arith ? OS2D_F16X3_KSTEP : GK;
+  long long splits = (long long)(workspace_floats / room);
   if (splits < 1) {
-    os2d_set_error("os2d_train_conv_backward_weight: workspace %zu floats < one slice of %zu", workspace_floats, slice);
+    os2d_set_error("os2d_train_conv_backward_weight: workspace %zu floats < one slice of %zu", workspace_floats, room);
     return -2;
   }
   if (splits > 64) splits = 64;
-  if (splits > (K + GK - 1) / GK) splits = (K + GK - 1) / GK;
-  const int ksplit = (int)(((K + splits - 1) / splits + GK - 1) / GK * GK);
+  if (splits > (K + kstep - 1) / kstep) splits = (K + kstep - 1) / kstep;
+  const int ksplit = (int)(((K + splits - 1) / splits + kstep - 1) / kstep * kstep);
   splits = (K + ksplit - 1) / ksplit;
-  const Taps tp{L.ks, L.ks / 2, os2d_ws(W), T2};
-  const int N = L.cin * T2;
-  int rc = gemm<true>(LdPairRows{dy, (size_t)L.cout * PL, PL}, LdPairShifted{x, (size_t)input_planes(layer) * PL, PL, tp},
-                      StSlice{workspace, L.cout, N}, L.cout, N, (int)K, (int)splits, ksplit, os2d_stream(stream), "conv weight gradient");
+  float* part = arith ? workspace + WEIGHT_WORDS : workspace;
+  int rc;
+  if (arith) {
+    rc = os2d_f16x3_conv_weight(x, input_planes(layer), dy, part, L.cout, L.cin, L.ks, NB, H, W, (int)splits, ksplit,
+                                reinterpret_cast<unsigned*>(workspace), os2d_stream(stream));
+  } else {
+    const Taps tp{L.ks, L.ks / 2, os2d_ws(W), T2};
+    const int N = L.cin * T2;
+    rc = gemm<true>(LdPairRows{dy, (size_t)L.cout * PL, PL}, LdPairShifted{x, (size_t)input_planes(layer) * PL, PL, tp},
+                    StSlice{workspace, L.cout, N}, L.cout, N, (int)K, (int)splits, ksplit, os2d_stream(stream), "conv weight gradient");
+  }
   if (rc) return rc;
-  hipLaunchKernelGGL(split_sum_kernel, dim3(blocks(slice)), dim3(256), 0, os2d_stream(stream), workspace, (int)splits, slice, dw);
+  hipLaunchKernelGGL(split_sum_kernel, dim3(blocks(slice)), dim3(256), 0, os2d_stream(stream), part, (int)splits, slice, dw);
   return os2d_launched("split_sum_kernel");
+}
+
+int os2d_train_conv_backward_weight(int layer, int P, const float* x, const float* dy, int NB, int H, int W, float* dw,
+                                    float* workspace, size_t workspace_floats, void* stream) {
+  return os2d_train_conv_backward_weight_ex(0, layer, P, x, dy, NB, H, W, dw, workspace, workspace_floats, stream);
 }
 
 int os2d_train_norm225_backward(const float* corr, const float* dxn, int NB, int H, int W, float* dcorr, void* stream) {
@@ -758,9 +701,20 @@ size_t os2d_train_corr_workspace_floats(int A, int C, int H, int W) {
   return 2 * (size_t)A * HW + (size_t)A * C * HW;
 }
 
-int os2d_train_corr_backward(const float* fm, const float* qp, const float* dcorr, int A, int B, int C, int H, int W, float* dfm,
-                             float* dq, float* workspace, size_t workspace_floats, void* stream) {
+size_t os2d_train_corr_workspace_floats_ex(int arith, int A, int B, int C, int H, int W) {
+  const size_t base = os2d_train_corr_workspace_floats(A, C, H, W);
+  if (arith == 0 || base == 0) return arith == 0 ? base : 0;
+  if (arith != 1 || B < 1) return 0;
+  return base + 2 + (size_t)A + B;            // the maxima words: qp, the normalised image map, dcorr per image, dcorr per class
+}
+
+int os2d_train_corr_backward_ex(int arith, const float* fm, const float* qp, const float* dcorr, int A, int B, int C, int H, int W,
+                                float* dfm, float* dq, float* workspace, size_t workspace_floats, void* stream) {
   os2d_clear_error();
+  if (arith != 0 && arith != 1) {
+    os2d_set_error("os2d_train_corr_backward: bad arith %d (0 = fp32, 1 = f16x3)", arith);
+    return -1;
+  }
   if (!fm || !qp || !dcorr || !workspace) {
     os2d_set_error("os2d_train_corr_backward: null pointer");
     return -1;
@@ -774,7 +728,8 @@ int os2d_train_corr_backward(const float* fm, const float* qp, const float* dcor
     os2d_set_error("os2d_train_corr_backward: reduction length exceeds the 32-bit index");
     return -3;
   }
-  const size_t need = os2d_train_corr_workspace_floats(A, C, H, W);
+  const size_t base = os2d_train_corr_workspace_floats(A, C, H, W);
+  const size_t need = arith ? base + 2 + (size_t)A + B : base;
   if (workspace_floats < need) {
     os2d_set_error("os2d_train_corr_backward: workspace %zu floats < %zu", workspace_floats, need);
     return -2;
@@ -785,6 +740,13 @@ int os2d_train_corr_backward(const float* fm, const float* qp, const float* dcor
   hipLaunchKernelGGL(image_norm_kernel, dim3(blocks(HW), A), dim3(256), 0, os2d_stream(stream), fm, C, (int)HW, rinv);
   int rc = os2d_launched("image_norm_kernel");
   if (rc) return rc;
+  if (arith) {
+    rc = os2d_f16x3_corr(fm, rinv, qp, dcorr, A, B, C, (int)HW, dfm ? dfh : nullptr, dq, reinterpret_cast<unsigned*>(workspace + base),
+                         os2d_stream(stream));
+    if (rc || !dfm) return rc;
+    hipLaunchKernelGGL(image_norm_backward_kernel, dim3(blocks(HW), A), dim3(256), 0, os2d_stream(stream), fm, dfh, C, (int)HW, dfm);
+    return os2d_launched("image_norm_backward_kernel");
+  }
   if (dfm) {
     rc = gemm<false>(LdClassT{qp, C}, LdCorrRows{dcorr, B, (int)HW}, StDense{dfh, C, (int)HW}, C, (int)HW, B * OS2D_K, A, 0, os2d_stream(stream),
                      "correlation backward (image)");
@@ -797,6 +759,11 @@ int os2d_train_corr_backward(const float* fm, const float* qp, const float* dcor
     rc = gemm<true>(LdImageNorm{fm, rinv, C, (int)HW}, LdCorrCols{dcorr, B, (int)HW}, StDense{dq, C, OS2D_K}, C, OS2D_K, A * (int)HW, B,
                     0, os2d_stream(stream), "correlation backward (class)");
   return rc;
+}
+
+int os2d_train_corr_backward(const float* fm, const float* qp, const float* dcorr, int A, int B, int C, int H, int W, float* dfm,
+                             float* dq, float* workspace, size_t workspace_floats, void* stream) {
+  return os2d_train_corr_backward_ex(0, fm, qp, dcorr, A, B, C, H, W, dfm, dq, workspace, workspace_floats, stream);
 }
 
 int os2d_train_class_backward(const float* q15, const float* dq, int B, int C, float* const* dsrcs, const int* sizes,

@@ -452,6 +452,9 @@ class Os2dHeadCreator(nn.Module):
         self.box_grid_generator_image_level = BoxGridGenerator(box_size=rec_field, box_stride=stride)
         self.box_grid_generator_feature_map_level = BoxGridGenerator(box_size=self.aligner.network_receptive_field,
                                                                      box_stride=self.aligner.network_stride)
+        # arithmetic of the backward GEMMs of the heads this creator makes (head_train.TRAIN_PRECISIONS); None: follow
+        # $OS2D_TRAIN_PRECISION (default "f32")
+        self.train_precision = None
 
     @staticmethod
     def get_rec_field_and_stride_after_concat_nets(receptive_field_netA, stride_netA, receptive_field_netB, stride_netB):
@@ -479,6 +482,7 @@ class Os2dHeadCreator(nn.Module):
         if isinstance(class_feature_maps, torch.Tensor):
             class_feature_maps = [m.unsqueeze(0) for m in class_feature_maps]
         head._raw_class_maps = list(class_feature_maps)
+        head.train_precision = self.train_precision         # a training step builds a new head per batch
         return head
 
 
@@ -565,6 +569,8 @@ class Os2dHead(nn.Module):
         self.aligner = aligner
         self.last_precision = None
         self.precision = None      # None: follow $OS2D_PRECISION (default "fftx3"); or one of PRECISIONS
+        self.train_precision = None        # backward GEMMs under autograd: None = $OS2D_TRAIN_PRECISION (default "f32"), "f32", "f16x3"
+        self.last_train_precision = None   # the one the last training forward resolved (head_train.py)
         # sticky status word of the split-fp16 kernels in mapped pinned host memory (one per device, process lifetime:
         # ``device_status_word``): the kernels store to it only when an activation leaves the fp16 range (impossible for
         # finite inputs, see TransformationNet.range_plan), the host reads it without synchronising

@@ -7,10 +7,13 @@ the backward pass of libos2d_train.so (include/os2d_train.h), wrapped in one ``t
   * the raw class maps (through the class L2 normalisation and the bilinear resize to 15 x 15),
   * the TransformNet: conv.0 / conv.3 / linear weights and biases and the affine parameters of the frozen (eval-mode)
     BatchNorms conv.1 / conv.4 (weight = gamma, bias = beta); the running statistics stay constants.
+The five GEMM-shaped launches of the backward pass run in fp32 or, with ``train_precision = "f16x3"`` on the head or its
+creator (or $OS2D_TRAIN_PRECISION), in split-fp16 arithmetic within fp32 rounding of it.
 As in the reference (head.py:396-402, 423): ``cls_det`` carries the same values as ``cls`` but its gradient reaches the
 correlation only, not the transformation; ``corners`` carries none.
 """
 import ctypes
+import os
 
 import torch
 
@@ -19,6 +22,19 @@ from .. import _train_lib
 
 TEMPLATE = 15
 MAX_W_DIRECT7 = 209
+# arithmetic of the backward pass's five GEMM launches (the `arith` argument of the *_ex entry points of include/os2d_train.h):
+# "f32" = v_mfma_f32_16x16x4_f32, "f16x3" = split-fp16 operands on v_mfma_f32_32x32x16_f16, within fp32 rounding of "f32".  The
+# training FORWARD is the strict-fp32 route either way.
+TRAIN_PRECISIONS = ("f32", "f16x3")
+DEFAULT_TRAIN_PRECISION = "f32"
+
+
+def resolve_train_precision(value=None):
+    """``value`` (a head's or a creator's ``train_precision``) or, for None, $OS2D_TRAIN_PRECISION (default "f32")."""
+    value = value or os.environ.get("OS2D_TRAIN_PRECISION") or DEFAULT_TRAIN_PRECISION
+    if value not in TRAIN_PRECISIONS:
+        raise ValueError("unknown train_precision {!r}: one of {}".format(value, TRAIN_PRECISIONS))
+    return value
 
 
 def _ptr(t):
@@ -68,6 +84,7 @@ class _HeadFunction(torch.autograd.Function):
             from .head import _prepare_class_maps
             q15raw, _ = _prepare_class_maps(list(raws), normalise=False)
         ctx.head, ctx.n_class, ctx.shape = head, n_class, (A, B, C, H, W, P, inverse, PL)
+        ctx.arith = TRAIN_PRECISIONS.index(head.last_train_precision)
         ctx.saved = dict(fm=fm, raws=raws, corr=corr, rnorm=rnorm, h1=h1, h2=h2, params=prm, q15raw=q15raw,
                          weights=[p.detach().contiguous() for p in params])
         ctx.mark_non_differentiable(corners)
@@ -78,6 +95,7 @@ class _HeadFunction(torch.autograd.Function):
         tl = _train_lib.load()
         head, n_class = ctx.head, ctx.n_class
         A, B, C, H, W, P, inverse, PL = ctx.shape
+        arith = ctx.arith
         sv = ctx.saved
         NB, HW = A * B, H * W
         fm = sv["fm"]
@@ -105,18 +123,18 @@ class _HeadFunction(torch.autograd.Function):
             splits = _wgrad_splits(NB, PL)
 
             def wgrad(layer, x, dy, like):
-                n = int(tl.os2d_train_conv_weight_slice_floats(layer, P))
+                n = int(tl.os2d_train_conv_weight_slice_floats_ex(arith, layer, P))
                 ws = torch.empty(n * splits, **f32)
                 dw = torch.empty_like(like)
-                _train_lib.check(tl.os2d_train_conv_backward_weight(layer, P, _ptr(x), _ptr(dy), NB, H, W, _ptr(dw), _ptr(ws), ws.numel(), s),
-                                 "os2d_train_conv_backward_weight")
+                _train_lib.check(tl.os2d_train_conv_backward_weight_ex(arith, layer, P, _ptr(x), _ptr(dy), NB, H, W, _ptr(dw), _ptr(ws),
+                                                                       ws.numel(), s), "os2d_train_conv_backward_weight_ex")
                 return dw
 
             def dgrad(layer, w, dy, cin):
-                ws = torch.empty(int(tl.os2d_train_conv_data_workspace_floats(layer, P)), **f32)
+                ws = torch.empty(int(tl.os2d_train_conv_data_workspace_floats_ex(arith, layer, P, NB)), **f32)
                 dx = torch.empty(NB * cin * PL, **f32)
-                _train_lib.check(tl.os2d_train_conv_backward_data(layer, P, _ptr(w), _ptr(dy), NB, H, W, _ptr(dx), _ptr(ws), ws.numel(), s),
-                                 "os2d_train_conv_backward_data")
+                _train_lib.check(tl.os2d_train_conv_backward_data_ex(arith, layer, P, _ptr(w), _ptr(dy), NB, H, W, _ptr(dx), _ptr(ws),
+                                                                     ws.numel(), s), "os2d_train_conv_backward_data_ex")
                 return dx
 
             def bn_relu(layer, dh, h, bn, gamma, beta, cout, ig, ib, iw):
@@ -154,11 +172,11 @@ class _HeadFunction(torch.autograd.Function):
                     _train_lib.check(tl.os2d_train_norm225_backward(_ptr(sv["corr"]), _ptr(dxn), NB, H, W, _ptr(dcorr), s),
                                      "os2d_train_norm225_backward")
             if need_fm or need_cls:
-                ws = torch.empty(int(tl.os2d_train_corr_workspace_floats(A, C, H, W)), **f32)
+                ws = torch.empty(int(tl.os2d_train_corr_workspace_floats_ex(arith, A, B, C, H, W)), **f32)
                 dfm = torch.empty(A, C, H, W, **f32) if need_fm else None
                 dq = torch.empty(B, C, 225, **f32) if need_cls else None
-                _train_lib.check(tl.os2d_train_corr_backward(_ptr(fm), _ptr(head._qp), _ptr(dcorr), A, B, C, H, W, _ptr(dfm), _ptr(dq),
-                                                             _ptr(ws), ws.numel(), s), "os2d_train_corr_backward")
+                _train_lib.check(tl.os2d_train_corr_backward_ex(arith, _ptr(fm), _ptr(head._qp), _ptr(dcorr), A, B, C, H, W, _ptr(dfm),
+                                                                _ptr(dq), _ptr(ws), ws.numel(), s), "os2d_train_corr_backward_ex")
                 if need_cls:
                     raws = sv["raws"]
                     draws = [torch.empty(r.shape, **f32) for r in raws]
@@ -189,7 +207,10 @@ def needs_grad(head, feature_maps):
 
 
 def head_forward_train(head, feature_maps):
-    """(loc, cls, cls_det, corners) of ``Os2dHead.forward`` with autograd (see the module docstring)."""
+    """(loc, cls, cls_det, corners) of ``Os2dHead.forward`` with autograd (see the module docstring).  The arithmetic of the
+    backward GEMMs is ``head.train_precision`` (None: $OS2D_TRAIN_PRECISION, default "f32"); the one taken is recorded in
+    ``head.last_train_precision``."""
+    head.last_train_precision = resolve_train_precision(head.train_precision)
     A, C, H, W = feature_maps.shape
     if W > MAX_W_DIRECT7:
         raise RuntimeError("autograd through the HIP head needs feature maps at most {} columns wide (the direct 7x7 kernels of the "

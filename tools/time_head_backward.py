@@ -3,7 +3,10 @@ the HIP training forward (the "f32" route with its intermediates kept) and the H
 the same step done eagerly by torch: the oracle's ``head_forward`` under autograd on the same GPU.
 
     python tools/time_head_backward.py [--reps N] [--no-eager] [--A 4 --B 15 --C 1024 --H 38 --W 38]
+                                       [--train-precision f32|f16x3|both]
 
+``--train-precision``: the arithmetic of the backward GEMMs (default: $OS2D_TRAIN_PRECISION, else "f32"); ``both`` times
+f32, f16x3 and f32 again in one process - the two f32 figures show the spread of the box.
 Per-kernel times: run it under ``rocprofv3 --kernel-trace --stats -- python tools/time_head_backward.py --reps 1 --no-eager``.
 Prints one JSON line."""
 import argparse
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--W", type=int, default=38)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--no-eager", action="store_true")
+    ap.add_argument("--train-precision", choices=["f32", "f16x3", "both"], default=None)
     a = ap.parse_args()
     from os2d_amd.modeling.head import build_os2d_head_creator
     from os2d_amd.structures.feature_map import FeatureMapSize
@@ -65,8 +69,18 @@ def main():
         ((loc * gl).sum() + (cls * gc).sum() + (cls_det * gc).sum()).backward()
         return loc
 
-    fwd, bwd = timed(hip_step)
-    res = {"shape": [a.A, a.B, a.C, a.H, a.W], "hip_forward_ms": round(fwd, 3), "hip_backward_ms": round(bwd, 3)}
+    res = {"shape": [a.A, a.B, a.C, a.H, a.W]}
+    if a.train_precision == "both":
+        for key, precision in (("f32", "f32"), ("f16x3", "f16x3"), ("f32_again", "f32")):
+            creator.train_precision = precision
+            fwd, bwd = timed(hip_step)
+            res[key] = {"hip_forward_ms": round(fwd, 3), "hip_backward_ms": round(bwd, 3)}
+    else:
+        creator.train_precision = a.train_precision
+        fwd, bwd = timed(hip_step)
+        head = creator.create_os2d_head(raws)
+        head(fm)
+        res.update({"train_precision": head.last_train_precision, "hip_forward_ms": round(fwd, 3), "hip_backward_ms": round(bwd, 3)})
     if not a.no_eager:
         st = {k: v.to(dev).requires_grad_(k.endswith("weight") or k.endswith("bias")) for k, v in state.items()}
 
