@@ -496,7 +496,9 @@ static int detect_pyramid_impl(const float* const* loc, const float* const* cls,
   if (rc) return rc;
   hipLaunchKernelGGL(pyr_compact_kernel, dim3(G), dim3(NTHR), 0, st, N, M, keys, ids[0], counts, final_pass);
   if ((rc = os2d_launched("pyr_compact"))) return rc;
-  const int NP2 = os2d_next_pow2(min(M, N));
+  // at least 64: pyr_chunk_nms_kernel sorts the next power of two of a chunk's size but never fewer than 64 keys, and lays its
+  // LDS arrays out for NP2 of them (with 32 candidates or fewer per label the key and position arrays overlapped)
+  const int NP2 = max(64, os2d_next_pow2(min(M, N)));
   const size_t lds = (size_t)NP2 * 6 + (((size_t)M * 2 + 15) & ~(size_t)15) + (size_t)KCAP * 16;
   if ((rc = os2d_set_dynamic_lds(pyr_chunk_nms_kernel, lds, "detect_pyramid"))) return rc;
   if ((rc = os2d_set_dynamic_lds(pyr_finalize_kernel, (size_t)16384 * 6, "detect_pyramid"))) return rc;
