@@ -131,8 +131,8 @@ int os2d_class_split(const float* qp, void* qs, int B, int C, void* stream);
  *                 store the call's epoch into range words at the start of the workspace (one per image, one for the whole call)
  *                 and the last kernel writes NaN into loc / cls / corners of every flagged image, as the reference's
  *                 torch.relu / norm propagate a NaN (head.py:339, 650) - no host synchronisation, later calls unaffected.  The
- *                 words are never cleared (a stale epoch matches no later call); zero-fill the first 4 KB of a NEW workspace
- *                 once so that its initial content cannot match either.  A caller that wants the reference's exact NaN
+ *                 words are never cleared (a stale epoch matches no later call); zero-fill the first (A + 1) * 4 bytes - the range
+ *                 words - of a NEW workspace once so that its initial content cannot match either.  A caller that wants the reference's exact NaN
  *                 pattern re-runs a flagged call in OS2D_PRECISION_F32, whose kernels keep NaN through their ReLUs;
  *   wspec, twQ, twP  the frequency-domain precisions only (NULL otherwise; w1 / b1..b3 / w2 / w3 as for F16X3, FFT32: as for F32):
  *                 OS2D_PRECISION_FFT / _FFT32: the weight spectra of the 7x7 layer for THIS map's transform size in the layout of

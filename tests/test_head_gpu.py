@@ -113,6 +113,71 @@ def test_image_batch_chunking_and_cat(precision, device, monkeypatch):
         assert util.maxdiff(out_cat[i], out_full[i]) == 0.0
 
 
+ROUTE_SHAPES = {"9x14": (2, 5, 9, 14), "5x212": (1, 3, 5, 212)}      # A, B, H, W at C = 32, P = 6; 5 x 212: wider than the direct kernels, tiled in x
+_route_heads = {}
+
+
+def _route_head(shape, device):
+    """(head, feature maps) of a shape, built once for all its precisions"""
+    if shape not in _route_heads:
+        from os2d_amd.utils import synthetic
+        A, B, H, W = ROUTE_SHAPES[shape]
+        creator = util.make_head_creator(6, True, synthetic.make_transform_net_state(6, seed=7), device)
+        class_fms = synthetic.make_class_feature_maps(B, 32, sizes=[(15, 15), (14, 16), (16, 14)], seed=500)
+        with torch.no_grad():
+            head = creator.create_os2d_head([c.to(device) for c in class_fms])
+        _route_heads[shape] = head, synthetic.make_feature_map(32, H, W, seed=5, A=A).to(device)
+    return _route_heads[shape]
+
+
+def _forward_ex2(head, fm, precision, workspace_bytes):
+    """os2d_head_forward_ex2 through ctypes on a zero-filled workspace of exactly that size: (chunk_classes, [loc, cls, corners])"""
+    import ctypes
+    from os2d_amd import _lib
+    from os2d_amd.modeling import head as head_mod
+    lib, ptr, dev = _lib.load(), _lib.ptr, fm.device
+    A, C, H, W = fm.shape
+    B = head.class_batch_size
+    net = head.aligner.parameter_regressor
+    spectra = net.spectra(H, W, split=precision == "fftx3")[:3] if precision in head_mod.FFT_MODES else (None, None, None)
+    spectra2 = net.spectra2(H, W) if precision == "fftx3" else None
+    packed = net.packed(precision)
+    qs = head._split_class_operand() if precision not in head_mod.FP32_MODES else None
+    out = [torch.full((A, B, k, H, W), float("nan"), device=dev) for k in (4, 1, 8)]      # a cell nobody writes stays NaN: never equal
+    ws = torch.zeros(workspace_bytes, dtype=torch.uint8, device=dev)
+    chunk = ctypes.c_int(0)
+    _lib.check(lib.os2d_head_forward_ex2(
+        ptr(fm), ptr(head._qp), *[ptr(t) for t in packed], A, B, C, H, W, 6, 1, head._stride, head._rec_field, *[ptr(t) for t in out],
+        ptr(ws), ws.numel(), _lib.current_stream(dev), head_mod.PRECISIONS[precision], ptr(qs), None, ctypes.byref(chunk), None,
+        *[ptr(t) for t in spectra], ptr(spectra2)), "os2d_head_forward_ex2")
+    torch.cuda.synchronize()
+    return chunk.value, out
+
+
+@pytest.mark.parametrize("shape,precision", [("9x14", p) for p in PRECISIONS] + [("5x212", p) for p in ("fftx3", "fft", "fft32")])
+def test_size_entry_point_and_forward_call_carve_the_same_workspace(shape, precision, device):
+    """What os2d_head_workspace_bytes_ex reports is what os2d_head_forward_ex2 carves (both go through one route record in abi.hip;
+    Os2dHead.forward passes chunk_classes = NULL, so nothing else sees it): a workspace of exactly the reported size takes all B
+    classes in one chunk, 256 bytes less - one unit of the carve's alignment - no longer does, the size reported for 2 classes
+    gives chunks of exactly 2, and the chunking changes no bit of the outputs."""
+    import ctypes
+    from os2d_amd import _lib
+    from os2d_amd.modeling import head as head_mod
+    head, fm = _route_head(shape, device)
+    A, B, H, W = ROUTE_SHAPES[shape]
+    full, two = ctypes.c_size_t(), ctypes.c_size_t()
+    for classes, n in ((B, full), (2, two)):
+        _lib.check(_lib.load().os2d_head_workspace_bytes_ex(A, classes, 32, H, W, 6, head_mod.PRECISIONS[precision], ctypes.byref(n)), "ws")
+    with torch.no_grad():
+        (c_full, o_full), (c_less, o_less), (c_two, o_two) = [_forward_ex2(head, fm, precision, n) for n in (full.value, full.value - 256, two.value)]
+    print("chunk_classes {}: {} B -> {}, {} B -> {}, {} B -> {}".format(precision, full.value, c_full, full.value - 256, c_less, two.value, c_two))
+    assert c_full == B
+    assert 1 <= c_less < B
+    assert c_two == 2
+    for a, b, c in zip(o_full, o_less, o_two):
+        assert torch.equal(a, b) and torch.equal(a, c)
+
+
 @pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("name", ["v2_affine_inv", "v1_simple", "v2_c256_wide"])
 def test_transformation_net_stage_kernels(name, precision, device):
