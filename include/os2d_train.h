@@ -15,7 +15,8 @@
  * Arithmetic: fp32 throughout, unless a caller asks the *_ex entry points for the split-fp16 GEMMs.  The matrix-shaped work (the transposed convolutions, the weight gradients, the two
  * correlation GEMMs) runs on v_mfma_f32_16x16x4_f32.  Weight gradients reduce over NB * PLANE positions in split-K partial
  * sums that a second kernel adds in a fixed order: deterministic.  The resampling backward scatters into d corr with fp32
- * atomicAdd: the order of those additions is not fixed (as in torch's own grid_sample backward).                         */
+ * atomicAdd: the order of those additions is not fixed (as in torch's own grid_sample backward), unless the caller takes
+ * os2d_train_decode_backward_det, which adds 64-bit integers on a fixed-point grid instead.                               */
 #ifndef OS2D_TRAIN_H
 #define OS2D_TRAIN_H
 
@@ -37,6 +38,36 @@ const char* os2d_train_last_error(void);
 int os2d_train_decode_backward(const float* corr, const float* params, const float* dcls, const float* dcls_det, const float* dloc,
                                int NB, int H, int W, int P, int inverse, int stride, int rec_field, float* dcorr, float* dparams,
                                void* stream);
+
+/* ---- the same stage with an order-independent d corr scatter: two calls on the same inputs give the same bits, and a pair's
+ * d corr depends neither on the order in which its addends arrive nor on the other pairs of the batch.  Arguments, dparams
+ * (bit for bit) and the contract of dcorr (ADDED into) as os2d_train_decode_backward.  Three launches:
+ *   maxima   word[nb] = max over the pair's locations of |dcls + dcls_det| (the fp32 sum), as fp32 bits, by atomicMax;
+ *   scatter  every addend (formed in fp32 as in the float kernel) is multiplied by 2^e - exact - rounded to the nearest
+ *            integer and added with a 64-bit integer atomic to the cell's sum; e = os2d_train_decode_det_exponent(word[nb], H, W)
+ *            puts the pair's maximum m at m 2^e in [2^(60-L), 2^(61-L)), L = ceil(log2(4 H W)): a cell receives at most 4 H W
+ *            addends of at most m / 121 each, so no sum reaches 2^62;
+ *   convert  dcorr[cell] += (float)((double)sum * 2^-e); a cell whose sum is 0 is left as it is.
+ * A pair whose word is zero adds nothing.  A pair whose word is not finite (>= 0x7f800000: a NaN or Inf among its dcls +
+ * dcls_det) gets NaN in EVERY cell of its dcorr; other pairs are not affected.  That is the only non-finite input this route
+ * reports through dcorr: where the pair's word is finite but an addend is not (a NaN or Inf in params makes the sample
+ * coordinates, hence the bilinear weights, NaN), the addend's integer is unspecified and the float entry point's NaN in the
+ * touched dcorr cells does not appear; dparams carries that NaN on both routes.  No floating-point atomics.
+ * workspace: os2d_train_decode_backward_det_workspace_bytes(NB, H, W) bytes (0 = bad or refused shape), 8-byte aligned; the call
+ * clears it and leaves in it  [0, NB*225*HW*8)  the sums, int64 [NB,225,HW] in units of 2^-e of their pair, then NB uint32
+ * pair words; the total is rounded up to a multiple of 256 bytes.
+ * Refused with -3: NB > 65535, and H*W > 2^21 (L > 23), where the grid step 2^-e could exceed 2^-30 of the pair's largest
+ * possible addend m / 121.
+ * os2d_train_decode_det_exponent runs on the host and needs no device: e for a finite non-zero word (-90 <= e <= 207), else
+ * one of the three values below.                                                                                          */
+#define OS2D_TRAIN_DET_ZERO (-1000)        /* the word is zero: the pair adds nothing */
+#define OS2D_TRAIN_DET_NONFINITE (-1001)   /* the word is >= 0x7f800000: the pair's dcorr becomes NaN */
+#define OS2D_TRAIN_DET_REFUSED (-1002)     /* H, W < 1 or H*W > 2^21 */
+size_t os2d_train_decode_backward_det_workspace_bytes(int NB, int H, int W);
+int os2d_train_decode_backward_det(const float* corr, const float* params, const float* dcls, const float* dcls_det, const float* dloc,
+                                   int NB, int H, int W, int P, int inverse, int stride, int rec_field, float* dcorr, float* dparams,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+int os2d_train_decode_det_exponent(unsigned max_bits, int H, int W);
 
 /* ---- layer 3 (64 -> P, 5x5, no BatchNorm): dparams [NB,P,HW] -> dy [NB,P,PLANE] (zero-bordered plane layout) and
  * dbias [P] = sum over pairs and positions (written; NULL = not computed).  One grid row per plane: NB * P <= 65535, else -1. */

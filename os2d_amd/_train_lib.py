@@ -19,6 +19,9 @@ SIGNATURES = {
     "os2d_train_abi_version": (_i, []),
     "os2d_train_last_error": (ctypes.c_char_p, []),
     "os2d_train_decode_backward": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "os2d_train_decode_backward_det_workspace_bytes": (_sz, [_i, _i, _i]),
+    "os2d_train_decode_backward_det": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "os2d_train_decode_det_exponent": (_i, [ctypes.c_uint, _i, _i]),
     "os2d_train_params_backward": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "os2d_train_bn_relu_backward": (_i, [_i, _p, _p, _p, _p, _p, _f, _i, _i, _i, _p, _p, _p, _p, _p]),
     "os2d_train_conv_data_workspace_floats": (_sz, [_i, _i]),

@@ -15,6 +15,7 @@
 #include "../csrc/os2d_common.h"
 #include "../csrc/sample_decode.h"
 #include "train_gemm.h"     // the operand loaders and result stores of the GEMMs; the launchers of gemm_f16x3.hip
+#include "decode_det.h"     // the fixed-point grid of the order-independent d corr scatter
 
 using namespace os2d_train_gemm;
 
@@ -138,12 +139,29 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// ---- (a) resample + pool + box decode backward: one thread per (pair, location)
+// ---- the order-independent d corr scatter (decode_det.h): where a pair's sums go and on which grid
+struct DetSink {
+  unsigned long long* acc;    // [NB,225,HW] fixed-point sums (two's complement: the wrap-around of unsigned addition is signed addition)
+  const unsigned* words;      // [NB] the largest |dcls + dcls_det| of each pair, fp32 bits
+  int L;                      // os2d_det_log2_addends(H, W)
+};
+__device__ __forceinline__ double det_pow2(int e) { return __longlong_as_double((long long)(1023 + e) << 52); }   // e in [-1022, 1023]
+// one addend onto the grid: the product is exact, the rounding to the nearest integer is the route's only one
+__device__ __forceinline__ void det_add(unsigned long long* cell, float a, double scale) {
+  const long long q = __double2ll_rn((double)a * scale);
+  if (q != 0) atomicAdd(cell, (unsigned long long)q);
+}
+
+// ---- (a) resample + pool + box decode backward: one thread per (pair, location).  DET = false adds the d corr taps into
+// dcorr with fp32 atomics (os2d_train_decode_backward); DET = true rounds the same fp32 addends onto the pair's fixed-point
+// grid and adds them into `sink` with 64-bit integer atomics (os2d_train_decode_backward_det: dcorr is not touched here).
+// Everything else - theta, the coordinates, the clamps, dparams - is the same code on both routes.
+template <bool DET>
 __global__ __launch_bounds__(256) void decode_backward_kernel(const float* __restrict__ corr, const float* __restrict__ params,
                                                               const float* __restrict__ dcls, const float* __restrict__ dcls_det,
                                                               const float* __restrict__ dloc, int H, int W, int P, int inverse,
                                                               float stride, float half_box, float* __restrict__ dcorr,
-                                                              float* __restrict__ dparams) {
+                                                              float* __restrict__ dparams, DetSink sink) {
   const int HW = H * W;
   const int nb = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
   if (n >= HW) return;
@@ -161,7 +179,16 @@ __global__ __launch_bounds__(256) void decode_backward_kernel(const float* __res
   const float cx = (float)w + 0.5f, cy = (float)h + 0.5f;
   const float wmax = (float)(W - 1), hmax = (float)(H - 1);
   const float* cbase = corr + (size_t)nb * OS2D_K * HW;
-  float* dbase = dcorr + (size_t)nb * OS2D_K * HW;
+  float* dbase = DET ? nullptr : dcorr + (size_t)nb * OS2D_K * HW;
+  unsigned long long* abase = nullptr;
+  double scale = 0.0;
+  bool scatter = true;
+  if (DET) {                  // a zero maximum has nothing to add; a non-finite one is the convert pass's to report
+    const int e = os2d_det_exponent(sink.words[nb], sink.L);
+    scatter = e != OS2D_TRAIN_DET_ZERO && e != OS2D_TRAIN_DET_NONFINITE;
+    scale = det_pow2(scatter ? e : 0);
+    abase = sink.acc + (size_t)nb * OS2D_K * HW;
+  }
   float d00 = 0.f, d01 = 0.f, d02 = 0.f, d10 = 0.f, d11 = 0.f, d12 = 0.f;
   if (wsc != 0.f || wth != 0.f) {
     for (int j = POOL_LO; j < POOL_HI; ++j) {
@@ -179,11 +206,23 @@ __global__ __launch_bounds__(256) void decode_backward_kernel(const float* __res
         const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
         const size_t ch = (size_t)(j * OS2D_T + i) * HW;
         if (wsc != 0.f) {       // d corr: the pool weight over the 4 taps of the point's own channel
-          float* d = dbase + ch;
-          unsafeAtomicAdd(d + y0 * W + x0, wsc * (1.f - ax) * (1.f - ay));
-          unsafeAtomicAdd(d + y0 * W + x1, wsc * ax * (1.f - ay));
-          unsafeAtomicAdd(d + y1 * W + x0, wsc * (1.f - ax) * ay);
-          unsafeAtomicAdd(d + y1 * W + x1, wsc * ax * ay);
+          const float a00 = wsc * (1.f - ax) * (1.f - ay), a01 = wsc * ax * (1.f - ay);
+          const float a10 = wsc * (1.f - ax) * ay, a11 = wsc * ax * ay;
+          if (DET) {
+            if (scatter) {
+              unsigned long long* d = abase + ch;
+              det_add(d + y0 * W + x0, a00, scale);
+              det_add(d + y0 * W + x1, a01, scale);
+              det_add(d + y1 * W + x0, a10, scale);
+              det_add(d + y1 * W + x1, a11, scale);
+            }
+          } else {
+            float* d = dbase + ch;
+            unsafeAtomicAdd(d + y0 * W + x0, a00);
+            unsafeAtomicAdd(d + y0 * W + x1, a01);
+            unsafeAtomicAdd(d + y1 * W + x0, a10);
+            unsafeAtomicAdd(d + y1 * W + x1, a11);
+          }
         }
         if (wth != 0.f) {       // d grid: derivative of the bilinear weights, zero where the coordinate was clamped
           const float* c = cbase + ch;
@@ -300,6 +339,48 @@ __global__ __launch_bounds__(256) void decode_backward_kernel(const float* __res
     dp[2 * (size_t)HW] = (float)g[4];
     dp[3 * (size_t)HW] = (float)g[5];
   }
+}
+
+// ---- the maxima of the order-independent route: words[nb] = max over the pair's locations of |dcls + dcls_det| (the fp32 sum
+// decode_backward_kernel forms), as the bits of a non-negative float - they order as unsigned integers, a NaN's above every
+// number's.  A work-group reduces DET_MAX_CHUNK locations and makes ONE atomicMax (the maxima pass of gemm_f16x3.hip).
+constexpr int DET_MAX_CHUNK = 2048;
+__global__ __launch_bounds__(256) void decode_det_max_kernel(const float* __restrict__ dcls, const float* __restrict__ dcls_det, int HW,
+                                                             unsigned* __restrict__ words) {
+  __shared__ unsigned red[4];
+  const int nb = blockIdx.y;
+  const int n0 = blockIdx.x * DET_MAX_CHUNK, n1 = min(HW, n0 + DET_MAX_CHUNK);
+  unsigned m = 0u;
+  for (int n = n0 + threadIdx.x; n < n1; n += 256) {
+    const size_t o = (size_t)nb * HW + n;
+    const float gcls = dcls ? dcls[o] : 0.f;
+    const float gsum = gcls + (dcls_det ? dcls_det[o] : 0.f);
+    m = max(m, __float_as_uint(gsum) & 0x7fffffffu);
+  }
+  for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = max(max(red[0], red[1]), max(red[2], red[3]));
+    if (m != 0u) atomicMax(words + nb, m);
+  }
+}
+
+// ---- the convert pass: dcorr[cell] += (float)(sum * 2^-e), one thread per cell of a pair.  A zero sum leaves the cell as it
+// is (so does a pair whose maximum is zero); a pair with a non-finite maximum gets NaN in every cell.
+__global__ __launch_bounds__(256) void decode_det_convert_kernel(DetSink sink, size_t cells, float* __restrict__ dcorr) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int nb = blockIdx.y;
+  if (i >= cells) return;
+  const int e = os2d_det_exponent(sink.words[nb], sink.L);
+  if (e == OS2D_TRAIN_DET_ZERO) return;
+  float* d = dcorr + (size_t)nb * cells + i;
+  if (e == OS2D_TRAIN_DET_NONFINITE) {
+    *d = __uint_as_float(0x7fc00000u);
+    return;
+  }
+  const long long q = (long long)sink.acc[(size_t)nb * cells + i];
+  if (q != 0) *d += (float)((double)q * det_pow2(-e));
 }
 
 // dparams [NB,P,HW] -> plane layout (zero pads)
@@ -501,9 +582,76 @@ int os2d_train_decode_backward(const float* corr, const float* params, const flo
     return -3;
   }
   const float half_box = 0.5f * (float)(stride * (OS2D_T - 1) + rec_field);
-  hipLaunchKernelGGL(decode_backward_kernel, dim3(blocks((size_t)H * W), NB), dim3(256), 0, os2d_stream(stream), corr, params, dcls, dcls_det,
-                     dloc, H, W, P, inverse ? 1 : 0, (float)stride, half_box, dcorr, dparams);
+  hipLaunchKernelGGL(decode_backward_kernel<false>, dim3(blocks((size_t)H * W), NB), dim3(256), 0, os2d_stream(stream), corr, params, dcls,
+                     dcls_det, dloc, H, W, P, inverse ? 1 : 0, (float)stride, half_box, dcorr, dparams, DetSink{nullptr, nullptr, 0});
   return os2d_launched("decode_backward_kernel");
+}
+
+int os2d_train_decode_det_exponent(unsigned max_bits, int H, int W) {
+  const int L = os2d_det_log2_addends(H, W);
+  return L < 0 ? OS2D_TRAIN_DET_REFUSED : os2d_det_exponent(max_bits, L);
+}
+
+// the accumulator, then the pair words
+static size_t det_acc_bytes(int NB, int H, int W) { return (size_t)NB * OS2D_K * H * W * sizeof(long long); }
+size_t os2d_train_decode_backward_det_workspace_bytes(int NB, int H, int W) {
+  if (NB < 1 || NB > 65535 || os2d_det_log2_addends(H, W) < 0) return 0;
+  return (det_acc_bytes(NB, H, W) + (size_t)NB * sizeof(unsigned) + 255) / 256 * 256;
+}
+
+int os2d_train_decode_backward_det(const float* corr, const float* params, const float* dcls, const float* dcls_det, const float* dloc,
+                                   int NB, int H, int W, int P, int inverse, int stride, int rec_field, float* dcorr, float* dparams,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  os2d_clear_error();
+  if (!corr || !params || !dcorr || !dparams || !workspace) {
+    os2d_set_error("os2d_train_decode_backward_det: null pointer");
+    return -1;
+  }
+  if (NB < 1 || H < 1 || W < 1 || (P != 6 && P != 4) || stride < 1 || rec_field < 1) {
+    os2d_set_error("os2d_train_decode_backward_det: bad shape NB=%d H=%d W=%d P=%d stride=%d rec_field=%d", NB, H, W, P, stride, rec_field);
+    return -1;
+  }
+  if (NB > 65535) {
+    os2d_set_error("os2d_train_decode_backward_det: NB=%d > 65535", NB);
+    return -3;
+  }
+  const int L = os2d_det_log2_addends(H, W);
+  if (L < 0) {
+    os2d_set_error("os2d_train_decode_backward_det: H*W=%lld > 2^%d locations: the fixed-point step would exceed 2^-30 of a pair's largest addend",
+                   (long long)H * W, OS2D_DET_MAX_LOG2 - 2);
+    return -3;
+  }
+  if (((uintptr_t)workspace & 7) != 0) {
+    os2d_set_error("os2d_train_decode_backward_det: workspace is not 8-byte aligned");
+    return -1;
+  }
+  const size_t need = os2d_train_decode_backward_det_workspace_bytes(NB, H, W);
+  if (workspace_bytes < need) {
+    os2d_set_error("os2d_train_decode_backward_det: workspace %zu bytes < %zu", workspace_bytes, need);
+    return -2;
+  }
+  const int HW = H * W;
+  const size_t cells = (size_t)OS2D_K * HW;
+  unsigned* words = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + det_acc_bytes(NB, H, W));
+  const DetSink sink{static_cast<unsigned long long*>(workspace), words, L};
+  const hipError_t err = hipMemsetAsync(workspace, 0, need, os2d_stream(stream));
+  if (err != hipSuccess) {
+    os2d_set_error("os2d_train_decode_backward_det: hipMemsetAsync of the workspace: %s", hipGetErrorString(err));
+    return -4;
+  }
+  int rc = 0;
+  if (dcls || dcls_det) {       // without either the words stay zero: no pair adds anything
+    hipLaunchKernelGGL(decode_det_max_kernel, dim3((HW + DET_MAX_CHUNK - 1) / DET_MAX_CHUNK, NB), dim3(256), 0, os2d_stream(stream), dcls,
+                       dcls_det, HW, words);
+    if ((rc = os2d_launched("decode_det_max_kernel"))) return rc;
+  }
+  const float half_box = 0.5f * (float)(stride * (OS2D_T - 1) + rec_field);
+  hipLaunchKernelGGL(decode_backward_kernel<true>, dim3(blocks((size_t)HW), NB), dim3(256), 0, os2d_stream(stream), corr, params, dcls,
+                     dcls_det, dloc, H, W, P, inverse ? 1 : 0, (float)stride, half_box, dcorr, dparams, sink);
+  if ((rc = os2d_launched("decode_backward_kernel (deterministic)"))) return rc;
+  if (!dcls && !dcls_det) return 0;
+  hipLaunchKernelGGL(decode_det_convert_kernel, dim3(blocks(cells), NB), dim3(256), 0, os2d_stream(stream), sink, cells, dcorr);
+  return os2d_launched("decode_det_convert_kernel");
 }
 
 int os2d_train_params_backward(const float* dparams, int NB, int P, int H, int W, float* dy, float* dbias, void* stream) {

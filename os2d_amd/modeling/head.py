@@ -455,6 +455,9 @@ class Os2dHeadCreator(nn.Module):
         # arithmetic of the backward GEMMs of the heads this creator makes (head_train.TRAIN_PRECISIONS); None: follow
         # $OS2D_TRAIN_PRECISION (default "f32")
         self.train_precision = None
+        # order-independent d corr scatter in the backward pass of the heads this creator makes (head_train.resolve_deterministic):
+        # None: follow $OS2D_DETERMINISTIC, else torch.are_deterministic_algorithms_enabled(); True / False
+        self.deterministic = None
 
     @staticmethod
     def get_rec_field_and_stride_after_concat_nets(receptive_field_netA, stride_netA, receptive_field_netB, stride_netB):
@@ -483,6 +486,7 @@ class Os2dHeadCreator(nn.Module):
             class_feature_maps = [m.unsqueeze(0) for m in class_feature_maps]
         head._raw_class_maps = list(class_feature_maps)
         head.train_precision = self.train_precision         # a training step builds a new head per batch
+        head.deterministic = self.deterministic
         return head
 
 
@@ -571,6 +575,8 @@ class Os2dHead(nn.Module):
         self.precision = None      # None: follow $OS2D_PRECISION (default "fftx3"); or one of PRECISIONS
         self.train_precision = None        # backward GEMMs under autograd: None = $OS2D_TRAIN_PRECISION (default "f32"), "f32", "f16x3"
         self.last_train_precision = None   # the one the last training forward resolved (head_train.py)
+        self.deterministic = None          # bit-reproducible backward: None = $OS2D_DETERMINISTIC, else torch's deterministic flag; True / False
+        self.last_deterministic = None     # what the last training forward resolved (head_train.py)
         # sticky status word of the split-fp16 kernels in mapped pinned host memory (one per device, process lifetime:
         # ``device_status_word``): the kernels store to it only when an activation leaves the fp16 range (impossible for
         # finite inputs, see TransformationNet.range_plan), the host reads it without synchronising

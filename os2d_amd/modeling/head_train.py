@@ -9,6 +9,9 @@ the backward pass of libos2d_train.so (include/os2d_train.h), wrapped in one ``t
     BatchNorms conv.1 / conv.4 (weight = gamma, bias = beta); the running statistics stay constants.
 The five GEMM-shaped launches of the backward pass run in fp32 or, with ``train_precision = "f16x3"`` on the head or its
 creator (or $OS2D_TRAIN_PRECISION), in split-fp16 arithmetic within fp32 rounding of it.
+With ``deterministic = True`` on the head or its creator (or $OS2D_DETERMINISTIC, or torch.use_deterministic_algorithms(True))
+the d corr scatter of the decode backward adds 64-bit integers on a fixed-point grid instead of fp32 atomics: two passes on the
+same inputs then return the same bits for every gradient.
 As in the reference (head.py:396-402, 423): ``cls_det`` carries the same values as ``cls`` but its gradient reaches the
 correlation only, not the transformation; ``corners`` carries none.
 """
@@ -35,6 +38,19 @@ def resolve_train_precision(value=None):
     if value not in TRAIN_PRECISIONS:
         raise ValueError("unknown train_precision {!r}: one of {}".format(value, TRAIN_PRECISIONS))
     return value
+
+
+def resolve_deterministic(value=None):
+    """``value`` (a head's or a creator's ``deterministic``: True / False) or, for None, $OS2D_DETERMINISTIC ("0" / empty: off,
+    anything else: on) or, where that is not set, ``torch.are_deterministic_algorithms_enabled()``."""
+    if value is not None and not isinstance(value, bool):
+        raise ValueError("deterministic must be None, True or False, got {!r}".format(value))
+    if value is not None:
+        return value
+    env = os.environ.get("OS2D_DETERMINISTIC")
+    if env is not None:
+        return env not in ("0", "")
+    return bool(torch.are_deterministic_algorithms_enabled())
 
 
 def _ptr(t):
@@ -85,6 +101,7 @@ class _HeadFunction(torch.autograd.Function):
             q15raw, _ = _prepare_class_maps(list(raws), normalise=False)
         ctx.head, ctx.n_class, ctx.shape = head, n_class, (A, B, C, H, W, P, inverse, PL)
         ctx.arith = TRAIN_PRECISIONS.index(head.last_train_precision)
+        ctx.deterministic = head.last_deterministic
         ctx.saved = dict(fm=fm, raws=raws, corr=corr, rnorm=rnorm, h1=h1, h2=h2, params=prm, q15raw=q15raw,
                          weights=[p.detach().contiguous() for p in params])
         ctx.mark_non_differentiable(corners)
@@ -117,9 +134,14 @@ class _HeadFunction(torch.autograd.Function):
             s = _lib.current_stream(dev)
             dcorr = torch.zeros(NB, 225, HW, **f32)
             dparams = torch.empty(NB, P, HW, **f32)
-            _train_lib.check(tl.os2d_train_decode_backward(_ptr(sv["corr"]), _ptr(sv["params"]), _ptr(dcls), _ptr(dcls_det), _ptr(dloc),
-                                                           NB, H, W, P, inverse, head._stride, head._rec_field, _ptr(dcorr),
-                                                           _ptr(dparams), s), "os2d_train_decode_backward")
+            decode_args = (_ptr(sv["corr"]), _ptr(sv["params"]), _ptr(dcls), _ptr(dcls_det), _ptr(dloc), NB, H, W, P, inverse,
+                           head._stride, head._rec_field, _ptr(dcorr), _ptr(dparams))
+            if ctx.deterministic:
+                ws = torch.empty(int(tl.os2d_train_decode_backward_det_workspace_bytes(NB, H, W)), dtype=torch.uint8, device=dev)
+                _train_lib.check(tl.os2d_train_decode_backward_det(*decode_args, _ptr(ws), ws.numel(), s), "os2d_train_decode_backward_det")
+                del ws
+            else:
+                _train_lib.check(tl.os2d_train_decode_backward(*decode_args, s), "os2d_train_decode_backward")
             splits = _wgrad_splits(NB, PL)
 
             def wgrad(layer, x, dy, like):
@@ -209,8 +231,10 @@ def needs_grad(head, feature_maps):
 def head_forward_train(head, feature_maps):
     """(loc, cls, cls_det, corners) of ``Os2dHead.forward`` with autograd (see the module docstring).  The arithmetic of the
     backward GEMMs is ``head.train_precision`` (None: $OS2D_TRAIN_PRECISION, default "f32"); the one taken is recorded in
-    ``head.last_train_precision``."""
+    ``head.last_train_precision``, and whether the backward pass is the bit-reproducible one (``head.deterministic``,
+    ``resolve_deterministic``) in ``head.last_deterministic``."""
     head.last_train_precision = resolve_train_precision(head.train_precision)
+    head.last_deterministic = resolve_deterministic(head.deterministic)
     A, C, H, W = feature_maps.shape
     if W > MAX_W_DIRECT7:
         raise RuntimeError("autograd through the HIP head needs feature maps at most {} columns wide (the direct 7x7 kernels of the "

@@ -3,10 +3,13 @@ the HIP training forward (the "f32" route with its intermediates kept) and the H
 the same step done eagerly by torch: the oracle's ``head_forward`` under autograd on the same GPU.
 
     python tools/time_head_backward.py [--reps N] [--no-eager] [--A 4 --B 15 --C 1024 --H 38 --W 38]
-                                       [--train-precision f32|f16x3|both]
+                                       [--train-precision f32|f16x3|both] [--deterministic off|on|both]
 
 ``--train-precision``: the arithmetic of the backward GEMMs (default: $OS2D_TRAIN_PRECISION, else "f32"); ``both`` times
 f32, f16x3 and f32 again in one process - the two f32 figures show the spread of the box.
+``--deterministic``: the d corr scatter of the decode backward (default: what the head resolves, see
+``head_train.resolve_deterministic``); ``both`` times off, on and off again in one process, under the one train precision given
+(or each of the three runs of ``--train-precision both``) - the two "off" figures show the spread of the box.
 Per-kernel times: run it under ``rocprofv3 --kernel-trace --stats -- python tools/time_head_backward.py --reps 1 --no-eager``.
 Prints one JSON line."""
 import argparse
@@ -29,6 +32,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--no-eager", action="store_true")
     ap.add_argument("--train-precision", choices=["f32", "f16x3", "both"], default=None)
+    ap.add_argument("--deterministic", choices=["off", "on", "both"], default=None)
     a = ap.parse_args()
     from os2d_amd.modeling.head import build_os2d_head_creator
     from os2d_amd.structures.feature_map import FeatureMapSize
@@ -69,18 +73,32 @@ def main():
         ((loc * gl).sum() + (cls * gc).sum() + (cls_det * gc).sum()).backward()
         return loc
 
+    def timed_step():
+        """One timing of hip_step under the creator's settings; with --deterministic both: off, on, off."""
+        if a.deterministic != "both":
+            creator.deterministic = None if a.deterministic is None else a.deterministic == "on"
+            fwd, bwd = timed(hip_step)
+            return {"hip_forward_ms": round(fwd, 3), "hip_backward_ms": round(bwd, 3)}
+        out = {}
+        for key, flag in (("off", False), ("on", True), ("off_again", False)):
+            creator.deterministic = flag
+            fwd, bwd = timed(hip_step)
+            out["deterministic_" + key] = {"hip_forward_ms": round(fwd, 3), "hip_backward_ms": round(bwd, 3)}
+        return out
+
     res = {"shape": [a.A, a.B, a.C, a.H, a.W]}
     if a.train_precision == "both":
         for key, precision in (("f32", "f32"), ("f16x3", "f16x3"), ("f32_again", "f32")):
             creator.train_precision = precision
-            fwd, bwd = timed(hip_step)
-            res[key] = {"hip_forward_ms": round(fwd, 3), "hip_backward_ms": round(bwd, 3)}
+            res[key] = timed_step()
     else:
         creator.train_precision = a.train_precision
-        fwd, bwd = timed(hip_step)
+        res.update(timed_step())
         head = creator.create_os2d_head(raws)
         head(fm)
-        res.update({"train_precision": head.last_train_precision, "hip_forward_ms": round(fwd, 3), "hip_backward_ms": round(bwd, 3)})
+        res["train_precision"] = head.last_train_precision
+        if a.deterministic != "both":
+            res["deterministic"] = head.last_deterministic
     if not a.no_eager:
         st = {k: v.to(dev).requires_grad_(k.endswith("weight") or k.endswith("bias")) for k, v in state.items()}
 
