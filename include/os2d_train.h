@@ -137,6 +137,20 @@ int os2d_train_corr_backward_ex(int arith, const float* fm, const float* qp, con
 int os2d_train_class_backward(const float* q15, const float* dq, int B, int C, float* const* dsrcs, const int* sizes,
                               float* workspace, size_t workspace_floats, void* stream);
 
+/* ---- the bridge from a split-fp16 ("f16x3") training forward to the entry points above (csrc_train/shb_planes.hip).  shb is an
+ * activation buffer of the f16x3 stage entry points of os2d_hip.h (os2d_corr_f16x3, os2d_transform_conv_f16x3) in the split-half
+ * blocked layout: [NB][ceil(channels/8)][hi|lo][PLANE] units of 16 bytes = 8 channels of one plane cell as fp16, channel c
+ * stored as x * 2^exp[c]; exp [channels] int32 on the DEVICE (the relu + L2 normalised correlation: 225 times os2d_rnorm_exp();
+ * h1 / h2: the layer's out_exp given to os2d_pack_conv_f16x3).  Writes planes [NB,out_channels,PLANE] fp32:
+ *   planes[nb][c][n] = (float(hi) + float(lo)) * 2^-exp[c]  at interior cells of the zero-bordered plane layout - exact: the
+ *                      halves of a split fp32 value add up to at most 24 bits, the power of two only moves the exponent;
+ *   +0.0               at every other cell, whatever shb holds there (pad cells, the unused channels of the last group);
+ *   +0.0               in the whole of planes channels .. out_channels-1 (rnorm: channels = 225, out_channels = 226).
+ * shb and planes 16-byte aligned.  One grid row per (pair, 8-channel group): NB * ceil(out_channels/8) <= 65535, else -1; also
+ * -1: a null pointer, NB / channels / H / W < 1, out_channels < channels, H or W beyond the head's own limits.  One launch.  */
+int os2d_train_planes_from_shb(const void* shb, const int* exp, int NB, int channels, int out_channels, int H, int W,
+                               float* planes, void* stream);
+
 /* ==== Target assignment and the training objective (csrc_train/objective.hip; reference os2d/modeling/box_coder.py:234-389 and
  * os2d/engine/objective.py:107-313).  A images, B labels, HW = H*W anchors per level, N = A*B*HW elements.  Class targets are
  * int64 (1 positive, 0 negative, -1 ignored), as the reference returns them.  No call synchronises with the host; float sums

@@ -38,6 +38,7 @@ SIGNATURES = {
     "os2d_train_corr_workspace_floats_ex": (_sz, [_i, _i, _i, _i, _i, _i]),
     "os2d_train_corr_backward_ex": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "os2d_train_class_backward": (_i, [_p, _p, _i, _i, _p, _p, _p, _sz, _p]),
+    "os2d_train_planes_from_shb": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "os2d_train_assign_targets": (_i, [_i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p]),
     "os2d_train_assign_targets_ops": (_i, [_i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p]),
     "os2d_train_crop_boxes": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),

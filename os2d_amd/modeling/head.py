@@ -14,7 +14,8 @@ memory, the stream and the parameter containers.  There is no CPU / eager fallba
 
 Training: when grad mode is on and the image feature maps, the raw class maps given to ``create_os2d_head`` or a TransformNet
 parameter require grad, ``Os2dHead.forward`` runs the strict-fp32 "f32" route stage by stage, keeps its intermediates, and its
-backward pass runs in libos2d_train.so (os2d_amd/csrc_train, fp32 MFMA; see head_train.py).  Gradients reach the image and raw
+backward pass runs in libos2d_train.so (os2d_amd/csrc_train, fp32 MFMA; see head_train.py).  ``train_forward_precision = "f16x3"``
+on the head or its creator runs that forward on the direct split-fp16 route instead.  Gradients reach the image and raw
 class maps and every TransformNet weight, bias and BatchNorm affine parameter; BatchNorm must be frozen (eval mode, the
 reference's training default); maps wider than MAX_W_DIRECT7 columns raise.  ``TransformationNet.forward`` on its own and the
 other precisions stay inference-only.
@@ -262,6 +263,10 @@ class TransformationNet(nn.Module):
             out = []
             P = self.output_dim
             plan = self.range_plan() if precision == "f16x3" else None
+            if plan is not None:
+                # the exponents of the activation buffers this packing reads and writes (``activation_exponents``)
+                act = tuple(e.to(dev).contiguous() for e in (plan["in_exp"][0], plan["out_exp"][0], plan["out_exp"][1]))
+                self._packed_cache["f16x3.act_exp"] = _StreamOrdered(key, act, dev)
             layers = ((1, self.conv[0], self.conv[1]), (2, self.conv[3], self.conv[4]), (3, self.linear, None))
             for layer, conv, bn in layers:
                 w = _require_device_f32(conv.weight.detach(), "conv weight")
@@ -290,6 +295,14 @@ class TransformationNet(nn.Module):
             result = tuple(out)
             self._packed_cache[precision] = _StreamOrdered(key, result, dev)
         return result
+
+    def activation_exponents(self):
+        """Per-channel exponents of the three split-half blocked activation buffers of the "f16x3" kernels, as int32 device tensors:
+        (the relu + L2 normalised correlation [225], the 7x7 layer's output h1 [128], the 5x5 layer's output h2 [64]); channel c
+        of a buffer holds x * 2^exp[c].  They belong to the weights of ``packed("f16x3")`` and are cached with them (the training
+        forward hands them to os2d_train_planes_from_shb, head_train.py)."""
+        self.packed("f16x3")
+        return self._packed_cache["f16x3.act_exp"].get(self.linear.weight.device)
 
     def _cached_spectra(self, H, W, split, slot_tag, build):
         """This net's entry of slot (P, Q, split) + ``slot_tag`` in the device's store, built by ``build(P, Q, nbins, dev)`` on a
@@ -455,6 +468,9 @@ class Os2dHeadCreator(nn.Module):
         # arithmetic of the backward GEMMs of the heads this creator makes (head_train.TRAIN_PRECISIONS); None: follow
         # $OS2D_TRAIN_PRECISION (default "f32")
         self.train_precision = None
+        # arithmetic of the training FORWARD of the heads this creator makes (head_train.TRAIN_FORWARD_PRECISIONS); None: follow
+        # $OS2D_TRAIN_FORWARD_PRECISION (default "f32"); independent of ``train_precision``
+        self.train_forward_precision = None
         # order-independent d corr scatter in the backward pass of the heads this creator makes (head_train.resolve_deterministic):
         # None: follow $OS2D_DETERMINISTIC, else torch.are_deterministic_algorithms_enabled(); True / False
         self.deterministic = None
@@ -486,6 +502,7 @@ class Os2dHeadCreator(nn.Module):
             class_feature_maps = [m.unsqueeze(0) for m in class_feature_maps]
         head._raw_class_maps = list(class_feature_maps)
         head.train_precision = self.train_precision         # a training step builds a new head per batch
+        head.train_forward_precision = self.train_forward_precision
         head.deterministic = self.deterministic
         return head
 
@@ -575,6 +592,13 @@ class Os2dHead(nn.Module):
         self.precision = None      # None: follow $OS2D_PRECISION (default "fftx3"); or one of PRECISIONS
         self.train_precision = None        # backward GEMMs under autograd: None = $OS2D_TRAIN_PRECISION (default "f32"), "f32", "f16x3"
         self.last_train_precision = None   # the one the last training forward resolved (head_train.py)
+        self.train_forward_precision = None        # the forward under autograd: None = $OS2D_TRAIN_FORWARD_PRECISION (default "f32"), "f32", "f16x3"
+        self.last_train_forward_precision = None   # the one the last training forward resolved; ``last_precision`` follows it
+        # debugging hook of the training forward: True keeps a reference to what the autograd Function saved for its backward in
+        # ``last_train_activations`` = dict(corr, rnorm, h1, h2, params) (fp32; layouts of include/os2d_train.h) - the tensors
+        # themselves, so they stay alive with the head and must not be written
+        self.keep_train_activations = False
+        self.last_train_activations = None
         self.deterministic = None          # bit-reproducible backward: None = $OS2D_DETERMINISTIC, else torch's deterministic flag; True / False
         self.last_deterministic = None     # what the last training forward resolved (head_train.py)
         # sticky status word of the split-fp16 kernels in mapped pinned host memory (one per device, process lifetime:
@@ -660,12 +684,12 @@ class Os2dHead(nn.Module):
             raise RuntimeError("feature_maps must be [A,C,H,W], got {}".format(tuple(feature_maps.shape)))
         _resolve(precision or self.precision)          # a bad precision is refused on every route
         if out is None and stage_events is None and head_train.needs_grad(self, feature_maps):
-            # training: the strict-fp32 route with a HIP backward pass (``precision`` / ``route_pairs`` do not apply)
+            # training: the strict-fp32 route - or, with ``train_forward_precision = "f16x3"``, the direct split-fp16 one - stage by
+            # stage, with a HIP backward pass (``precision`` / ``route_pairs`` do not apply)
             if feature_maps.size(1) != self.class_feature_maps.size(1):
                 raise RuntimeError("Feature dimensionality of input={0} and class={1} feature maps has to equal".format(
                     feature_maps.size(1), self.class_feature_maps.size(1)))
-            self.last_precision = "f32"
-            return head_train.head_forward_train(self, feature_maps)
+            return head_train.head_forward_train(self, feature_maps)         # (sets ``last_precision``)
         if torch.is_grad_enabled() and feature_maps.requires_grad:
             raise RuntimeError("autograd through the HIP head does not take preallocated outputs or stage events: "
                                "call under torch.no_grad()")

@@ -1,5 +1,6 @@
-"""Autograd through the HIP head: the training forward (the strict-fp32 "f32" route, stage by stage, intermediates kept) and
-the backward pass of libos2d_train.so (include/os2d_train.h), wrapped in one ``torch.autograd.Function``.
+"""Autograd through the HIP head: the training forward (the strict-fp32 "f32" route or, on request, the direct split-fp16
+"f16x3" route; stage by stage, intermediates kept) and the backward pass of libos2d_train.so (include/os2d_train.h), wrapped in
+one ``torch.autograd.Function``.
 
 ``Os2dHead.forward`` comes here when grad mode is on and the image feature maps, the raw class maps the head was created from
 (``Os2dHeadCreator.create_os2d_head``) or a TransformNet parameter require grad.  Gradients reach
@@ -9,6 +10,11 @@ the backward pass of libos2d_train.so (include/os2d_train.h), wrapped in one ``t
     BatchNorms conv.1 / conv.4 (weight = gamma, bias = beta); the running statistics stay constants.
 The five GEMM-shaped launches of the backward pass run in fp32 or, with ``train_precision = "f16x3"`` on the head or its
 creator (or $OS2D_TRAIN_PRECISION), in split-fp16 arithmetic within fp32 rounding of it.
+With ``train_forward_precision = "f16x3"`` (or $OS2D_TRAIN_FORWARD_PRECISION) - a switch of its own, independent of
+``train_precision`` - the forward runs the f16x3 stage kernels of the inference route (os2d_corr_f16x3, os2d_transform_conv_f16x3 x 3,
+os2d_sample_decode: the bits of ``head(fm, precision="f16x3")``) and os2d_train_planes_from_shb turns each split-half blocked
+activation buffer into the fp32 planes the backward reads - exactly, so the backward differentiates the values the forward
+multiplied with.
 With ``deterministic = True`` on the head or its creator (or $OS2D_DETERMINISTIC, or torch.use_deterministic_algorithms(True))
 the d corr scatter of the decode backward adds 64-bit integers on a fixed-point grid instead of fp32 atomics: two passes on the
 same inputs then return the same bits for every gradient.
@@ -27,9 +33,13 @@ TEMPLATE = 15
 MAX_W_DIRECT7 = 209
 # arithmetic of the backward pass's five GEMM launches (the `arith` argument of the *_ex entry points of include/os2d_train.h):
 # "f32" = v_mfma_f32_16x16x4_f32, "f16x3" = split-fp16 operands on v_mfma_f32_32x32x16_f16, within fp32 rounding of "f32".  The
-# training FORWARD is the strict-fp32 route either way.
+# training FORWARD does not follow it: that is TRAIN_FORWARD_PRECISIONS.
 TRAIN_PRECISIONS = ("f32", "f16x3")
 DEFAULT_TRAIN_PRECISION = "f32"
+# arithmetic of the training forward: "f32" = the strict-fp32 stages (the bits of ``precision="f32"``), "f16x3" = the direct
+# split-fp16 stages (the bits of ``precision="f16x3"``) + os2d_train_planes_from_shb
+TRAIN_FORWARD_PRECISIONS = ("f32", "f16x3")
+DEFAULT_TRAIN_FORWARD_PRECISION = "f32"
 
 
 def resolve_train_precision(value=None):
@@ -37,6 +47,14 @@ def resolve_train_precision(value=None):
     value = value or os.environ.get("OS2D_TRAIN_PRECISION") or DEFAULT_TRAIN_PRECISION
     if value not in TRAIN_PRECISIONS:
         raise ValueError("unknown train_precision {!r}: one of {}".format(value, TRAIN_PRECISIONS))
+    return value
+
+
+def resolve_train_forward_precision(value=None):
+    """``value`` (a head's or a creator's ``train_forward_precision``) or, for None, $OS2D_TRAIN_FORWARD_PRECISION (default "f32")."""
+    value = value or os.environ.get("OS2D_TRAIN_FORWARD_PRECISION") or DEFAULT_TRAIN_FORWARD_PRECISION
+    if value not in TRAIN_FORWARD_PRECISIONS:
+        raise ValueError("unknown train_forward_precision {!r}: one of {}".format(value, TRAIN_FORWARD_PRECISIONS))
     return value
 
 
@@ -62,6 +80,73 @@ def _wgrad_splits(NB, PL):
     return max(1, min(64, (NB * PL + 4095) // 4096))
 
 
+def _stages_f32(lib, head, fm, corr, prm, shape, s):
+    """The strict-fp32 stages up to the transformation parameters: fills ``corr`` and ``prm``, returns the activations
+    (rnorm [NB,226,PLANE], h1 [NB,128,PLANE], h2 [NB,64,PLANE]) as flat fp32 tensors."""
+    A, B, C, H, W, P, PL = shape
+    NB, HW = A * B, H * W
+    f32 = dict(dtype=torch.float32, device=fm.device)
+    w1, b1, w2, b2, w3, b3 = head.aligner.parameter_regressor.packed("f32")
+    sumsq = torch.empty(A * HW, **f32)
+    rnorm = torch.empty(NB * 226 * PL, **f32)
+    h1 = torch.empty(NB * 128 * PL, **f32)
+    h2 = torch.empty(NB * 64 * PL, **f32)
+    _lib.check(lib.os2d_fm_sumsq(_ptr(fm), _ptr(sumsq), A, C, H, W, s), "os2d_fm_sumsq")
+    _lib.check(lib.os2d_corr(_ptr(fm), _ptr(head._qp), _ptr(sumsq), _ptr(corr), _ptr(rnorm), A, B, C, H, W, s), "os2d_corr")
+    for layer, src, wp, bp, dst in ((1, rnorm, w1, b1, h1), (2, h1, w2, b2, h2), (3, h2, w3, b3, prm)):
+        _lib.check(lib.os2d_transform_conv(layer, _ptr(src), _ptr(wp), _ptr(bp), _ptr(dst), NB, P, H, W, s),
+                   "os2d_transform_conv")
+    return rnorm, h1, h2
+
+
+def _stages_f16x3(lib, head, fm, corr, prm, shape, s):
+    """The same on the direct split-fp16 route: the stage entry points the head call of ``precision="f16x3"`` is made of (they
+    zero the borders the next layer's taps read themselves: os2d_corr_f16x3 those of its output before the correlation writes
+    it, the convolutions in their epilogue).  Each split-half blocked buffer becomes fp32 planes (os2d_train_planes_from_shb:
+    exact) as soon as the layer that reads it has been launched, and is freed: at most one activation tensor exists twice.
+    An activation outside the fp16 range - a non-finite feature: nothing else gets past the range plan - raises the head's
+    sticky status word (``Os2dHead.range_status``), as on the inference route."""
+    A, B, C, H, W, P, PL = shape
+    NB = A * B
+    dev = fm.device
+    tl = _train_lib.load()
+    regressor = head.aligner.parameter_regressor
+    w1, b1, w2, b2, w3, b3 = regressor.packed("f16x3")
+    exps = regressor.activation_exponents()
+    qs = head._split_class_operand()
+    status = _lib.host_ptr(head._status_word())
+
+    def shb(channels):
+        return torch.empty(NB * int(lib.os2d_shb_bytes(channels, H, W)), dtype=torch.uint8, device=dev)
+
+    def planes(buf, exp, channels, out_channels):
+        out = torch.empty(NB * out_channels * PL, dtype=torch.float32, device=dev)
+        _train_lib.check(tl.os2d_train_planes_from_shb(_ptr(buf), _ptr(exp), NB, channels, out_channels, H, W, _ptr(out), s),
+                         "os2d_train_planes_from_shb")
+        return out
+
+    def conv(layer, src, wp, bp, dst):
+        _lib.check(lib.os2d_transform_conv_f16x3(layer, _ptr(src), _ptr(wp), _ptr(bp), _ptr(dst), NB, P, H, W, 3, status, s),
+                   "os2d_transform_conv_f16x3")
+
+    ws = torch.empty(int(lib.os2d_corr_f16x3_workspace_bytes(A, C, H, W)), dtype=torch.uint8, device=dev)
+    rshb = shb(225)
+    _lib.check(lib.os2d_corr_f16x3(_ptr(fm), _ptr(qs), _ptr(corr), _ptr(rshb), A, B, C, H, W, _ptr(ws), ws.numel(), s), "os2d_corr_f16x3")
+    del ws
+    h1shb = shb(128)
+    conv(1, rshb, w1, b1, h1shb)
+    rnorm = planes(rshb, exps[0], 225, 226)
+    del rshb
+    h2shb = shb(64)
+    conv(2, h1shb, w2, b2, h2shb)
+    h1 = planes(h1shb, exps[1], 128, 128)
+    del h1shb
+    conv(3, h2shb, w3, b3, prm)
+    h2 = planes(h2shb, exps[2], 64, 64)
+    del h2shb
+    return rnorm, h1, h2
+
+
 class _HeadFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, head, n_class, fm, *tensors):
@@ -74,25 +159,19 @@ class _HeadFunction(torch.autograd.Function):
         regressor = head.aligner.parameter_regressor
         P = regressor.output_dim
         inverse = 1 if head.aligner.use_inverse_geom_model else 0
-        w1, b1, w2, b2, w3, b3 = regressor.packed("f32")
         PL = int(lib.os2d_plane_floats(H, W))
         f32 = dict(dtype=torch.float32, device=dev)
-        sumsq = torch.empty(A * HW, **f32)
         corr = torch.empty(NB, 225, HW, **f32)
-        rnorm = torch.empty(NB * 226 * PL, **f32)
-        h1 = torch.empty(NB * 128 * PL, **f32)
-        h2 = torch.empty(NB * 64 * PL, **f32)
         prm = torch.empty(NB, P, HW, **f32)
         loc = torch.empty(A, B, 4, H, W, **f32)
         cls = torch.empty(A, B, 1, H, W, **f32)
         corners = torch.empty(A, B, 8, H, W, **f32)
         with torch.cuda.device(dev):
             s = _lib.current_stream(dev)
-            _lib.check(lib.os2d_fm_sumsq(_ptr(fm), _ptr(sumsq), A, C, H, W, s), "os2d_fm_sumsq")
-            _lib.check(lib.os2d_corr(_ptr(fm), _ptr(head._qp), _ptr(sumsq), _ptr(corr), _ptr(rnorm), A, B, C, H, W, s), "os2d_corr")
-            for layer, src, wp, bp, dst in ((1, rnorm, w1, b1, h1), (2, h1, w2, b2, h2), (3, h2, w3, b3, prm)):
-                _lib.check(lib.os2d_transform_conv(layer, _ptr(src), _ptr(wp), _ptr(bp), _ptr(dst), NB, P, H, W, s),
-                           "os2d_transform_conv")
+            if head.last_train_forward_precision == "f16x3":
+                rnorm, h1, h2 = _stages_f16x3(lib, head, fm, corr, prm, (A, B, C, H, W, P, PL), s)
+            else:
+                rnorm, h1, h2 = _stages_f32(lib, head, fm, corr, prm, (A, B, C, H, W, P, PL), s)
             _lib.check(lib.os2d_sample_decode(_ptr(corr), _ptr(prm), NB, H, W, P, inverse, head._stride, head._rec_field,
                                               _ptr(loc), _ptr(cls), _ptr(corners), s), "os2d_sample_decode")
         q15raw = None
@@ -104,6 +183,8 @@ class _HeadFunction(torch.autograd.Function):
         ctx.deterministic = head.last_deterministic
         ctx.saved = dict(fm=fm, raws=raws, corr=corr, rnorm=rnorm, h1=h1, h2=h2, params=prm, q15raw=q15raw,
                          weights=[p.detach().contiguous() for p in params])
+        if head.keep_train_activations:
+            head.last_train_activations = dict(corr=corr, rnorm=rnorm, h1=h1, h2=h2, params=prm)
         ctx.mark_non_differentiable(corners)
         return loc, cls, cls.clone(), corners
 
@@ -231,9 +312,11 @@ def needs_grad(head, feature_maps):
 def head_forward_train(head, feature_maps):
     """(loc, cls, cls_det, corners) of ``Os2dHead.forward`` with autograd (see the module docstring).  The arithmetic of the
     backward GEMMs is ``head.train_precision`` (None: $OS2D_TRAIN_PRECISION, default "f32"); the one taken is recorded in
-    ``head.last_train_precision``, and whether the backward pass is the bit-reproducible one (``head.deterministic``,
+    ``head.last_train_precision``; the arithmetic of the forward is ``head.train_forward_precision`` (None:
+    $OS2D_TRAIN_FORWARD_PRECISION, default "f32"), recorded in ``head.last_train_forward_precision`` and ``head.last_precision``; whether the backward pass is the bit-reproducible one (``head.deterministic``,
     ``resolve_deterministic``) in ``head.last_deterministic``."""
     head.last_train_precision = resolve_train_precision(head.train_precision)
+    head.last_train_forward_precision = head.last_precision = resolve_train_forward_precision(head.train_forward_precision)
     head.last_deterministic = resolve_deterministic(head.deterministic)
     A, C, H, W = feature_maps.shape
     if W > MAX_W_DIRECT7:

@@ -1,9 +1,18 @@
 """Time the training step of the head at the reference training shape (A = 4 images, B = 15 classes, C = 1024, 38 x 38):
-the HIP training forward (the "f32" route with its intermediates kept) and the HIP backward pass (libos2d_train.so), against
-the same step done eagerly by torch: the oracle's ``head_forward`` under autograd on the same GPU.
+the HIP training forward (the "f32" or the "f16x3" route with its intermediates kept) and the HIP backward pass
+(libos2d_train.so), against the same step done eagerly by torch: the oracle's ``head_forward`` under autograd on the same GPU.
 
     python tools/time_head_backward.py [--reps N] [--no-eager] [--A 4 --B 15 --C 1024 --H 38 --W 38]
                                        [--train-precision f32|f16x3|both] [--deterministic off|on|both]
+                                       [--train-forward-precision f32|f16x3|both]
+
+A training step changes the TransformNet parameters, so the packed weights (and, on the f16x3 forward, the range plan) are
+rebuilt every step: every timed iteration first bumps a parameter's version (an in-place ``add_(0)`` on linear.bias) inside the
+timed region - ``hip_forward_ms``; ``hip_forward_cached_pack_ms`` is the same forward without the bump (packed weights cached).
+``forward_peak_bytes``: what one forward adds to ``torch.cuda.max_memory_allocated`` (intermediates and outputs included).
+``--train-forward-precision``: the arithmetic of the training forward (default: $OS2D_TRAIN_FORWARD_PRECISION, else "f32");
+``both`` runs everything below under f32, f16x3 and f32 again in one process (keys ``forward_f32``, ``forward_f16x3``,
+``forward_f32_again``) - the two f32 figures show the spread of the box.
 
 ``--train-precision``: the arithmetic of the backward GEMMs (default: $OS2D_TRAIN_PRECISION, else "f32"); ``both`` times
 f32, f16x3 and f32 again in one process - the two f32 figures show the spread of the box.
@@ -33,6 +42,7 @@ def main():
     ap.add_argument("--no-eager", action="store_true")
     ap.add_argument("--train-precision", choices=["f32", "f16x3", "both"], default=None)
     ap.add_argument("--deterministic", choices=["off", "on", "both"], default=None)
+    ap.add_argument("--train-forward-precision", choices=["f32", "f16x3", "both"], default=None)
     a = ap.parse_args()
     from os2d_amd.modeling.head import build_os2d_head_creator
     from os2d_amd.structures.feature_map import FeatureMapSize
@@ -65,7 +75,12 @@ def main():
         ts.sort(key=lambda t: t[0] + t[1])
         return ts[len(ts) // 2]
 
-    def hip_step(mid=None):
+    bias = creator.aligner.parameter_regressor.linear.bias
+
+    def hip_step(mid=None, bump=True):
+        if bump:                        # what an optimizer step does to the caches: the packed weights are stale
+            with torch.no_grad():
+                bias.add_(0)
         head = creator.create_os2d_head(raws)
         loc, cls, cls_det, _ = head(fm)
         if mid is not None:
@@ -73,32 +88,61 @@ def main():
         ((loc * gl).sum() + (cls * gc).sum() + (cls_det * gc).sum()).backward()
         return loc
 
+    def figures():
+        fwd, bwd = timed(hip_step)
+        cached, _ = timed(lambda mid=None: hip_step(mid, bump=False))
+        return {"hip_forward_ms": round(fwd, 3), "hip_backward_ms": round(bwd, 3), "hip_step_ms": round(fwd + bwd, 3),
+                "hip_forward_cached_pack_ms": round(cached, 3)}
+
     def timed_step():
         """One timing of hip_step under the creator's settings; with --deterministic both: off, on, off."""
         if a.deterministic != "both":
             creator.deterministic = None if a.deterministic is None else a.deterministic == "on"
-            fwd, bwd = timed(hip_step)
-            return {"hip_forward_ms": round(fwd, 3), "hip_backward_ms": round(bwd, 3)}
+            return figures()
         out = {}
         for key, flag in (("off", False), ("on", True), ("off_again", False)):
             creator.deterministic = flag
-            fwd, bwd = timed(hip_step)
-            out["deterministic_" + key] = {"hip_forward_ms": round(fwd, 3), "hip_backward_ms": round(bwd, 3)}
+            out["deterministic_" + key] = figures()
+        return out
+
+    def forward_peak_bytes():
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        out = creator.create_os2d_head(raws)(fm)
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - before
+        del out
+        return int(peak)
+
+    def under_forward_precision():
+        """Everything --train-precision / --deterministic ask for, under the creator's train_forward_precision."""
+        out = {}
+        if a.train_precision == "both":
+            for key, precision in (("f32", "f32"), ("f16x3", "f16x3"), ("f32_again", "f32")):
+                creator.train_precision = precision
+                out[key] = timed_step()
+        else:
+            creator.train_precision = a.train_precision
+            out.update(timed_step())
+        head = creator.create_os2d_head(raws)
+        head(fm)
+        out["train_forward_precision"] = head.last_train_forward_precision
+        if a.train_precision != "both":
+            out["train_precision"] = head.last_train_precision
+            if a.deterministic != "both":
+                out["deterministic"] = head.last_deterministic
+        out["forward_peak_bytes"] = forward_peak_bytes()
         return out
 
     res = {"shape": [a.A, a.B, a.C, a.H, a.W]}
-    if a.train_precision == "both":
-        for key, precision in (("f32", "f32"), ("f16x3", "f16x3"), ("f32_again", "f32")):
-            creator.train_precision = precision
-            res[key] = timed_step()
+    if a.train_forward_precision == "both":
+        for key, precision in (("forward_f32", "f32"), ("forward_f16x3", "f16x3"), ("forward_f32_again", "f32")):
+            creator.train_forward_precision = precision
+            res[key] = under_forward_precision()
     else:
-        creator.train_precision = a.train_precision
-        res.update(timed_step())
-        head = creator.create_os2d_head(raws)
-        head(fm)
-        res["train_precision"] = head.last_train_precision
-        if a.deterministic != "both":
-            res["deterministic"] = head.last_deterministic
+        creator.train_forward_precision = a.train_forward_precision
+        res.update(under_forward_precision())
     if not a.no_eager:
         st = {k: v.to(dev).requires_grad_(k.endswith("weight") or k.endswith("bias")) for k, v in state.items()}
 
