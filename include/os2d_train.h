@@ -130,6 +130,40 @@ size_t os2d_train_corr_workspace_floats_ex(int arith, int A, int B, int C, int H
 int os2d_train_corr_backward_ex(int arith, const float* fm, const float* qp, const float* dcorr, int A, int B, int C, int H, int W,
                                 float* dfm, float* dq, float* workspace, size_t workspace_floats, void* stream);
 
+/* ==== Batch-statistics ("live") BatchNorm of TransformNet layer 1 (225 -> 128, 7x7) or 2 (128 -> 64, 5x5): what a training
+ * forward runs for a layer whose BatchNorm is in training mode, and its backward (csrc_train/bn_live.hip).
+ * n = NB*H*W values per channel: the data cells of the planes; pad cells are told by index and never read as data.  Plane tensors
+ * 16-byte aligned.  Layer 3 has no BatchNorm: -1.  One grid row per plane: NB * Cout <= 65535, else -1.
+ *
+ * ---- the raw convolution: z [NB,Cout,PLANE] = conv(x) + bias at data cells, +0.0 at every other cell (no BatchNorm, no ReLU).
+ * w [Cout,Cin,k,k] and bias [Cout] as the module holds them; x = rnorm [NB,226,PLANE] (plane 225 is never read) or h1
+ * [NB,128,PLANE].  arith 0: the fp32 GEMM of the backward pass; 1: the split-fp16 GEMM (maxima passes on the device: one word for
+ * the filters, one per pair of x), within fp32 rounding of it.  workspace: os2d_train_conv_forward_workspace_floats floats
+ * (0 = bad argument).                                                                                                       */
+size_t os2d_train_conv_forward_workspace_floats(int arith, int layer, int P, int NB);
+int os2d_train_conv_forward(int arith, int layer, int P, const float* w, const float* bias, const float* x, int NB, int H, int W, float* z,
+                            float* workspace, size_t workspace_floats, void* stream);
+
+/* ---- the statistics of z per channel: mean [C], var [C] (biased: M2 / n) and invstd [C] = 1 / sqrt(var + eps), each rounded
+ * once from fp64.  The second moment is centred: a work-group takes the mean of its slice of pairs, then the squared
+ * distances to it, and the slices are combined in a fixed order (Chan et al.): the same bits on every run.  n < 2: -1.
+ * workspace: os2d_train_bn_workspace_bytes(layer, NB) bytes (0 = bad argument), 16-byte aligned; shared with the backward.  */
+size_t os2d_train_bn_workspace_bytes(int layer, int NB);
+int os2d_train_bn_stats(int layer, const float* z, int NB, int H, int W, float eps, float* mean, float* var, float* invstd,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- h [NB,C,PLANE] = relu(((z - mean) * invstd) * gamma + beta) at data cells, +0.0 elsewhere.                            */
+int os2d_train_bn_relu_forward(int layer, const float* z, const float* gamma, const float* beta, const float* mean, const float* invstd,
+                               int NB, int H, int W, float* h, void* stream);
+
+/* ---- the backward through the statistics: g = dh where h > 0 (the forward's own bits), xhat = (z - mean) * invstd;
+ *   dbeta [C] = sum g, dgamma [C] = sum g xhat (fp64 sums in a fixed order; each may be NULL: not written);
+ *   dy [NB,C,PLANE] = gamma invstd (g - dbeta / n - xhat dgamma / n) at data cells, 0 at pad cells (always written).
+ * The gradient of the convolution's bias is exactly zero on such a layer (a constant shift cancels in z - mean): not computed. */
+int os2d_train_bn_relu_backward_batch(int layer, const float* dh, const float* z, const float* h, const float* gamma, const float* mean,
+                                      const float* invstd, int NB, int H, int W, float* dy, float* dgamma, float* dbeta, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+
 /* ---- class map backward, the inverse of os2d_class_prepare_batch (head.py:241-268): q15 [B,C,225] the resized, NOT normalised
  * maps (cell order i*15 + j; os2d_class_prepare_batch with normalize = 0), dq [B,C,225] from os2d_train_corr_backward.  L2 over
  * C (eps 1e-5) backward, then bilinear-resize backward (align_corners = True, zero padding) into dsrcs[b] [C,h_b,w_b]

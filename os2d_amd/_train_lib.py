@@ -37,6 +37,12 @@ SIGNATURES = {
     "os2d_train_conv_backward_weight_ex": (_i, [_i, _i, _i, _p, _p, _i, _i, _i, _p, _p, _sz, _p]),
     "os2d_train_corr_workspace_floats_ex": (_sz, [_i, _i, _i, _i, _i, _i]),
     "os2d_train_corr_backward_ex": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
+    "os2d_train_conv_forward_workspace_floats": (_sz, [_i, _i, _i, _i]),
+    "os2d_train_conv_forward": (_i, [_i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p, _sz, _p]),
+    "os2d_train_bn_workspace_bytes": (_sz, [_i, _i]),
+    "os2d_train_bn_stats": (_i, [_i, _p, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
+    "os2d_train_bn_relu_forward": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "os2d_train_bn_relu_backward_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "os2d_train_class_backward": (_i, [_p, _p, _i, _i, _p, _p, _p, _sz, _p]),
     "os2d_train_planes_from_shb": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "os2d_train_assign_targets": (_i, [_i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p]),

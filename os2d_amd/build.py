@@ -57,7 +57,9 @@ TRAIN_CSRC = os.path.join(HERE, "csrc_train")
 # gemm_f16x3.hip: the backward GEMMs in split-fp16 arithmetic (the *_ex entry points of train.hip at arith = 1).
 # mining.hip needs no flag: every function of it that rounds (csrc/detect_common.h, mining_crop.h) switches contraction off itself
 # shb_planes.hip: the split-half blocked activations of an f16x3 training forward as the fp32 planes the backward reads
-TRAIN = Library("libos2d_train.so", TRAIN_CSRC, ["train.hip", "gemm_f16x3.hip", "objective.hip", "mining.hip", "shb_planes.hip"], FLAGS + PACKED_OFF,
+# bn_live.hip: batch-statistics BatchNorm of the TransformNet (statistics, normalise + ReLU, backward through the statistics)
+TRAIN = Library("libos2d_train.so", TRAIN_CSRC, ["train.hip", "gemm_f16x3.hip", "objective.hip", "mining.hip", "shb_planes.hip", "bn_live.hip"],
+                FLAGS + PACKED_OFF,
                 {"objective.hip": ["-ffp-contract=off"]},
                 [TRAIN_CSRC, CSRC, SHARED], "os2d_train.h", "OS2D_TRAIN_LIB")
 # The VOC evaluation (include/os2d_eval.h): the kernel list of libos2d_hip.so and the ABI of libos2d_train.so stay what they

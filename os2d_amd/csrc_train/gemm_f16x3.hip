@@ -289,6 +289,20 @@ int os2d_f16x3_conv_data(const float* wt, const float* dy, float* dx, int cout, 
                            stream, "conv data gradient (f16x3)");
 }
 
+int os2d_f16x3_conv_forward(const float* w, const float* bias, const float* x, int xplanes, float* z, int cout, int cin, int ks, int NB,
+                            int H, int W, unsigned* words, hipStream_t stream) {
+  const int PL = os2d_plane(H, W), T2 = ks * ks, K = cin * T2;
+  int rc = clear_words(words, 1 + (size_t)NB, stream);
+  if (rc) return rc;
+  if ((rc = absmax(SrcPlain{w, 0}, 1, (size_t)cout * K, MaxWord{words, 1, 1}, MaxWord{nullptr, 1, 1}, stream))) return rc;
+  // the cin planes the layer reads of the xplanes a pair has
+  if ((rc = absmax(SrcPlain{x, (size_t)xplanes * PL}, NB, (size_t)cin * PL, MaxWord{words + 1, 1, NB}, MaxWord{nullptr, 1, 1}, stream))) return rc;
+  const Taps tp{ks, ks / 2, os2d_ws(W), T2};
+  return gemm_f16x3<false, true>(LdRows{w, K, aligned16(w) && (K & 3) == 0}, LdShifted{x, (size_t)xplanes * PL, PL, tp},
+                                 StPlane{z, (size_t)cout * PL, PL, H, W, bias}, ScaleWord{words, 1, 1}, ScaleWord{words + 1, 1, NB}, cout, PL,
+                                 K, NB, 0, stream, "conv forward (f16x3)");
+}
+
 int os2d_f16x3_conv_weight(const float* x, int xplanes, const float* dy, float* part, int cout, int cin, int ks, int NB, int H, int W,
                            int splits, int ksplit, unsigned* words, hipStream_t stream) {
   const int PL = os2d_plane(H, W), T2 = ks * ks, N = cin * T2;

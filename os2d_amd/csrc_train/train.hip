@@ -7,6 +7,8 @@
 //   * the transposed convolutions (B = the output gradient read at the tap offsets of the zero-bordered plane layout),
 //   * the weight gradients (an implicit GEMM over K = NB * PLANE positions, split-K, partial sums added in a fixed order),
 //   * the two correlation GEMMs (d F^ = Q^T d corr per image, d Q^ = d corr F^T per class).
+//   * the forward convolution of a layer whose BatchNorm takes batch statistics (os2d_train_conv_forward: the data gradient's
+//     launch with the raw filters as the A operand and the bias added in the store; bn_live.hip has the BatchNorm itself).
 // The rest is per-location work: resample / pool / box decode backward, BatchNorm + ReLU masks, the two L2 normalisations
 // and the bilinear class-map resize.
 #include <stdio.h>
@@ -756,6 +758,48 @@ int os2d_train_conv_backward_data_ex(int arith, int layer, int P, const float* w
 int os2d_train_conv_backward_data(int layer, int P, const float* w, const float* dy, int NB, int H, int W, float* dx,
                                   float* workspace, size_t workspace_floats, void* stream) {
   return os2d_train_conv_backward_data_ex(0, layer, P, w, dy, NB, H, W, dx, workspace, workspace_floats, stream);
+}
+
+// the forward convolution of a layer whose BatchNorm takes batch statistics: the data gradient's GEMM with the roles of the
+// channel counts swapped, the raw (unflipped) filters as the A operand and the bias added in the store
+size_t os2d_train_conv_forward_workspace_floats(int arith, int layer, int P, int NB) {
+  Layer L;
+  if ((layer != 1 && layer != 2) || !layer_shape(layer, P, &L) || NB < 1) return 0;
+  return arith == 0 ? 1 : arith == 1 ? 1 + (size_t)NB : 0;      // f16x3: the maxima words (the filters', one per pair of x)
+}
+
+int os2d_train_conv_forward(int arith, int layer, int P, const float* w, const float* bias, const float* x, int NB, int H, int W, float* z,
+                            float* workspace, size_t workspace_floats, void* stream) {
+  os2d_clear_error();
+  Layer L;
+  if (arith != 0 && arith != 1) {
+    os2d_set_error("os2d_train_conv_forward: bad arith %d (0 = fp32, 1 = f16x3)", arith);
+    return -1;
+  }
+  if ((layer != 1 && layer != 2) || !layer_shape(layer, P, &L)) {
+    os2d_set_error("os2d_train_conv_forward: bad layer %d / P %d (the layers with a BatchNorm: 1 or 2)", layer, P);
+    return -1;
+  }
+  if (!w || !bias || !x || !z || !workspace) {
+    os2d_set_error("os2d_train_conv_forward: null pointer");
+    return -1;
+  }
+  if (!shape_ok(NB, H, W) || (size_t)NB * L.cout > 65535) {
+    os2d_set_error("os2d_train_conv_forward: bad shape NB=%d H=%d W=%d (W <= %d, NB * %d <= 65535)", NB, H, W, OS2D_MAX_W_DIRECT7, L.cout);
+    return -1;
+  }
+  const size_t need = arith ? 1 + (size_t)NB : 1;
+  if (workspace_floats < need) {
+    os2d_set_error("os2d_train_conv_forward: workspace %zu floats < %zu", workspace_floats, need);
+    return -2;
+  }
+  if (arith)
+    return os2d_f16x3_conv_forward(w, bias, x, input_planes(layer), z, L.cout, L.cin, L.ks, NB, H, W, reinterpret_cast<unsigned*>(workspace),
+                                   os2d_stream(stream));
+  const int PL = os2d_plane(H, W), T2 = L.ks * L.ks;
+  const Taps tp{L.ks, L.ks / 2, os2d_ws(W), T2};
+  return gemm<false>(LdRows{w, L.cin * T2}, LdShifted{x, (size_t)input_planes(layer) * PL, PL, tp},
+                     StPlane{z, (size_t)L.cout * PL, PL, H, W, bias}, L.cout, PL, L.cin * T2, NB, 0, os2d_stream(stream), "conv forward");
 }
 
 size_t os2d_train_conv_weight_slice_floats(int layer, int P) { return os2d_train_conv_data_workspace_floats(layer, P); }

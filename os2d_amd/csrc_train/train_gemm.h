@@ -71,13 +71,15 @@ struct LdShifted {
     }
   }
 };
-// out[z][m][n] of a plane buffer, zero at the pad cells
+// out[z][m][n] of a plane buffer, zero at the pad cells; `bias` (NULL: none) is a per-row constant added at the data cells - a
+// forward convolution's bias (one functor for both, so that the data gradient and the forward convolution share a kernel)
 struct StPlane {
   float* out;
   size_t zstride;
   int PL, H, W;
+  const float* bias = nullptr;
   __device__ __forceinline__ void operator()(int z, int m, int n, float v) const {
-    out[z * zstride + (size_t)m * PL + n] = os2d_interior(n, H, W) ? v : 0.f;
+    out[z * zstride + (size_t)m * PL + n] = os2d_interior(n, H, W) ? (bias ? v + bias[m] : v) : 0.f;
   }
 };
 // weight gradient: A(o, k = (pair, n)) = dy[pair][o][n]
@@ -215,6 +217,11 @@ struct LdCorrCols {
 // conv data gradient: wt = the flipped filters [cin][cout*T2]; words: 1 + NB
 int os2d_f16x3_conv_data(const float* wt, const float* dy, float* dx, int cout, int cin, int ks, int NB, int H, int W, unsigned* words,
                          hipStream_t stream);
+// forward convolution z = conv(x) + bias (the training forward of a layer whose BatchNorm takes batch statistics): w = the raw
+// filters [cout][cin*T2] - a forward convolution is the data gradient's shape with the channel counts swapped and unflipped
+// filters -, xplanes = planes per pair of x; words: 1 + NB (the filters', one per pair of x)
+int os2d_f16x3_conv_forward(const float* w, const float* bias, const float* x, int xplanes, float* z, int cout, int cin, int ks, int NB,
+                            int H, int W, unsigned* words, hipStream_t stream);
 // conv weight gradient into `splits` partial slices of ksplit positions (a multiple of OS2D_F16X3_KSTEP); xplanes = planes per
 // pair of x; words: 2
 #define OS2D_F16X3_KSTEP 32

@@ -166,17 +166,52 @@ class TransformationNet(nn.Module):
             if isinstance(layer, nn.BatchNorm2d):
                 layer.eval()
 
-    def check_ready(self):
-        """The HIP kernels need the parameters on a HIP device and eval-mode BatchNorm; said here, before ``packed`` /
-        ``spectra`` run torch operators on them (CPU-resident parameters used to surface as torch errors)."""
+    def live_batchnorm(self):
+        """(conv.1, conv.4): True where the BatchNorm takes the statistics of the call's own batch - the layer is in training
+        mode inside a net in training mode (the condition ``check_ready`` has always refused).  Only the training route of the
+        head (head_train.py) runs such a layer."""
+        return tuple(bool(self.training and bn.training) for bn in (self.conv[1], self.conv[4]))
+
+    def check_ready(self, allow_live_batchnorm=False):
+        """The HIP kernels need the parameters on a HIP device and - everywhere but on the head's training route
+        (``allow_live_batchnorm``) - eval-mode BatchNorm; said here, before ``packed`` / ``spectra`` run torch operators on them
+        (CPU-resident parameters used to surface as torch errors)."""
         dev = self.linear.weight.device
         if dev.type != "cuda":
             raise RuntimeError("TransformationNet parameters are on {}: move the model to the HIP device "
                                "(no CPU fallback)".format(dev))
         if self.training and any(isinstance(m, nn.BatchNorm2d) and m.training for m in self.modules()):
-            raise RuntimeError("TransformationNet is in training mode: the HIP path implements eval-mode "
-                               "BatchNorm (running statistics) only; call .eval()")
+            if not allow_live_batchnorm:
+                raise RuntimeError("TransformationNet is in training mode: the HIP path implements eval-mode "
+                                   "BatchNorm (running statistics) only; call .eval()")
+            for name, bn, live in zip(("conv.1", "conv.4"), (self.conv[1], self.conv[4]), self.live_batchnorm()):
+                if live and bn.momentum is None:
+                    raise ValueError("{}: momentum=None (a cumulative average) is not implemented for a training-mode BatchNorm".format(name))
+                if live and not bn.track_running_stats:
+                    raise ValueError("{}: track_running_stats=False is not implemented for a training-mode BatchNorm".format(name))
         return dev
+
+    def packed_linear_f32(self):
+        """(w3, b3) of ``packed("f32")`` for the last layer alone (it has no BatchNorm): what the training route takes when a
+        BatchNorm of the layers before it runs on batch statistics, where nothing can be folded ahead of the call.  Cached until
+        the layer's weight or bias changes."""
+        ts = (self.linear.weight, self.linear.bias)
+        key = ("linear.f32",) + tuple((t.data_ptr(), t._version, str(t.device)) for t in ts)
+        dev = self.linear.weight.device
+        cached = self._packed_cache.get("linear.f32")
+        if cached is not None and cached.key == key:
+            return cached.get(dev)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            w = _require_device_f32(self.linear.weight.detach(), "conv weight")
+            b = _require_device_f32(self.linear.bias.detach(), "conv bias")
+            pw = torch.empty(lib.os2d_packed_conv_floats(3), dtype=torch.float32, device=dev)
+            pb = torch.zeros(lib.os2d_packed_bias_floats(3), dtype=torch.float32, device=dev)
+            _lib.check(lib.os2d_pack_conv(3, self.output_dim, _lib.ptr(w), _lib.ptr(b), None, None, None, None, ctypes.c_float(0.0),
+                                          _lib.ptr(pw), _lib.ptr(pb), _lib.current_stream(dev)), "os2d_pack_conv")
+            result = (pw, pb)
+            self._packed_cache["linear.f32"] = _StreamOrdered(key, result, dev)
+        return result
 
     def _state_key(self):
         ts = list(self.parameters()) + list(self.buffers())
@@ -601,6 +636,7 @@ class Os2dHead(nn.Module):
         self.last_train_activations = None
         self.deterministic = None          # bit-reproducible backward: None = $OS2D_DETERMINISTIC, else torch's deterministic flag; True / False
         self.last_deterministic = None     # what the last training forward resolved (head_train.py)
+        self.last_live_batchnorm = None    # (conv.1, conv.4): which BatchNorms the last training forward ran on batch statistics
         # sticky status word of the split-fp16 kernels in mapped pinned host memory (one per device, process lifetime:
         # ``device_status_word``): the kernels store to it only when an activation leaves the fp16 range (impossible for
         # finite inputs, see TransformationNet.range_plan), the host reads it without synchronising
@@ -683,9 +719,11 @@ class Os2dHead(nn.Module):
         if feature_maps.dim() != 4:
             raise RuntimeError("feature_maps must be [A,C,H,W], got {}".format(tuple(feature_maps.shape)))
         _resolve(precision or self.precision)          # a bad precision is refused on every route
-        if out is None and stage_events is None and head_train.needs_grad(self, feature_maps):
+        if out is None and stage_events is None and (head_train.needs_grad(self, feature_maps)
+                                                      or any(self.aligner.parameter_regressor.live_batchnorm())):
             # training: the strict-fp32 route - or, with ``train_forward_precision = "f16x3"``, the direct split-fp16 one - stage by
-            # stage, with a HIP backward pass (``precision`` / ``route_pairs`` do not apply)
+            # stage, with a HIP backward pass (``precision`` / ``route_pairs`` do not apply).  A training-mode BatchNorm of the
+            # TransformNet comes here under torch.no_grad() too: it normalises with batch statistics and updates the running ones
             if feature_maps.size(1) != self.class_feature_maps.size(1):
                 raise RuntimeError("Feature dimensionality of input={0} and class={1} feature maps has to equal".format(
                     feature_maps.size(1), self.class_feature_maps.size(1)))

@@ -18,6 +18,10 @@ multiplied with.
 With ``deterministic = True`` on the head or its creator (or $OS2D_DETERMINISTIC, or torch.use_deterministic_algorithms(True))
 the d corr scatter of the decode backward adds 64-bit integers on a fixed-point grid instead of fp32 atomics: two passes on the
 same inputs then return the same bits for every gradient.
+A BatchNorm of the TransformNet in training mode ("live": ``TransformationNet.live_batchnorm``) takes the statistics of the call's
+own batch, updates its running statistics as torch does - under torch.no_grad() too - and its backward goes through the statistics
+(``_stages_live``; os2d_train_conv_forward / _bn_stats / _bn_relu_forward / _bn_relu_backward_batch); the bias
+of the convolution in front of it gets an exactly zero gradient.  ``head.last_live_batchnorm`` records which layers were live.
 As in the reference (head.py:396-402, 423): ``cls_det`` carries the same values as ``cls`` but its gradient reaches the
 correlation only, not the transformation; ``corners`` carries none.
 """
@@ -147,6 +151,74 @@ def _stages_f16x3(lib, head, fm, corr, prm, shape, s):
     return rnorm, h1, h2
 
 
+def _update_running_stats(bn, mean, var, n):
+    """torch's training-mode update of a BatchNorm's buffers from the batch statistics (biased ``var`` of ``n`` values), as a few
+    in-place torch ops on the device: no host synchronisation, and the buffers' ``_version`` moves, which is what the
+    packed-weight and spectra caches of the TransformNet are keyed on."""
+    m = float(bn.momentum)
+    bn.running_mean.mul_(1.0 - m).add_(mean, alpha=m)
+    bn.running_var.mul_(1.0 - m).add_(var, alpha=m * n / (n - 1.0))
+    bn.num_batches_tracked.add_(1)
+
+
+def _stages_live(lib, head, fm, corr, prm, shape, s, live, forward_precision):
+    """The stages up to the transformation parameters when a BatchNorm of the TransformNet takes batch statistics (DESIGN.md
+    section 16).  Both layers with a BatchNorm run os2d_train_conv_forward (the raw convolution z; arith = the forward
+    precision) and os2d_train_bn_relu_forward; a live layer gets its mean and 1 / sqrt(var + eps) from os2d_train_bn_stats and
+    updates its running statistics, a frozen layer beside it gets the running ones (its eval-mode fold, applied after the
+    convolution instead of folded into it).  Layer 3 has no BatchNorm and keeps its fp32 kernel.  Returns
+    (rnorm, h1, h2, [(z, mean, invstd) or None per layer])."""
+    A, B, C, H, W, P, PL = shape
+    NB, HW = A * B, H * W
+    dev = fm.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    tl = _train_lib.load()
+    regressor = head.aligner.parameter_regressor
+    arith = TRAIN_FORWARD_PRECISIONS.index(forward_precision)
+    rnorm = torch.empty(NB * 226 * PL, **f32)
+    if arith:
+        qs = head._split_class_operand()
+        ws = torch.empty(int(lib.os2d_corr_f16x3_workspace_bytes(A, C, H, W)), dtype=torch.uint8, device=dev)
+        rshb = torch.empty(NB * int(lib.os2d_shb_bytes(225, H, W)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.os2d_corr_f16x3(_ptr(fm), _ptr(qs), _ptr(corr), _ptr(rshb), A, B, C, H, W, _ptr(ws), ws.numel(), s), "os2d_corr_f16x3")
+        # the exponent of the normalised correlation is a constant of the library: it does not depend on the BatchNorms
+        exp0 = torch.full((225,), int(lib.os2d_rnorm_exp()), dtype=torch.int32, device=dev)
+        _train_lib.check(tl.os2d_train_planes_from_shb(_ptr(rshb), _ptr(exp0), NB, 225, 226, H, W, _ptr(rnorm), s),
+                         "os2d_train_planes_from_shb")
+        del ws, rshb
+    else:
+        sumsq = torch.empty(A * HW, **f32)
+        _lib.check(lib.os2d_fm_sumsq(_ptr(fm), _ptr(sumsq), A, C, H, W, s), "os2d_fm_sumsq")
+        _lib.check(lib.os2d_corr(_ptr(fm), _ptr(head._qp), _ptr(sumsq), _ptr(corr), _ptr(rnorm), A, B, C, H, W, s), "os2d_corr")
+    src, acts, kept = rnorm, [], []
+    layers = ((1, regressor.conv[0], regressor.conv[1], 128), (2, regressor.conv[3], regressor.conv[4], 64))
+    for (layer, conv, bn, cout), is_live in zip(layers, live):
+        z = torch.empty(NB * cout * PL, **f32)
+        cws = torch.empty(int(tl.os2d_train_conv_forward_workspace_floats(arith, layer, P, NB)), **f32)
+        _train_lib.check(tl.os2d_train_conv_forward(arith, layer, P, _ptr(conv.weight.detach().contiguous()),
+                                                    _ptr(conv.bias.detach().contiguous()), _ptr(src), NB, H, W, _ptr(z), _ptr(cws),
+                                                    cws.numel(), s), "os2d_train_conv_forward")
+        if is_live:
+            mean, var, invstd = (torch.empty(cout, **f32) for _ in range(3))
+            bws = torch.empty(int(tl.os2d_train_bn_workspace_bytes(layer, NB)), dtype=torch.uint8, device=dev)
+            _train_lib.check(tl.os2d_train_bn_stats(layer, _ptr(z), NB, H, W, ctypes.c_float(float(bn.eps)), _ptr(mean), _ptr(var),
+                                                    _ptr(invstd), _ptr(bws), bws.numel(), s), "os2d_train_bn_stats")
+            _update_running_stats(bn, mean, var, float(NB * HW))
+        else:
+            mean = bn.running_mean.detach().contiguous()
+            invstd = 1.0 / torch.sqrt(bn.running_var.detach() + float(bn.eps))
+        h = torch.empty(NB * cout * PL, **f32)
+        _train_lib.check(tl.os2d_train_bn_relu_forward(layer, _ptr(z), _ptr(bn.weight.detach().contiguous()),
+                                                       _ptr(bn.bias.detach().contiguous()), _ptr(mean), _ptr(invstd), NB, H, W, _ptr(h), s),
+                         "os2d_train_bn_relu_forward")
+        kept.append((z, mean, invstd) if is_live else None)
+        acts.append(h)
+        src = h
+    w3, b3 = regressor.packed_linear_f32()
+    _lib.check(lib.os2d_transform_conv(3, _ptr(acts[1]), _ptr(w3), _ptr(b3), _ptr(prm), NB, P, H, W, s), "os2d_transform_conv")
+    return rnorm, acts[0], acts[1], kept
+
+
 class _HeadFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, head, n_class, fm, *tensors):
@@ -168,7 +240,11 @@ class _HeadFunction(torch.autograd.Function):
         corners = torch.empty(A, B, 8, H, W, **f32)
         with torch.cuda.device(dev):
             s = _lib.current_stream(dev)
-            if head.last_train_forward_precision == "f16x3":
+            live, kept = head.last_live_batchnorm, [None, None]
+            if any(live):
+                rnorm, h1, h2, kept = _stages_live(lib, head, fm, corr, prm, (A, B, C, H, W, P, PL), s, live,
+                                                   head.last_train_forward_precision)
+            elif head.last_train_forward_precision == "f16x3":
                 rnorm, h1, h2 = _stages_f16x3(lib, head, fm, corr, prm, (A, B, C, H, W, P, PL), s)
             else:
                 rnorm, h1, h2 = _stages_f32(lib, head, fm, corr, prm, (A, B, C, H, W, P, PL), s)
@@ -182,7 +258,7 @@ class _HeadFunction(torch.autograd.Function):
         ctx.arith = TRAIN_PRECISIONS.index(head.last_train_precision)
         ctx.deterministic = head.last_deterministic
         ctx.saved = dict(fm=fm, raws=raws, corr=corr, rnorm=rnorm, h1=h1, h2=h2, params=prm, q15raw=q15raw,
-                         weights=[p.detach().contiguous() for p in params])
+                         weights=[p.detach().contiguous() for p in params], live=kept)
         if head.keep_train_activations:
             head.last_train_activations = dict(corr=corr, rnorm=rnorm, h1=h1, h2=h2, params=prm)
         ctx.mark_non_differentiable(corners)
@@ -244,6 +320,15 @@ class _HeadFunction(torch.autograd.Function):
                 dy = torch.empty(NB * cout * PL, **f32)
                 dg = torch.empty(cout, **f32) if need_p[ig] else None
                 dbe = torch.empty(cout, **f32) if need_p[ib] else None
+                if sv["live"][layer - 1] is not None:
+                    # batch statistics: the backward goes through them; the convolution's bias cancels in z - mean
+                    z, mean, invstd = sv["live"][layer - 1]
+                    ws = torch.empty(int(tl.os2d_train_bn_workspace_bytes(layer, NB)), dtype=torch.uint8, device=dev)
+                    _train_lib.check(tl.os2d_train_bn_relu_backward_batch(layer, _ptr(dh), _ptr(z), _ptr(h), _ptr(gamma), _ptr(mean),
+                                                                          _ptr(invstd), NB, H, W, _ptr(dy), _ptr(dg), _ptr(dbe), _ptr(ws),
+                                                                          ws.numel(), s), "os2d_train_bn_relu_backward_batch")
+                    grads[ig], grads[ib], grads[iw] = dg, dbe, (torch.zeros(cout, **f32) if need_p[iw] else None)
+                    return dy
                 db = torch.empty(cout, **f32) if need_p[iw] else None
                 _train_lib.check(tl.os2d_train_bn_relu_backward(layer, _ptr(dh), _ptr(h), _ptr(gamma), _ptr(beta),
                                                                 _ptr(bn.running_var.detach().contiguous()), ctypes.c_float(float(bn.eps)),
@@ -323,10 +408,17 @@ def head_forward_train(head, feature_maps):
         raise RuntimeError("autograd through the HIP head needs feature maps at most {} columns wide (the direct 7x7 kernels of the "
                            "training forward), got W={}: crop the training images".format(MAX_W_DIRECT7, W))
     regressor = head.aligner.parameter_regressor
-    regressor.check_ready()
+    regressor.check_ready(allow_live_batchnorm=True)
+    # which BatchNorms take the statistics of this call's batch (each follows its own training flag); recorded for the caller
+    head.last_live_batchnorm = regressor.live_batchnorm()
     _train_lib.load()                       # a missing backward library is an error now, not at backward time
     raws = list(head._raw_class_maps) if head._raw_class_maps is not None else []
     for r in raws:
         if r.device != feature_maps.device or r.dtype != torch.float32:
             raise RuntimeError("raw class maps must be float32 on {}".format(feature_maps.device))
-    return _HeadFunction.apply(head, len(raws), feature_maps, *raws, *transform_parameters(regressor))
+    out = _HeadFunction.apply(head, len(raws), feature_maps, *raws, *transform_parameters(regressor))
+    if not needs_grad(head, feature_maps):
+        # a training-mode BatchNorm without autograd (torch.no_grad(), or nothing requires grad): one recognition tensor, as on
+        # the inference route
+        return out[0], out[1], out[1], out[3]
+    return out

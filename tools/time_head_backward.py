@@ -4,7 +4,7 @@ the HIP training forward (the "f32" or the "f16x3" route with its intermediates 
 
     python tools/time_head_backward.py [--reps N] [--no-eager] [--A 4 --B 15 --C 1024 --H 38 --W 38]
                                        [--train-precision f32|f16x3|both] [--deterministic off|on|both]
-                                       [--train-forward-precision f32|f16x3|both]
+                                       [--train-forward-precision f32|f16x3|both] [--live-bn]
 
 A training step changes the TransformNet parameters, so the packed weights (and, on the f16x3 forward, the range plan) are
 rebuilt every step: every timed iteration first bumps a parameter's version (an in-place ``add_(0)`` on linear.bias) inside the
@@ -19,6 +19,9 @@ f32, f16x3 and f32 again in one process - the two f32 figures show the spread of
 ``--deterministic``: the d corr scatter of the decode backward (default: what the head resolves, see
 ``head_train.resolve_deterministic``); ``both`` times off, on and off again in one process, under the one train precision given
 (or each of the three runs of ``--train-precision both``) - the two "off" figures show the spread of the box.
+``--live-bn``: after the figures above (the BatchNorms of the TransformNet frozen, as always), the same figures with both of
+them in training mode - batch statistics, DESIGN.md section 16 - under key ``live_bn``, in the same process; the eager column
+then has ``eager_live_forward_ms`` / ``eager_live_backward_ms`` too: the oracle with ``F.batch_norm(training=True)``.
 Per-kernel times: run it under ``rocprofv3 --kernel-trace --stats -- python tools/time_head_backward.py --reps 1 --no-eager``.
 Prints one JSON line."""
 import argparse
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--train-precision", choices=["f32", "f16x3", "both"], default=None)
     ap.add_argument("--deterministic", choices=["off", "on", "both"], default=None)
     ap.add_argument("--train-forward-precision", choices=["f32", "f16x3", "both"], default=None)
+    ap.add_argument("--live-bn", action="store_true")
     a = ap.parse_args()
     from os2d_amd.modeling.head import build_os2d_head_creator
     from os2d_amd.structures.feature_map import FeatureMapSize
@@ -135,16 +139,35 @@ def main():
         out["forward_peak_bytes"] = forward_peak_bytes()
         return out
 
-    res = {"shape": [a.A, a.B, a.C, a.H, a.W]}
-    if a.train_forward_precision == "both":
-        for key, precision in (("forward_f32", "f32"), ("forward_f16x3", "f16x3"), ("forward_f32_again", "f32")):
-            creator.train_forward_precision = precision
-            res[key] = under_forward_precision()
-    else:
-        creator.train_forward_precision = a.train_forward_precision
-        res.update(under_forward_precision())
+    def under_every_forward_precision(res):
+        if a.train_forward_precision == "both":
+            for key, precision in (("forward_f32", "f32"), ("forward_f16x3", "f16x3"), ("forward_f32_again", "f32")):
+                creator.train_forward_precision = precision
+                res[key] = under_forward_precision()
+        else:
+            creator.train_forward_precision = a.train_forward_precision
+            res.update(under_forward_precision())
+        return res
+
+    res = under_every_forward_precision({"shape": [a.A, a.B, a.C, a.H, a.W]})
+    if a.live_bn:
+        net = creator.aligner.parameter_regressor
+        net.train()                     # both BatchNorms on batch statistics
+        res["live_bn"] = under_every_forward_precision({})
+        net.eval()
     if not a.no_eager:
         st = {k: v.to(dev).requires_grad_(k.endswith("weight") or k.endswith("bias")) for k, v in state.items()}
+
+        import torch.nn.functional as F
+
+        def live_transform_net(corr, state):
+            """oracle.transform_net with both BatchNorms in training mode (they update the running statistics, as the head does)."""
+            x = O.l2_normalize_channels(F.relu(corr), 1e-6)
+            for conv, bn, pad in (("conv.0", "conv.1", 3), ("conv.3", "conv.4", 2)):
+                x = F.conv2d(x, state[conv + ".weight"], state[conv + ".bias"], padding=pad)
+                x = F.relu(F.batch_norm(x, state[bn + ".running_mean"], state[bn + ".running_var"], state[bn + ".weight"],
+                                        state[bn + ".bias"], training=True, momentum=0.1, eps=O.BN_EPS))
+            return F.conv2d(x, state["linear.weight"], state["linear.bias"], padding=2)
 
         def eager_step(mid=None):
             with torch.device(dev):          # the oracle builds its grids / masks with default-device factories
@@ -154,11 +177,18 @@ def main():
                 mid.record()
             ((loc * gl).sum() + (cls * gc).sum() + (cls_det * gc).sum()).backward()
             return loc
+        frozen_transform_net = O.transform_net
         try:
             efwd, ebwd = timed(eager_step)
             res.update({"eager_forward_ms": round(efwd, 3), "eager_backward_ms": round(ebwd, 3)})
+            if a.live_bn:
+                O.transform_net = live_transform_net        # head_forward looks the function up in its module
+                efwd, ebwd = timed(eager_step)
+                res.update({"eager_live_forward_ms": round(efwd, 3), "eager_live_backward_ms": round(ebwd, 3)})
         except RuntimeError as e:       # report, do not hide: the comparison point is missing
             res["eager_error"] = str(e)[:300]
+        finally:
+            O.transform_net = frozen_transform_net
     print(json.dumps(res))
 
 
