@@ -38,12 +38,20 @@
 // Radix 2 in the column direction of the FORWARD transform for P = 64 (the instantiations with 8 k-steps: every plan with
 // Pp = 64 has P = 64, see dft_plan_transform).  One decimation step makes the dense 64-point matrix block-diagonal:
 //   E = F32 . R[even h], O = F32 . R[odd h];   X[u] = E[u] + w^u O[u], X[u + 32] = E[u] - w^u O[u], w = exp(-2 pi i / 64)
-// Row tiles 0, 1 of step 2 are the even block, 2, 3 the odd block, both with the SAME 64 x 64 real matrix (stored once): 4
-// k-steps instead of 8, half the matrix instructions and half the fragment registers.  The kernel orders the window rows
-// parity-major when it writes x (an index map in the W phase: step 1 then delivers R parity-major for free) and applies the
-// butterfly in fp32 where it streams the staged spectra out.  The 32 twiddles are a float64-built table behind the half-size
-// matrix.  (The mirror image in step A of the inverse kernel - butterfly in WY, two 32-point products, row 2 m + parity in WT -
-// was built and measured: step A does not shrink at 1024 pairs and the epilogue grows; tools/patches/dft_inverse_radix2.patch.)
+// Half the matrix instructions of the dense product.  The kernel orders the window rows parity-major when it writes x (an index
+// map in the W phase), so row tile wv of step 1 - the tile wave wv owns - is one (image, row parity) block: 32 rows h' by all 96
+// columns (v, re|im), exactly the K of that block's 32-point transform.  Step 1's rows therefore never leave the wave: its
+// accumulators, scaled and split, ARE the B operand of step 2 (an accumulator holds column lane & 31 and rows 8 q + 4 (lane >> 5)
+// + e; a B fragment wants column lane & 31 and 8 consecutive k per half-wave - two runs q of a lane, once the k order of the row
+// operand is permuted to h' = 8 (2 a + t / 4) + 4 (lane >> 5) + t % 4 for k-step a, element t).  The row operand is real, 64 x 32:
+// 32 rows of cosines, 32 of sines, the same for every wave (32 fragment registers); the complex combination
+//   E | O [u] = (C R_re + S R_im) + i (C R_im - S R_re)
+// couples the lanes of columns (v, re) and (v, im): one swap of neighbouring lanes (a DPP operand).  No LDS round trip of R and
+// no barrier between step 1 and the staging of E | O: four barriers per iteration.  The butterfly is applied in fp32 where the
+// staged spectra are streamed out; its 32 twiddles are a float64-built table behind the matrix.  (The dense products keep the
+// R phase: their row tiles of step 1 mix images or the k of step 2 spans re and im of every row.  The mirror image in step A of
+// the inverse kernel - butterfly in WY, two 32-point products, row 2 m + parity in WT - was built and measured: step A does not
+// shrink at 1024 pairs and the epilogue grows; tools/patches/dft_inverse_radix2.patch.)
 #pragma once
 
 #ifndef DFT_DEV
@@ -58,6 +66,9 @@
 #endif
 #ifndef DFT_LANDED
 #define DFT_LANDED(X)             /* device build: an empty asm that reads and writes X - see the Fp2 fragments in the forward kernel */
+#endif
+#ifndef DFT_SWAP1
+#define DFT_SWAP1(V) DFT_SHFL_XOR(V, 1)      /* the float of lane ^ 1 (device build: a DPP operand, no LDS crossbar) */
 #endif
 #ifndef DFT_FWD_PREFETCH_AFTER
 #define DFT_FWD_PREFETCH_AFTER 2  /* the next window's loads right AFTER step 2 instead of in front of it: 0 never, 1 always, 2 for the
@@ -132,8 +143,9 @@ DFT_HD unsigned dft_magic(unsigned d) { return d > 1 ? (unsigned)(((1ull << 32) 
 // sizes of the constant operand arrays of a (P, Q) transform, in 16-byte units: they depend on P and Q only, so every map
 // (and every tiling) that uses the transform shares them
 DFT_HD int dft_units_fqt(int P, int Q) { return (dft_round_up(Q, 16) / 8) * 2 * dft_round_up(Q + 2, 32); }
-// P = 64 (radix 2 in the forward kernel): Fp2 is the 64 x 64 real matrix of the 32-point transform [k / 8 = 8][hi|lo][64 rows] followed by
-// DFT_R2_TWU units of twiddles: float [32][re|im] = exp(-2 pi i u / 64)
+// P = 64 (radix 2 in the forward kernel): Fp2 is a block of DFT_R2_MATU units - the 64 x 32 real matrix of the 32-point transform
+// [k group = 4][hi|lo][64 rows: cos | sin] in its first half, zeros behind it - followed by DFT_R2_TWU units of twiddles:
+// float [32][re|im] = exp(-2 pi i u / 64)
 constexpr int DFT_R2_P = 64, DFT_R2_MATU = 8 * 2 * 64, DFT_R2_TWU = 16;
 // the 1024 bytes behind the union region of LDS (lds_total): the inverse kernel keeps its per-image maxima in the first 256, the
 // forward kernel of the 64-row transform its twiddles (DFT_R2_TWU units = 256 bytes) from this offset
@@ -471,8 +483,10 @@ DFT_DEV void dft_product_lds_any(f32x16* acc, int ntiles, int ks0, int ks1, cons
 //   Fp2 [k = (ri * Pp + h) / 8][hi|lo][m = 2 u + ro]  value = ro == 0 ? (ri == 0 ? cos : sin) : (ri == 0 ? -sin : cos) of 2 pi u h / P
 //   E2  [k = (ri * Pp + u) / 8][hi|lo][m = 2 h + ro]  value = ro == 0 ? (ri == 0 ? cos : -sin) : (ri == 0 ? sin : cos)
 //   Gq  [k = (2 v + ri) / 8][hi|lo][n = w]            value = a_v * E_Q[v w].{re, im}, a_0 = a_{Q/2} = 1, else 2   * 2^13
-// P = 64 (dft_radix2): Fp2 is the matrix of the 32-point transform, the same formula with (P, Pp) = (32, 32) - 64 rows,
-// k < 64 - followed by the twiddle units: float (cos, sin) of -2 pi u / 64, u = 0 .. 31 (two u per unit, rounded once from float64)
+// P = 64 (dft_radix2): Fp2 is the REAL matrix of the 32-point transform with the k order of step 1's accumulators,
+//   Fp2 [kidx = 2 a + hw < 4][hi|lo][m < 64]       value(t) = m < 32 ? cos : sin of 2 pi (m % 32) h' / 32,  h' = 8 (2 a + t / 4) + 4 hw + t % 4
+// (k-step a, half-wave hw, element t of the unit), zero units up to DFT_R2_MATU, then the twiddle units: float (cos, sin) of
+// -2 pi u / 64, u = 0 .. 31 (two u per unit, rounded once from float64)
 DFT_DEV void dft_matrix_unit(int which, int unit, int P, int Q, const double* twP, const double* twQ, u32x4* out) {
   const int V = Q / 2 + 1;
   const bool r2 = which == 1 && dft_radix2(P);
@@ -500,6 +514,12 @@ DFT_DEV void dft_matrix_unit(int which, int unit, int P, int Q, const double* tw
     if (which == 0) {                  // FqT: k = w, col = 2 v + ri
       const int v = col >> 1, ri = col & 1;
       if (k < Q && v < V) x = twQ[2 * (int)(((long long)v * k) % Q) + ri] * 16384.0;
+    } else if (r2) {                   // Fp2 of the 64-row transform: cos | sin rows, k permuted to the accumulator order
+      const int h = 8 * (2 * (kidx >> 1) + (t >> 2)) + 4 * (kidx & 1) + (t & 3), u = col & 31;
+      if (kidx < 4) {                  // P = Pp = 32 here: units [kidx = 2 a + half-wave][hi|lo][64 rows], the rest of the block zero
+        const int a = (int)(((long long)u * h) % P) * tws;
+        x = (col < 32 ? twP[2 * a] : -twP[2 * a + 1]) * 16384.0;       // cos, sin of +2 pi u h / 32
+      }
     } else if (which == 1) {           // Fp2: k = ri * Pp + h, col (row of the product) = 2 u + ro
       const int ri = k / Pp, h = k - ri * Pp, u = col >> 1, ro = col & 1;
       if (h < P && u < P && ri < 2) {
@@ -576,14 +596,14 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
   const int mt1n = Mx / 32, nt1n = N1 / 32, nt2n = N2 / 32, mt2n = pl.M2 / 32;
   const int ks1n = Wk / 16, ks2n = 2 * Pp / 16;
   const int mt2 = wv & 3;
-  // R2: the wave's block is the parity mt2 >> 1, its fragments the 4 k-steps of row tile mt2 & 1 of the 64 x 64 matrix
+  // R2: every wave holds the whole 64 x 32 matrix - fragment 2 rt + a = row tile rt (cosines | sines), k-step a
   constexpr int KR2 = R2 ? 4 : KS2 ? KS2 : DFT_KREG;      // KS2 > 0: exactly the k-steps of step 2 (ks2n == KS2)
   half8 fp2h[KR2], fp2l[KR2];
   if (R2) {
 #pragma unroll
-    for (int ks = 0; ks < KR2; ++ks) {
-      fp2h[ks] = dft_frag(Fp2 + ((size_t)((2 * ks + hw) * 2 + 0)) * 64 + (mt2 & 1) * 32 + l31);
-      fp2l[ks] = dft_frag(Fp2 + ((size_t)((2 * ks + hw) * 2 + 1)) * 64 + (mt2 & 1) * 32 + l31);
+    for (int f = 0; f < KR2; ++f) {
+      fp2h[f] = dft_frag(Fp2 + ((size_t)((2 * (f & 1) + hw) * 2 + 0)) * 64 + (f >> 1) * 32 + l31);
+      fp2l[f] = dft_frag(Fp2 + ((size_t)((2 * (f & 1) + hw) * 2 + 1)) * 64 + (f >> 1) * 32 + l31);
     }
   } else if (!ALDS) {
 #pragma unroll
@@ -741,106 +761,160 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
       for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
     }
     dft_product_lds_any<NW, DFT_PIPE_LDS ? 2 : 0>(acc, nt1w, 0, ks1n, ldsU, MxS, ldsF, N1, wv, mt1n, l31, hw);
-    DFT_BARRIER();      // every wave is done reading x: the region becomes R2
+    DFT_BARRIER();      // every wave is done reading x: the region becomes R2 (64 rows: the staging buffer of X)
     DFT_STAMP(1)
 
-    // ---- R: R * 2^8 as units [k = (ri * Pp + h) / 8][hi|lo][n2 = img * V + v]; this lane owns column n = 2 v + ri of its
-    // tiles and, per accumulator run, 4 consecutive h of one image: half a unit
+    if constexpr (R2) {
+      // ---- chain (64 rows): step 1's rows go to step 2 in registers.  Row tile wv of step 1 is one (image, row parity) block -
+      // 32 rows h' by all 96 columns n = (v, re|im) - and the 32-point transform of that block has exactly those h' as its K:
+      //   CR | SR [(cos | sin, u)][n] = Fp2[(cos | sin, u)][h'] . R[h'][n]       two row tiles x three column tiles x two k-steps
+      // An accumulator holds column lane & 31 and rows 8 q + 4 (lane >> 5) + e; a B fragment wants column lane & 31 and 8
+      // consecutive k of its half-wave: runs q = 2 a, 2 a + 1 of a lane ARE the fragment of k-step a once Fp2's k order is
+      // h' = 8 (2 a + t / 4) + 4 (lane >> 5) + t % 4 (dft_matrix_unit).  No LDS round trip of R, no barrier up to the staging.
+      const int img = wv >> 1, par = wv & 1;
+      half8 bh[3][2], bl[3][2];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      if (tm[j] < 0) continue;
-      const int n = tn[j] * 32 + l31, v = n >> 1, ri = n & 1;
+      for (int j = 0; j < 3; ++j) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        // rows tm * 32 + 8 q (+ 4 for the upper half-wave): Pp is a multiple of 8, so both half-waves are in the same image -
-        // the division is wave-uniform (scalar unit, by multiplication)
-        const int mb = tm[j] * 32 + 8 * q;
-        const int img = dft_div(mb, pl.inv_pp), h0 = mb - img * Pp + 4 * hw;
-        if (v < V && img < G) {
-          u32x2 hi, lo;
+        for (int a = 0; a < 2; ++a) {
           const float sc = 1.0f / 2097152.0f;      // 2^-21 = 2^8 / (2^15 * 2^14)
-          dft_split4(acc[j][4 * q] * sc, acc[j][4 * q + 1] * sc, acc[j][4 * q + 2] * sc, acc[j][4 * q + 3] * sc, &hi, &lo);
-          // R2: h0 counts the parity-major rows of the W phase: k = parity * 64 + ri * 32 + h / 2
-          const int kg = R2 ? (h0 >> 5) * 8 + ri * 4 + ((h0 & 31) >> 3) : ri * (Pp / 8) + (h0 >> 3);
-          unsigned char* dst = ldsUb + ((size_t)(kg * 2) * N2S + img * V + v) * 16 + (h0 & 4) * 2;
-          *reinterpret_cast<u32x2*>(dst) = hi;
-          *reinterpret_cast<u32x2*>(dst + (size_t)N2S * 16) = lo;
+          u32x2 h0, l0, h1, l1;
+          dft_split4(acc[j][8 * a] * sc, acc[j][8 * a + 1] * sc, acc[j][8 * a + 2] * sc, acc[j][8 * a + 3] * sc, &h0, &l0);
+          dft_split4(acc[j][8 * a + 4] * sc, acc[j][8 * a + 5] * sc, acc[j][8 * a + 6] * sc, acc[j][8 * a + 7] * sc, &h1, &l1);
+          bh[j][a] = __builtin_bit_cast(half8, u32x4{h0[0], h0[1], h1[0], h1[1]});
+          bl[j][a] = __builtin_bit_cast(half8, u32x4{l0[0], l0[1], l1[0], l1[1]});
         }
       }
-    }
-    DFT_BARRIER();
-    DFT_STAMP(2)
-
-    // ---- step 2: X = Fp2 . R2 (Fp2 fragments in registers); this wave's column tiles (wv >> 2) + 2 j of row tile wv & 3
-    // (ALDS: tiles t = wv + NW j of the mt2n x nt2n grid, row tile fastest - as dft_product_lds counts them)
-    f32x16 xc[3];
-    int un[3], um[3];      // column / row tile of accumulator j, -1: none
-    int nt2w = 0;
+      // the next window's burst, unconditional and in front of the product (see the dense path below): the accumulators of step 1
+      // are dead, their registers take the window
+      const int itn = it + DFT_GRID < iters ? it + DFT_GRID : it;
+      DFT_FWD_PREFETCH_SLOTS(itn, tl, 0, NSLOT)
+      // E | O [u] = (CR_re + SR_im) + i (CR_im - SR_re): the lane of column (v, re) and its neighbour (v, im) swap their SR - the
+      // im lane takes it negated - and hold Re | Im of 16 u each; 2^-22 = 1 / (2^8 * 2^14) rides on the two operands (exact).
+      // One column tile at a time: two accumulators live.  E (even rows) is staged at u, O at 32 + u, as the butterfly reads them,
+      // in the layout of the XS phase below - a lane writes the 4-byte Re or Im of its 16 u.
+      const int XS = P * 8 * G + 16;
+      const float sc2 = 1.0f / 4194304.0f, sg = (l31 & 1) ? -sc2 : sc2;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int t = wv + NW * j;
-      const int nt = ALDS ? t / mt2n : (wv >> 2) + (NW / 4) * j;
-      const bool mine = ALDS ? t < mt2n * nt2n : (nt < nt2n && mt2 < mt2n);
-      un[j] = mine ? nt : -1;
-      um[j] = ALDS ? t - nt * mt2n : mt2;
-      nt2w += mine ? 1 : 0;
+      for (int j = 0; j < 3; ++j) {
+        f32x16 cr, sr;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) xc[j][r] = 0.f;
-    }
-    // the next window's loads are issued here - the accumulators of step 1 are dead, the values are needed a whole step 2 +
-    // store phase later - so that their registers do not overlap the first product's
-    // UNCONDITIONAL (round 5): the last iteration of a work-group requests its own window once more (cache hits, discarded).
-    // Behind "if (it + DFT_GRID < iters)" the prefetch registers stayed live through the whole iteration on the path that skips
-    // the loads - 60 registers the compiler had to keep next to the 64 of Fp2 in every phase - and the wait-count pass, merging
-    // the two paths, could not count what is in flight.  One burst of NSLOT x (G + 1) requests, in front of the product
-    // or right behind it (DFT_FWD_PREFETCH_AFTER).
-    const int itn = it + DFT_GRID < iters ? it + DFT_GRID : it;
-    {
-      if (ALDS) {
-        dft_product_lds_any<NW, DFT_PIPE_LDS ? 2 : 0>(xc, nt2w, 0, ks2n, ldsP, pl.M2, ldsU, N2S, wv, mt2n, l31, hw);
-        DFT_FWD_PREFETCH_SLOTS(itn, tl, 0, NSLOT)
-      } else if (!R2 && (DFT_FWD_PREFETCH_AFTER == 1 || (DFT_FWD_PREFETCH_AFTER == 2 && KS2 > 0 && KS2 <= 6))) {      // the burst behind the product
-        dft_product_rega_any<KS2>(xc, nt2w, fp2h, fp2l, ks2n, ldsU, N2S, wv >> 2, NW / 4, l31, hw);
-        DFT_FWD_PREFETCH_SLOTS(itn, tl, 0, NSLOT)
-      } else if (R2) {      // E | O = F32 . R2[this wave's parity block: 8 k groups of 2 N2S units]
-        DFT_FWD_PREFETCH_SLOTS(itn, tl, 0, NSLOT)
-        dft_product_rega_any<4>(xc, nt2w, fp2h, fp2l, 4, ldsU + (size_t)(mt2 >> 1) * 16 * N2S, N2S, wv >> 2, NW / 4, l31, hw);
-      } else {
-        DFT_FWD_PREFETCH_SLOTS(itn, tl, 0, NSLOT)
-        dft_product_rega_any<KS2>(xc, nt2w, fp2h, fp2l, ks2n, ldsU, N2S, wv >> 2, NW / 4, l31, hw);
-      }
-    }
-    DFT_BARRIER();      // every wave is done reading R2: the region becomes the staging buffer of X
-    DFT_STAMP(3)
-
-    // ---- XS: X = acc * 2^-22 staged as [v][u / 4][img][u % 4][re|im] (+16 bytes per v: consecutive lanes = consecutive v land
-    // in different banks); a lane owns (img, v) and per accumulator run two consecutive u
-    const int XS = P * 8 * G + 16;
+        for (int r = 0; r < 16; ++r) cr[r] = sr[r] = 0.f;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      if (un[j] < 0) continue;
-      const int n2 = un[j] * 32 + l31;
-      const int img = dft_div(n2, pl.inv_v), v = n2 - img * V;
+        for (int a = 0; a < 2; ++a) {
+          cr = dft_mma3(fp2h[a], fp2l[a], bh[j][a], bl[j][a], cr);
+          sr = dft_mma3(fp2h[2 + a], fp2l[2 + a], bh[j][a], bl[j][a], sr);
+        }
+        float z[16];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        // R2: row tiles 0, 1 are E[u], u < 32, staged at u; row tiles 2, 3 are O[u], staged at 32 + u
-        const int u0 = (um[j] * 32 + 8 * q + 4 * hw) >> 1;
-        if (img < G && u0 < P) {
-          const float sc = 1.0f / 4194304.0f;      // 2^-22 = 1 / (2^8 * 2^14)
-          f32x4 o;
-          o[0] = xc[j][4 * q] * sc;
-          o[1] = xc[j][4 * q + 1] * sc;
-          o[2] = xc[j][4 * q + 2] * sc;
-          o[3] = xc[j][4 * q + 3] * sc;
-          *reinterpret_cast<f32x4*>(ldsUb + (size_t)v * XS + (u0 >> 2) * (G * 32) + img * 32 + (u0 & 3) * 8) = o;
+        for (int r = 0; r < 16; ++r) {
+          z[r] = cr[r] * sc2 + DFT_SWAP1(sr[r]) * sg;
+          DFT_LANDED(z[r]);      // formed HERE, next to the swap (one multiply with a DPP operand), not sunk behind the branch below
+        }
+        const int n = j * 32 + l31, v = n >> 1;
+        if (v < V) {
+          unsigned char* dst = ldsUb + (size_t)v * XS + (par * (DFT_R2_P / 8) + hw) * (G * 32) + img * 32 + (n & 1) * 4;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) *reinterpret_cast<float*>(dst + (r >> 2) * (2 * G * 32) + (r & 3) * 8) = z[r];
         }
       }
+      DFT_BARRIER();
+      DFT_STAMP(3)      // (the diagnostic build: the whole chain is phase 3, phases 2 and 4 stay zero)
+    } else {
+      // ---- R: R * 2^8 as units [k = (ri * Pp + h) / 8][hi|lo][n2 = img * V + v]; this lane owns column n = 2 v + ri of its
+      // tiles and, per accumulator run, 4 consecutive h of one image: half a unit
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        if (tm[j] < 0) continue;
+        const int n = tn[j] * 32 + l31, v = n >> 1, ri = n & 1;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          // rows tm * 32 + 8 q (+ 4 for the upper half-wave): Pp is a multiple of 8, so both half-waves are in the same image -
+          // the division is wave-uniform (scalar unit, by multiplication)
+          const int mb = tm[j] * 32 + 8 * q;
+          const int img = dft_div(mb, pl.inv_pp), h0 = mb - img * Pp + 4 * hw;
+          if (v < V && img < G) {
+            u32x2 hi, lo;
+            const float sc = 1.0f / 2097152.0f;      // 2^-21 = 2^8 / (2^15 * 2^14)
+            dft_split4(acc[j][4 * q] * sc, acc[j][4 * q + 1] * sc, acc[j][4 * q + 2] * sc, acc[j][4 * q + 3] * sc, &hi, &lo);
+            const int kg = ri * (Pp / 8) + (h0 >> 3);
+            unsigned char* dst = ldsUb + ((size_t)(kg * 2) * N2S + img * V + v) * 16 + (h0 & 4) * 2;
+            *reinterpret_cast<u32x2*>(dst) = hi;
+            *reinterpret_cast<u32x2*>(dst + (size_t)N2S * 16) = lo;
+          }
+        }
+      }
+      DFT_BARRIER();
+      DFT_STAMP(2)
+
+      // ---- step 2: X = Fp2 . R2 (Fp2 fragments in registers); this wave's column tiles (wv >> 2) + 2 j of row tile wv & 3
+      // (ALDS: tiles t = wv + NW j of the mt2n x nt2n grid, row tile fastest - as dft_product_lds counts them)
+      f32x16 xc[3];
+      int un[3], um[3];      // column / row tile of accumulator j, -1: none
+      int nt2w = 0;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const int t = wv + NW * j;
+        const int nt = ALDS ? t / mt2n : (wv >> 2) + (NW / 4) * j;
+        const bool mine = ALDS ? t < mt2n * nt2n : (nt < nt2n && mt2 < mt2n);
+        un[j] = mine ? nt : -1;
+        um[j] = ALDS ? t - nt * mt2n : mt2;
+        nt2w += mine ? 1 : 0;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) xc[j][r] = 0.f;
+      }
+      // the next window's loads are issued here - the accumulators of step 1 are dead, the values are needed a whole step 2 +
+      // store phase later - so that their registers do not overlap the first product's
+      // UNCONDITIONAL (round 5): the last iteration of a work-group requests its own window once more (cache hits, discarded).
+      // Behind "if (it + DFT_GRID < iters)" the prefetch registers stayed live through the whole iteration on the path that skips
+      // the loads - 60 registers the compiler had to keep next to the 64 of Fp2 in every phase - and the wait-count pass, merging
+      // the two paths, could not count what is in flight.  One burst of NSLOT x (G + 1) requests, in front of the product
+      // or right behind it (DFT_FWD_PREFETCH_AFTER).
+      const int itn = it + DFT_GRID < iters ? it + DFT_GRID : it;
+      {
+        if (ALDS) {
+          dft_product_lds_any<NW, DFT_PIPE_LDS ? 2 : 0>(xc, nt2w, 0, ks2n, ldsP, pl.M2, ldsU, N2S, wv, mt2n, l31, hw);
+          DFT_FWD_PREFETCH_SLOTS(itn, tl, 0, NSLOT)
+        } else if (DFT_FWD_PREFETCH_AFTER == 1 || (DFT_FWD_PREFETCH_AFTER == 2 && KS2 > 0 && KS2 <= 6)) {      // the burst behind the product
+          dft_product_rega_any<KS2>(xc, nt2w, fp2h, fp2l, ks2n, ldsU, N2S, wv >> 2, NW / 4, l31, hw);
+          DFT_FWD_PREFETCH_SLOTS(itn, tl, 0, NSLOT)
+        } else {
+          DFT_FWD_PREFETCH_SLOTS(itn, tl, 0, NSLOT)
+          dft_product_rega_any<KS2>(xc, nt2w, fp2h, fp2l, ks2n, ldsU, N2S, wv >> 2, NW / 4, l31, hw);
+        }
+      }
+      DFT_BARRIER();      // every wave is done reading R2: the region becomes the staging buffer of X
+      DFT_STAMP(3)
+
+      // ---- XS: X = acc * 2^-22 staged as [v][u / 4][img][u % 4][re|im] (+16 bytes per v: consecutive lanes = consecutive v land
+      // in different banks); a lane owns (img, v) and per accumulator run two consecutive u
+      const int XS = P * 8 * G + 16;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        if (un[j] < 0) continue;
+        const int n2 = un[j] * 32 + l31;
+        const int img = dft_div(n2, pl.inv_v), v = n2 - img * V;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int u0 = (um[j] * 32 + 8 * q + 4 * hw) >> 1;
+          if (img < G && u0 < P) {
+            const float sc = 1.0f / 4194304.0f;      // 2^-22 = 1 / (2^8 * 2^14)
+            f32x4 o;
+            o[0] = xc[j][4 * q] * sc;
+            o[1] = xc[j][4 * q + 1] * sc;
+            o[2] = xc[j][4 * q + 2] * sc;
+            o[3] = xc[j][4 * q + 3] * sc;
+            *reinterpret_cast<f32x4*>(ldsUb + (size_t)v * XS + (u0 >> 2) * (G * 32) + img * 32 + (u0 & 3) * 8) = o;
+          }
+        }
+      }
+      DFT_BARRIER();
+      DFT_STAMP(4)
     }
-    DFT_BARRIER();
-    DFT_STAMP(4)
 
     // ---- ST: 16-byte pieces, 8 per quad of bins = the 128 contiguous bytes of the 4 channels; then the padding bins
     {
+      const int XS = P * 8 * G + 16;      // the staging pitch of both paths above
       const int per_v = (P / 4) * (G * 2), npieces = V * per_v;
       size_t qstride;                                            // floats between consecutive quads of bins
       float* dstbase = X + dft_spectra_pair0(pr_, NBT, pl.NBINS / 4, Cpad, &qstride) + (size_t)c0_ * 8;

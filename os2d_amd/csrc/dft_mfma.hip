@@ -21,6 +21,8 @@ extern __shared__ __attribute__((aligned(16))) unsigned char os2d_dft_smem[];
 #define DFT_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
 #define DFT_SHFL_XOR(v, m) __shfl_xor(v, m, 64)
 #define DFT_SHFL_XOR_U32(v, m) ((unsigned)__shfl_xor((int)(v), m, 64))
+// lane ^ 1 within every quad: quad_perm [1, 0, 3, 2], all rows and banks
+#define DFT_SWAP1(v) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (float)(v)), 0xB1, 0xF, 0xF, true))
 #define DFT_BALLOT(p) __builtin_amdgcn_ballot_w64(p)
 #define DFT_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
 #define DFT_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -32,7 +34,8 @@ extern __shared__ __attribute__((aligned(16))) unsigned char os2d_dft_smem[];
 #define DFT_RAISE(f) os2d_raise(f)
 #ifdef OS2D_DIAG_DFT_STAMPS
 // diagnostic build: thread 0 of every work-group accumulates the wall-clock ticks (100 MHz) between the phase barriers; the sums
-// over all work-groups land in os2d_dft_stamps[0..5] (forward: W | step 1 | R | step 2 | XS | ST) and [8..13] (inverse: max |
+// over all work-groups land in os2d_dft_stamps[0..5] (forward: W | step 1 | R | step 2 | XS | ST; the 64-row kernel has no R and XS
+// phase - its convert + step 2 + combine + stage is phase 3, indices 2 and 4 stay zero) and [8..13] (inverse: max |
 // WY | step A | WT | step B | epilogue), [6] / [14] count iterations.  Read with os2d_debug_dft_stamps (tools/time_dft_phases.py).
 __device__ unsigned long long os2d_dft_stamps[16];
 #define DFT_STAMP_BEGIN() unsigned long long st_acc_[6] = {0, 0, 0, 0, 0, 0}, st_n_ = 0, st_last_ = wall_clock64();
@@ -58,7 +61,8 @@ using namespace os2d_dft;
 // KS = k-steps of the product whose row operand lives in registers (step 2 / step A: 2 Pp / 16): a template parameter for the
 // canonical transform sizes (5 .. 8: straight-line products, exactly as many fragment registers as the size needs), 0 = any
 // size behind uniform guards ($OS2D_DFT_SIZES=exact).  KS = 8 is the 64-row transform and nothing else (dft_plan_transform): the
-// forward instantiations run the radix-2 form of step 2 - two half-size products of 4 k-steps and a butterfly (dft_mfma.h)
+// forward instantiations run the radix-2 form of step 2 - per wave the 32-point transform of its own step-1 rows, handed over in
+// registers (2 k-steps, a 64 x 32 real row operand), and a butterfly (dft_mfma.h)
 template <bool TILED, bool FAST, int G, int NW, int KS>
 __global__ __launch_bounds__(NW * 64, 8 / NW) void dft_forward_kernel(const float* __restrict__ corr, const float* __restrict__ invn,
                                                                       float* __restrict__ X, const u32x4* __restrict__ FqT,

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """NEEDS A DIAGNOSTIC BUILD: python -m os2d_amd.build --variant stamps -DOS2D_DIAG_DFT_STAMPS, run with
 OS2D_HIP_LIB=tools/diag_libs/stamps/libos2d_hip.so.  Phase breakdown of the matrix-product transforms (dft_mfma.h): wall-clock
-ticks of thread 0 of every work-group between the phase barriers, averaged per iteration (4 images).
+ticks of thread 0 of every work-group between the phase barriers, averaged per iteration (4 images).  The 64-row forward kernel has
+no R and XS phase of its own: its convert + step 2 + combine + stage is booked under "step 2", the other two read 0.00.
     python tools/time_dft_phases.py [pairs=64] [H=60] [W=80]"""
 import ctypes
 import os
