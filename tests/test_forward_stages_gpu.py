@@ -1,7 +1,8 @@
 """GPU: the small forward entry points of libos2d_hip.so (include/os2d_hip.h) on their own, called through os2d_amd/_lib.py with
 tensors built on the host, against the float64 model of the same stage (tests/forward_model.py).  The head tests reach these
 kernels only through ``Os2dHead.forward``, at the fixtures' shapes and under end-to-end tolerances; the matrix kernels have
-stage tests of their own (correlation, convolutions, transforms, per-bin GEMM).  Counterpart of
+stage tests of their own (correlation and the inference convolutions: tests/test_forward_matrix_gpu.py; transforms and per-bin
+GEMM: tests/test_dft_*_gpu.py, tests/test_spectral*_gpu.py).  Counterpart of
 tests/test_backward_stages_gpu.py, with its rules:
 
   * an output the header calls "written" is pre-filled with NaN (0xFF bytes for byte buffers: NaN as fp16 too);

@@ -823,9 +823,10 @@ def test_correlation_stage_matches_reference(name, device):
     plane = lib.os2d_plane_floats(H, W)
     Ws, base = plane_interior(H, W)
     # ---- fp32 kernels
-    sumsq = torch.empty(A * HW, device=device)
-    corr = torch.empty(NB, 225, HW, device=device)
-    rnorm = torch.empty(NB * 226 * plane, device=device)
+    # (outputs and workspaces pre-filled with NaN / 0xFF bytes: an unwritten cell cannot pass as a zero)
+    sumsq = torch.full((A * HW,), float("nan"), device=device)
+    corr = torch.full((NB, 225, HW), float("nan"), device=device)
+    rnorm = torch.full((NB * 226 * plane,), float("nan"), device=device)
     _lib.check(lib.os2d_fm_sumsq(_lib.ptr(fm), _lib.ptr(sumsq), A, C, H, W, st), "os2d_fm_sumsq")
     _lib.check(lib.os2d_corr(_lib.ptr(fm), _lib.ptr(head._qp), _lib.ptr(sumsq), _lib.ptr(corr), _lib.ptr(rnorm), A, B, C, H, W, st), "os2d_corr")
     assert util.maxdiff(corr, ref) < 2e-6
@@ -833,10 +834,10 @@ def test_correlation_stage_matches_reference(name, device):
     assert util.maxdiff(got, rn_ref) < 2e-6
     # ---- split-fp16 kernels
     nbytes = lib.os2d_corr_f16x3_workspace_bytes(A, C, H, W)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device=device)
     corr16 = torch.full((NB, 225, HW), float("nan"), device=device)
     shb_bytes = lib.os2d_shb_bytes(225, H, W)
-    rshb = torch.empty(NB * shb_bytes, dtype=torch.uint8, device=device)
+    rshb = torch.full((NB * shb_bytes,), 0xFF, dtype=torch.uint8, device=device)
     _lib.check(lib.os2d_corr_f16x3(_lib.ptr(fm), _lib.ptr(head._split_class_operand()), _lib.ptr(corr16), _lib.ptr(rshb), A, B, C, H, W,
                                    _lib.ptr(ws), ws.numel(), st), "os2d_corr_f16x3")
     assert util.maxdiff(corr16, ref) < 2e-6
@@ -880,9 +881,9 @@ def test_packed_correlation_stage_matches_reference(name, device):
     inv_ref = 1.0 / (torch.relu(fx["ref_corr"].double()).reshape(NB, 225, HW).norm(dim=1) + 1e-6)
     assert float(((invn.double().cpu() - inv_ref).abs() / inv_ref).max()) < 3e-6
     # the padded kernel: same correlation bits
-    ws = torch.empty(lib.os2d_corr_f16x3_workspace_bytes(A, C, H, W), dtype=torch.uint8, device=device)
-    corr16 = torch.empty(NB, 225, HW, device=device)
-    rshb = torch.empty(NB * lib.os2d_shb_bytes(225, H, W), dtype=torch.uint8, device=device)
+    ws = torch.full((lib.os2d_corr_f16x3_workspace_bytes(A, C, H, W),), 0xFF, dtype=torch.uint8, device=device)
+    corr16 = torch.full((NB, 225, HW), float("nan"), device=device)
+    rshb = torch.full((NB * lib.os2d_shb_bytes(225, H, W),), 0xFF, dtype=torch.uint8, device=device)
     _lib.check(lib.os2d_corr_f16x3(_lib.ptr(fm), _lib.ptr(head._split_class_operand()), _lib.ptr(corr16), _lib.ptr(rshb), A, B, C, H, W,
                                    _lib.ptr(ws), ws.numel(), _lib.current_stream(device)), "os2d_corr_f16x3")
     assert torch.equal(corr, corr16)
