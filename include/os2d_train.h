@@ -217,7 +217,9 @@ int os2d_train_assign_targets(int mode, const float* gt_boxes, const int* gt_lab
  * cls_targets for the class loss, not for the localisation loss; cls_preds_for_neg (NULL = none) replaces cls_preds at negatives.
  * Outputs: losses [5] = loss, loc_smoothL1, cls, cls_pos, cls_neg; cls_loss [N] the per-element class loss; loc_loss [N] the
  * per-element localisation loss (NULL = not written); flags [N] bytes (1 positive, 2 negative used, 4 regression positive,
- * 8 candidate) and coef [N] (d class loss / d score before the count normalisation) for the backward.  The counts
+ * 8 candidate, 16 the element's hinge is active for the gradient: margin_pos - score >= 0 at a positive, score - margin >= 0 at
+ * a candidate - torch's clamp(min=0) passes the gradient at 0 too, so a score exactly at its margin has the RLL coefficient of the
+ * active side) and coef [N] (d class loss / d score before the count normalisation) for the backward.  The counts
  * (a zero count divides as 1) stay in `workspace`, os2d_train_objective_workspace_floats floats, which the backward reads.   */
 size_t os2d_train_objective_workspace_floats(int A, int B, int HW);
 int os2d_train_objective_forward(int class_loss, int patch_mining_mode, const float* loc_preds, const float* loc_targets,

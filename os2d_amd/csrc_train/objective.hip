@@ -32,6 +32,7 @@ constexpr unsigned char F_POS = 1;      // positive of the class loss (remapped 
 constexpr unsigned char F_NEG = 2;      // negative that enters the class loss (after mining)
 constexpr unsigned char F_POSREG = 4;   // positive of the localisation loss (original targets)
 constexpr unsigned char F_CAND = 8;     // neither positive nor ignored: candidate negative
+constexpr unsigned char F_HINGE = 16;   // the argument of the element's own clamp is >= 0: where torch's clamp passes the gradient
 
 // workspace layout, in 4-byte words
 constexpr int W_CNT = 0;      // unsigned counters: 0 num_pos, 1 num_pos_for_regression, 2 non-trivial positives, 3 candidates
@@ -300,6 +301,9 @@ __global__ __launch_bounds__(OBJ_THREADS) void objective_elements_kernel(ObjPara
     if (cls_preds_for_neg) x = pos ? x : (cand ? cls_preds_for_neg[i] : 0.f);
     const float lneg = cand ? 0.5f * fmaxf(x - P.margin, 0.f) : 0.f;
     const float lpos = pos ? 0.5f * fmaxf(P.margin_pos - x, 0.f) : 0.f;
+    // the reference's clamp(min=0) passes the gradient where its argument is exactly 0 as well: the RLL coefficients go by the
+    // argument (>= 0), the count of non-trivial positives by the loss (> 0), as objective.py has them
+    const bool hinge = pos ? P.margin_pos - x >= 0.f : (cand && x - P.margin >= 0.f);
     if (preg) {
       const size_t l0 = ((size_t)ab * 4) * P.HW + p;
       float s = smooth_l1(loc_preds[l0], loc_targets[l0]);
@@ -309,7 +313,7 @@ __global__ __launch_bounds__(OBJ_THREADS) void objective_elements_kernel(ObjPara
       locv = s;
     }
     if (loc_loss) loc_loss[i] = locv;
-    unsigned char f = (pos ? F_POS : 0) | (preg ? F_POSREG : 0) | (cand ? F_CAND : 0);
+    unsigned char f = (pos ? F_POS : 0) | (preg ? F_POSREG : 0) | (cand ? F_CAND : 0) | (hinge ? F_HINGE : 0);
     npos = pos;
     nreg = preg;
     ncand = cand;
@@ -325,7 +329,7 @@ __global__ __launch_bounds__(OBJ_THREADS) void objective_elements_kernel(ObjPara
         c = pos ? -lpos : lneg;
       } else {
         cl = lneg + lpos;
-        c = pos ? (lpos > 0.f ? -0.5f : 0.f) : (lneg > 0.f ? 0.5f : 0.f);
+        c = hinge ? (pos ? -0.5f : 0.5f) : 0.f;
       }
       cls_loss[i] = cl;
       coef[i] = c;
@@ -541,7 +545,7 @@ __global__ __launch_bounds__(OBJ_THREADS) void rll_elements_kernel(ObjParams P, 
     const float lp = lpos * pos_scale;
     const float cl = (cand ? ln : 0.f) + (pos ? lp : 0.f);
     cls_loss[i] = cl;
-    coef[i] = pos ? (lpos > 0.f ? -0.5f * pos_scale : 0.f) : (wm ? 0.5f * w : 0.f);
+    coef[i] = pos ? ((f & F_HINGE) ? -0.5f * pos_scale : 0.f) : (wm ? 0.5f * w : 0.f);
     if (cand && take_negs) {
       f |= F_NEG;
       negv = cl;

@@ -21,6 +21,7 @@ from .. import _train_lib
 
 CLASS_LOSSES = {"contrastiveloss": 0, "rll": 1}
 F_POS, F_NEG, F_POSREG = 1, 2, 4        # bits of the per-element flags (include/os2d_train.h)
+F_CAND, F_HINGE = 8, 16                 # candidate negative; hinge active for the gradient (clamp argument >= 0)
 
 
 class _ObjectiveFunction(torch.autograd.Function):
