@@ -12,11 +12,12 @@
  * negative on error (-1 bad argument, -2 workspace too small, -3 unsupported shape, -4 HIP runtime error), described by
  * os2d_train_last_error() on the calling thread.  Arguments are checked before anything is launched.
  *
- * Arithmetic: fp32 throughout, unless a caller asks the *_ex entry points for the split-fp16 GEMMs.  The matrix-shaped work (the transposed convolutions, the weight gradients, the two
- * correlation GEMMs) runs on v_mfma_f32_16x16x4_f32.  Weight gradients reduce over NB * PLANE positions in split-K partial
- * sums that a second kernel adds in a fixed order: deterministic.  The resampling backward scatters into d corr with fp32
- * atomicAdd: the order of those additions is not fixed (as in torch's own grid_sample backward), unless the caller takes
- * os2d_train_decode_backward_det, which adds 64-bit integers on a fixed-point grid instead.                               */
+ * Arithmetic: fp32 throughout, unless a caller asks the *_ex entry points for the split-fp16 GEMMs.  The matrix-shaped work
+ * (the transposed convolutions, the weight gradients, the two correlation GEMMs) runs on v_mfma_f32_16x16x4_f32.  Weight
+ * gradients reduce over NB * PLANE positions in split-K partial sums that a second kernel adds in a fixed order:
+ * deterministic.  The resampling backward scatters into d corr with fp32 atomicAdd: the order of those additions is not
+ * fixed (as in torch's own grid_sample backward), unless the caller takes os2d_train_decode_backward_det, which adds 64-bit
+ * integers on a fixed-point grid instead.                                                                                  */
 #ifndef OS2D_TRAIN_H
 #define OS2D_TRAIN_H
 

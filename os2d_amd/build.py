@@ -54,11 +54,13 @@ HIP = Library("libos2d_hip.so", CSRC, SOURCES, FLAGS, {s: PACKED_OFF for s in NO
 # objective.hip restates the reference's IoU and box encoding operation for operation: a fused multiply-add would round
 # differently from the CPU reference
 TRAIN_CSRC = os.path.join(HERE, "csrc_train")
-# gemm_f16x3.hip: the backward GEMMs in split-fp16 arithmetic (the *_ex entry points of train.hip at arith = 1).
+# train.hip: the C ABI of the backward pass and its per-location kernels
+# train_gemm.hip: the GEMMs in fp32 and in split-fp16 arithmetic and their five launch sites (the `arith` of the *_ex entry points)
+# decode_backward.hip: the resample / pool / box decode backward, float-atomic and order-independent
 # mining.hip needs no flag: every function of it that rounds (csrc/detect_common.h, mining_crop.h) switches contraction off itself
 # shb_planes.hip: the split-half blocked activations of an f16x3 training forward as the fp32 planes the backward reads
 # bn_live.hip: batch-statistics BatchNorm of the TransformNet (statistics, normalise + ReLU, backward through the statistics)
-TRAIN = Library("libos2d_train.so", TRAIN_CSRC, ["train.hip", "gemm_f16x3.hip", "objective.hip", "mining.hip", "shb_planes.hip", "bn_live.hip"],
+TRAIN = Library("libos2d_train.so", TRAIN_CSRC, ["train.hip", "train_gemm.hip", "decode_backward.hip", "objective.hip", "mining.hip", "shb_planes.hip", "bn_live.hip"],
                 FLAGS + PACKED_OFF,
                 {"objective.hip": ["-ffp-contract=off"]},
                 [TRAIN_CSRC, CSRC, SHARED], "os2d_train.h", "OS2D_TRAIN_LIB")

@@ -1,6 +1,6 @@
 // Batch-statistics ("live") BatchNorm of the TransformNet layers 1 (128 channels) and 2 (64) for the training forward and
 // backward (include/os2d_train.h): statistics, normalise + ReLU, and the backward through the statistics.  The raw
-// convolution that feeds them is os2d_train_conv_forward (train.hip: it runs on the GEMMs of the backward pass).
+// convolution that feeds them is os2d_train_conv_forward (train.hip: it runs on the GEMMs of the backward pass, train_gemm.hip).
 //
 // All four kernels are memory-bound passes over z [NB,C,PLANE]: 16-byte loads and stores along the plane (PLANE is a multiple
 // of 64 floats, every plane 16-byte aligned), pad cells told from data cells by index - what a pad cell holds is never used.
@@ -8,14 +8,14 @@
 // four waves of a work-group are added as (0 + 1) + (2 + 3), and the work-groups of a channel - one per slice of `per`
 // consecutive pairs - are combined in slice order.  Two runs on the same input give the same bits.
 #include "../../include/os2d_train.h"
-#include "../csrc/os2d_common.h"
+#include "train_common.h"    // layer_channels, shape_ok
+
+using namespace os2d_train;
 
 namespace {
 
 constexpr int MAX_SLICES = 32;     // work-groups per channel
 
-int layer_channels(int layer) { return layer == 1 ? 128 : layer == 2 ? 64 : 0; }
-bool shape_ok(int NB, int H, int W) { return NB >= 1 && H >= 1 && W >= 1 && W <= OS2D_MAX_W_DIRECT7 && H <= OS2D_MAX_H; }
 // pairs per slice, slices
 void slices(int NB, int* per, int* S) {
   *per = (NB + MAX_SLICES - 1) / MAX_SLICES;

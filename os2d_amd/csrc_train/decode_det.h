@@ -1,5 +1,5 @@
 // The fixed-point grid of the order-independent d corr scatter (os2d_train_decode_backward_det, include/os2d_train.h): one
-// rule, used by the host helper os2d_train_decode_det_exponent and by the scatter and convert kernels of train.hip.
+// rule, used by the host helper os2d_train_decode_det_exponent and by the scatter and convert kernels of decode_backward.hip.
 //
 // Per pair, m = the largest |dcls + dcls_det| over its locations (the fp32 sum the kernel forms), read from the pair's word
 // as an fp32 bit pattern.  An addend of the scatter is wsc * (a bilinear weight in [0, 1]) with |wsc| = |gsum| / 121 (one
@@ -51,5 +51,24 @@ OS2D_DET_HD inline int os2d_det_exponent(unsigned bits, int L) {
   }
   return 60 - L - fl;
 }
+
+// the workspace of the route (for a shape the rule accepts): the accumulator [NB,225,HW] of 64-bit sums, then the pair words
+inline size_t os2d_det_acc_bytes(int NB, int H, int W) { return (size_t)NB * 225 * H * W * sizeof(long long); }
+inline size_t os2d_det_workspace_bytes(int NB, int H, int W) {
+  return (os2d_det_acc_bytes(NB, H, W) + (size_t)NB * sizeof(unsigned) + 255) / 256 * 256;
+}
+
+#if defined(__HIPCC__)
+// ---- the launches of decode_backward.hip; the entry points of train.hip have checked the arguments.  The deterministic one
+// clears `workspace` (os2d_det_workspace_bytes), takes the maxima, scatters and converts.  Not exports of the library: hidden.
+#pragma GCC visibility push(hidden)
+int os2d_decode_backward_launch(const float* corr, const float* params, const float* dcls, const float* dcls_det, const float* dloc, int NB,
+                                int H, int W, int P, int inverse, int stride, int rec_field, float* dcorr, float* dparams,
+                                hipStream_t stream);
+int os2d_decode_backward_det_launch(const float* corr, const float* params, const float* dcls, const float* dcls_det, const float* dloc,
+                                    int NB, int H, int W, int P, int inverse, int stride, int rec_field, float* dcorr, float* dparams,
+                                    void* workspace, hipStream_t stream);
+#pragma GCC visibility pop
+#endif
 
 #endif

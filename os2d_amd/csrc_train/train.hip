@@ -1,116 +1,19 @@
-// libos2d_train.so (include/os2d_train.h): the backward pass of the OS2D head on gfx950, fp32 throughout (the *_ex entry points
-// take the GEMMs to the split-fp16 kernel of gemm_f16x3.hip at arith = 1).
-//
-// Matrix-shaped work goes through ONE tiled GEMM kernel on v_mfma_f32_16x16x4_f32 (gemm16_kernel): 64 x 64 output tile per
-// 256-thread work-group (4 waves, each 2 x 2 blocks of 16 x 16), k-steps of 16 staged in LDS.  Operands are read through small
-// loader functors, so the same kernel runs
-//   * the transposed convolutions (B = the output gradient read at the tap offsets of the zero-bordered plane layout),
-//   * the weight gradients (an implicit GEMM over K = NB * PLANE positions, split-K, partial sums added in a fixed order),
-//   * the two correlation GEMMs (d F^ = Q^T d corr per image, d Q^ = d corr F^T per class).
-//   * the forward convolution of a layer whose BatchNorm takes batch statistics (os2d_train_conv_forward: the data gradient's
-//     launch with the raw filters as the A operand and the bias added in the store; bn_live.hip has the BatchNorm itself).
-// The rest is per-location work: resample / pool / box decode backward, BatchNorm + ReLU masks, the two L2 normalisations
-// and the bilinear class-map resize.
+// libos2d_train.so (include/os2d_train.h): the C ABI of the backward pass of the OS2D head on gfx950 - check, size, launch - and
+// its per-location kernels: BatchNorm + ReLU masks, the two L2 normalisations, the bilinear class-map resize and the small
+// passes around the GEMMs.  The matrix-shaped work is train_gemm.hip's (fp32, or split-fp16 at arith = 1 of the *_ex entry
+// points), the resample / pool / box decode backward decode_backward.hip's.
 #include <stdio.h>
 
 #include "../../include/os2d_train.h"
 #include "../csrc/os2d_common.h"
-#include "../csrc/sample_decode.h"
-#include "train_gemm.h"     // the operand loaders and result stores of the GEMMs; the launchers of gemm_f16x3.hip
-#include "decode_det.h"     // the fixed-point grid of the order-independent d corr scatter
+#include "train_common.h"   // the layer table, shape_ok, blocks
+#include "train_gemm.h"     // the five GEMM sites and the layouts of their workspaces
+#include "decode_det.h"     // the fixed-point grid of the order-independent d corr scatter; the launches of decode_backward.hip
 
+using namespace os2d_train;
 using namespace os2d_train_gemm;
 
 namespace {
-
-struct Layer {
-  int cout, cin, ks;
-};
-bool layer_shape(int layer, int P, Layer* s) {
-  switch (layer) {
-    case 1: *s = {128, OS2D_K, 7}; return true;
-    case 2: *s = {64, 128, 5}; return true;
-    case 3:
-      if (P != 6 && P != 4) return false;
-      *s = {P, 64, 5};
-      return true;
-    default: return false;
-  }
-}
-// channel count of the forward buffer that feeds a layer: rnorm keeps 226 planes per pair (OS2D_KP)
-int input_planes(int layer) { return layer == 1 ? OS2D_KP : layer == 2 ? 128 : 64; }
-
-bool shape_ok(int NB, int H, int W) { return NB >= 1 && H >= 1 && W >= 1 && W <= OS2D_MAX_W_DIRECT7 && H <= OS2D_MAX_H; }
-
-// ------------------------------------------------------------------------------------------------ fp32-MFMA GEMM
-constexpr int GT = 64;   // output tile (M and N)
-constexpr int GK = 16;   // k-step staged in LDS
-
-// C(z)[m][n] = sum_{k in [kb, ke)} A(z, m, k) * B(z, k, n).  ksplit > 0: z is a split-K slice, [kb, ke) = [z*ksplit, ...);
-// ksplit == 0: z is a batch index and the whole K is reduced.  B_KFAST: B's fastest-varying address is k (else n).
-template <class LA, class LB, class ST, bool B_KFAST>
-__global__ __launch_bounds__(256) void gemm16_kernel(LA la, LB lb, ST st, int M, int N, int K, int ksplit) {
-  __shared__ float As[GK][GT + 4];
-  __shared__ float Bs[GK][GT + 4];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int wm = wv >> 1, wn = wv & 1;
-  const int m0 = blockIdx.y * GT, n0 = blockIdx.x * GT, z = blockIdx.z;
-  const int kb = ksplit > 0 ? z * ksplit : 0;
-  const int ke = ksplit > 0 ? min(K, kb + ksplit) : K;
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int k0 = kb; k0 < ke; k0 += GK) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int e = tid + r * 256;
-      const int kk = e & (GK - 1), mm = e >> 4;
-      const int m = m0 + mm, k = k0 + kk;
-      As[kk][mm] = (m < M && k < ke) ? la(z, m, k) : 0.f;
-      int bk, bn;
-      if (B_KFAST) {
-        bk = e & (GK - 1);
-        bn = e >> 4;
-      } else {
-        bn = e & (GT - 1);
-        bk = e >> 6;
-      }
-      const int n = n0 + bn, k2 = k0 + bk;
-      Bs[bk][bn] = (n < N && k2 < ke) ? lb(z, k2, n) : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < GK / 4; ++s) {
-      const int kr = s * 4 + (lane >> 4);
-      const float a0 = As[kr][wm * 32 + (lane & 15)], a1 = As[kr][wm * 32 + 16 + (lane & 15)];
-      const float b0 = Bs[kr][wn * 32 + (lane & 15)], b1 = Bs[kr][wn * 32 + 16 + (lane & 15)];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm * 32 + i * 16 + (lane >> 4) * 4 + r;   // C/D map of the 16x16 MFMA: row (lane>>4)*4+r, col lane&15
-        const int n = n0 + wn * 32 + j * 16 + (lane & 15);
-        if (m < M && n < N) st(z, m, n, acc[i][j][r]);
-      }
-}
-
-template <bool B_KFAST, class LA, class LB, class ST>
-int gemm(LA la, LB lb, ST st, int M, int N, int K, int Z, int ksplit, hipStream_t stream, const char* what) {
-  const dim3 grid((N + GT - 1) / GT, (M + GT - 1) / GT, Z);
-  hipLaunchKernelGGL((gemm16_kernel<LA, LB, ST, B_KFAST>), grid, dim3(256), 0, stream, la, lb, st, M, N, K, ksplit);
-  return os2d_launched(what);
-}
 
 // ------------------------------------------------------------------------------------------------ small kernels
 // Wt[c][o*T2 + t] = w[o][c][T2-1-t]: the filters of the transposed convolution
@@ -139,250 +42,6 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// ---- the order-independent d corr scatter (decode_det.h): where a pair's sums go and on which grid
-struct DetSink {
-  unsigned long long* acc;    // [NB,225,HW] fixed-point sums (two's complement: the wrap-around of unsigned addition is signed addition)
-  const unsigned* words;      // [NB] the largest |dcls + dcls_det| of each pair, fp32 bits
-  int L;                      // os2d_det_log2_addends(H, W)
-};
-__device__ __forceinline__ double det_pow2(int e) { return __longlong_as_double((long long)(1023 + e) << 52); }   // e in [-1022, 1023]
-// one addend onto the grid: the product is exact, the rounding to the nearest integer is the route's only one
-__device__ __forceinline__ void det_add(unsigned long long* cell, float a, double scale) {
-  const long long q = __double2ll_rn((double)a * scale);
-  if (q != 0) atomicAdd(cell, (unsigned long long)q);
-}
-
-// ---- (a) resample + pool + box decode backward: one thread per (pair, location).  DET = false adds the d corr taps into
-// dcorr with fp32 atomics (os2d_train_decode_backward); DET = true rounds the same fp32 addends onto the pair's fixed-point
-// grid and adds them into `sink` with 64-bit integer atomics (os2d_train_decode_backward_det: dcorr is not touched here).
-// Everything else - theta, the coordinates, the clamps, dparams - is the same code on both routes.
-template <bool DET>
-__global__ __launch_bounds__(256) void decode_backward_kernel(const float* __restrict__ corr, const float* __restrict__ params,
-                                                              const float* __restrict__ dcls, const float* __restrict__ dcls_det,
-                                                              const float* __restrict__ dloc, int H, int W, int P, int inverse,
-                                                              float stride, float half_box, float* __restrict__ dcorr,
-                                                              float* __restrict__ dparams, DetSink sink) {
-  const int HW = H * W;
-  const int nb = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= HW) return;
-  const int h = n / W, w = n - h * W;
-  const float* pp = params + (size_t)nb * P * HW + n;
-  float t00, t01, t02, t10, t11, t12;
-  os2d_theta(pp, HW, P, inverse, t00, t01, t02, t10, t11, t12);     // the forward's own theta
-  const size_t o = (size_t)nb * HW + n;
-  const float gcls = dcls ? dcls[o] : 0.f;
-  const float gsum = gcls + (dcls_det ? dcls_det[o] : 0.f);
-  constexpr int NTAP = POOL_HI - POOL_LO;
-  const float inv_pool = 1.0f / (NTAP * NTAP);
-  const float wsc = gsum * inv_pool, wth = gcls * inv_pool;
-  const float half_t = 0.5f * OS2D_T;
-  const float cx = (float)w + 0.5f, cy = (float)h + 0.5f;
-  const float wmax = (float)(W - 1), hmax = (float)(H - 1);
-  const float* cbase = corr + (size_t)nb * OS2D_K * HW;
-  float* dbase = DET ? nullptr : dcorr + (size_t)nb * OS2D_K * HW;
-  unsigned long long* abase = nullptr;
-  double scale = 0.0;
-  bool scatter = true;
-  if (DET) {                  // a zero maximum has nothing to add; a non-finite one is the convert pass's to report
-    const int e = os2d_det_exponent(sink.words[nb], sink.L);
-    scatter = e != OS2D_TRAIN_DET_ZERO && e != OS2D_TRAIN_DET_NONFINITE;
-    scale = det_pow2(scatter ? e : 0);
-    abase = sink.acc + (size_t)nb * OS2D_K * HW;
-  }
-  float d00 = 0.f, d01 = 0.f, d02 = 0.f, d10 = 0.f, d11 = 0.f, d12 = 0.f;
-  if (wsc != 0.f || wth != 0.f) {
-    for (int j = POOL_LO; j < POOL_HI; ++j) {
-      const float xj = os2d_template_coord(j);
-      for (int i = POOL_LO; i < POOL_HI; ++i) {
-        const float yi = os2d_template_coord(i);
-        const float gx = t00 * xj + t01 * yi + t02;
-        const float gy = t10 * xj + t11 * yi + t12;
-        const float Xr = gx * half_t + cx, Yr = gy * half_t + cy;
-        const float X = fminf(fmaxf(Xr, 0.f), wmax);
-        const float Y = fminf(fmaxf(Yr, 0.f), hmax);
-        const float fx0 = floorf(X), fy0 = floorf(Y);
-        const float ax = X - fx0, ay = Y - fy0;
-        const int x0 = (int)fx0, y0 = (int)fy0;
-        const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-        const size_t ch = (size_t)(j * OS2D_T + i) * HW;
-        if (wsc != 0.f) {       // d corr: the pool weight over the 4 taps of the point's own channel
-          const float a00 = wsc * (1.f - ax) * (1.f - ay), a01 = wsc * ax * (1.f - ay);
-          const float a10 = wsc * (1.f - ax) * ay, a11 = wsc * ax * ay;
-          if (DET) {
-            if (scatter) {
-              unsigned long long* d = abase + ch;
-              det_add(d + y0 * W + x0, a00, scale);
-              det_add(d + y0 * W + x1, a01, scale);
-              det_add(d + y1 * W + x0, a10, scale);
-              det_add(d + y1 * W + x1, a11, scale);
-            }
-          } else {
-            float* d = dbase + ch;
-            unsafeAtomicAdd(d + y0 * W + x0, a00);
-            unsafeAtomicAdd(d + y0 * W + x1, a01);
-            unsafeAtomicAdd(d + y1 * W + x0, a10);
-            unsafeAtomicAdd(d + y1 * W + x1, a11);
-          }
-        }
-        if (wth != 0.f) {       // d grid: derivative of the bilinear weights, zero where the coordinate was clamped
-          const float* c = cbase + ch;
-          const float v00 = c[y0 * W + x0], v01 = c[y0 * W + x1], v10 = c[y1 * W + x0], v11 = c[y1 * W + x1];
-          const float dX = (Xr >= 0.f && Xr <= wmax) ? (1.f - ay) * (v01 - v00) + ay * (v11 - v10) : 0.f;
-          const float dY = (Yr >= 0.f && Yr <= hmax) ? (1.f - ax) * (v10 - v00) + ax * (v11 - v01) : 0.f;
-          const float dgx = dX * half_t * wth, dgy = dY * half_t * wth;
-          d00 += dgx * xj;
-          d01 += dgx * yi;
-          d02 += dgx;
-          d10 += dgy * xj;
-          d11 += dgy * yi;
-          d12 += dgy;
-        }
-      }
-    }
-  }
-  if (dloc) {   // loc = encode(clip(min / max over the corners of the transformed template), anchor)
-    const float l0 = dloc[((size_t)nb * 4 + 0) * HW + n], l1 = dloc[((size_t)nb * 4 + 1) * HW + n];
-    const float l2 = dloc[((size_t)nb * 4 + 2) * HW + n], l3 = dloc[((size_t)nb * 4 + 3) * HW + n];
-    const float ecx = stride * cx, ecy = stride * cy;
-    float U[4], V[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float yi = (k & 2) ? 1.0f : -1.0f;
-      const float xj = (k & 1) ? 1.0f : -1.0f;
-      U[k] = (t00 * xj + t01 * yi + t02) * half_box + ecx;
-      V[k] = (t10 * xj + t11 * yi + t12) * half_box + ecy;
-    }
-    // arg-min / arg-max: first occurrence in the reference's row-major point order (corners 0, 14, 210, 224 = k 0..3)
-    int ux1 = 0, ux2 = 0, vy1 = 0, vy2 = 0;
-#pragma unroll
-    for (int k = 1; k < 4; ++k) {
-      if (U[k] < U[ux1]) ux1 = k;
-      if (U[k] > U[ux2]) ux2 = k;
-      if (V[k] < V[vy1]) vy1 = k;
-      if (V[k] > V[vy2]) vy2 = k;
-    }
-    const float ax1 = ecx - half_box, ay1 = ecy - half_box;
-    const float aw = (ecx + half_box) - ax1, ah = (ecy + half_box) - ay1;
-    float dU[4] = {0.f, 0.f, 0.f, 0.f}, dV[4] = {0.f, 0.f, 0.f, 0.f};
-    {
-      float x1 = U[ux1], x2 = U[ux2];
-      const bool clip = x1 + 1.0f > x2;
-      if (clip) x2 = x1 + 1.0f;
-      const float dg = 10.0f * l0 / aw, dw_ = 5.0f * l2 / (x2 - x1);
-      float g1 = 0.5f * dg - dw_, g2 = 0.5f * dg + dw_;
-      if (clip) {
-        g1 += g2;
-        g2 = 0.f;
-      }
-      dU[ux1] += g1;
-      dU[ux2] += g2;
-    }
-    {
-      float y1 = V[vy1], y2 = V[vy2];
-      const bool clip = y1 + 1.0f > y2;
-      if (clip) y2 = y1 + 1.0f;
-      const float dg = 10.0f * l1 / ah, dh_ = 5.0f * l3 / (y2 - y1);
-      float g1 = 0.5f * dg - dh_, g2 = 0.5f * dg + dh_;
-      if (clip) {
-        g1 += g2;
-        g2 = 0.f;
-      }
-      dV[vy1] += g1;
-      dV[vy2] += g2;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float yi = (k & 2) ? 1.0f : -1.0f;
-      const float xj = (k & 1) ? 1.0f : -1.0f;
-      const float gx = dU[k] * half_box, gy = dV[k] * half_box;
-      d00 += gx * xj;
-      d01 += gx * yi;
-      d02 += gx;
-      d10 += gy * xj;
-      d11 += gy * yi;
-      d12 += gy;
-    }
-  }
-  double g[6] = {d00, d01, d02, d10, d11, d12};
-  if (inverse) {   // theta = top rows of M^-1 (M = [[p],[0 0 1]], regularised as the forward did): dM = -N^T G N^T in fp64
-    double a, b, c, d, tx, ty;
-    if (P == 6) {
-      a = pp[0]; b = pp[HW]; tx = pp[2 * (size_t)HW]; c = pp[3 * (size_t)HW]; d = pp[4 * (size_t)HW]; ty = pp[5 * (size_t)HW];
-    } else {
-      a = pp[0]; b = 0.0; tx = pp[HW]; c = 0.0; d = pp[2 * (size_t)HW]; ty = pp[3 * (size_t)HW];
-    }
-    double hom = 1.0;
-    double det = a * d - b * c;
-    if (det == 0.0) {
-      a = (double)((float)a + 1e-5f);
-      d = (double)((float)d + 1e-5f);
-      hom = (double)(1.0f + 1e-5f);
-      det = a * d - b * c;
-    }
-    const double r = 1.0 / det;
-    const double i00 = d * r, i01 = -b * r, i10 = -c * r, i11 = a * r;
-    const double N[3][3] = {{i00, i01, -(i00 * tx + i01 * ty) / hom}, {i10, i11, -(i10 * tx + i11 * ty) / hom}, {0.0, 0.0, 1.0 / hom}};
-    const double G[3][3] = {{g[0], g[1], g[2]}, {g[3], g[4], g[5]}, {0.0, 0.0, 0.0}};
-    double X[3][3];   // X = G N^T
-    for (int u = 0; u < 3; ++u)
-      for (int v = 0; v < 3; ++v) X[u][v] = G[u][0] * N[v][0] + G[u][1] * N[v][1] + G[u][2] * N[v][2];
-    for (int u = 0; u < 2; ++u)     // dM[u][v] = -sum_s N[s][u] X[s][v]
-      for (int v = 0; v < 3; ++v) g[u * 3 + v] = -(N[0][u] * X[0][v] + N[1][u] * X[1][v] + N[2][u] * X[2][v]);
-  }
-  float* dp = dparams + (size_t)nb * P * HW + n;
-  if (P == 6) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) dp[(size_t)k * HW] = (float)g[k];
-  } else {
-    dp[0] = (float)g[0];
-    dp[HW] = (float)g[2];
-    dp[2 * (size_t)HW] = (float)g[4];
-    dp[3 * (size_t)HW] = (float)g[5];
-  }
-}
-
-// ---- the maxima of the order-independent route: words[nb] = max over the pair's locations of |dcls + dcls_det| (the fp32 sum
-// decode_backward_kernel forms), as the bits of a non-negative float - they order as unsigned integers, a NaN's above every
-// number's.  A work-group reduces DET_MAX_CHUNK locations and makes ONE atomicMax (the maxima pass of gemm_f16x3.hip).
-constexpr int DET_MAX_CHUNK = 2048;
-__global__ __launch_bounds__(256) void decode_det_max_kernel(const float* __restrict__ dcls, const float* __restrict__ dcls_det, int HW,
-                                                             unsigned* __restrict__ words) {
-  __shared__ unsigned red[4];
-  const int nb = blockIdx.y;
-  const int n0 = blockIdx.x * DET_MAX_CHUNK, n1 = min(HW, n0 + DET_MAX_CHUNK);
-  unsigned m = 0u;
-  for (int n = n0 + threadIdx.x; n < n1; n += 256) {
-    const size_t o = (size_t)nb * HW + n;
-    const float gcls = dcls ? dcls[o] : 0.f;
-    const float gsum = gcls + (dcls_det ? dcls_det[o] : 0.f);
-    m = max(m, __float_as_uint(gsum) & 0x7fffffffu);
-  }
-  for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m = max(max(red[0], red[1]), max(red[2], red[3]));
-    if (m != 0u) atomicMax(words + nb, m);
-  }
-}
-
-// ---- the convert pass: dcorr[cell] += (float)(sum * 2^-e), one thread per cell of a pair.  A zero sum leaves the cell as it
-// is (so does a pair whose maximum is zero); a pair with a non-finite maximum gets NaN in every cell.
-__global__ __launch_bounds__(256) void decode_det_convert_kernel(DetSink sink, size_t cells, float* __restrict__ dcorr) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const int nb = blockIdx.y;
-  if (i >= cells) return;
-  const int e = os2d_det_exponent(sink.words[nb], sink.L);
-  if (e == OS2D_TRAIN_DET_ZERO) return;
-  float* d = dcorr + (size_t)nb * cells + i;
-  if (e == OS2D_TRAIN_DET_NONFINITE) {
-    *d = __uint_as_float(0x7fc00000u);
-    return;
-  }
-  const long long q = (long long)sink.acc[(size_t)nb * cells + i];
-  if (q != 0) *d += (float)((double)q * det_pow2(-e));
 }
 
 // dparams [NB,P,HW] -> plane layout (zero pads)
@@ -557,7 +216,33 @@ __global__ __launch_bounds__(256) void class_resize_backward_kernel(const float*
   }
 }
 
-inline unsigned blocks(size_t n) { return (unsigned)((n + 255) / 256); }
+// ---- the argument checks the entry points share; `who` is the entry point's name in the error text (the *_ex entry points
+// report under the name without _ex).  The bad_... ones return true after setting the text.
+bool null_pointer(const char* who, bool pointers) { return !pointers && OS2D_REFUSE(true, "%s: null pointer", who); }
+// 0, or the return code
+int check_decode(const char* who, bool pointers, int NB, int H, int W, int P, int stride, int rec_field) {
+  if (null_pointer(who, pointers)) return -1;
+  if (NB < 1 || H < 1 || W < 1 || (P != 6 && P != 4) || stride < 1 || rec_field < 1)
+    return OS2D_REFUSE(-1, "%s: bad shape NB=%d H=%d W=%d P=%d stride=%d rec_field=%d", who, NB, H, W, P, stride, rec_field);
+  return NB > 65535 ? OS2D_REFUSE(-3, "%s: NB=%d > 65535", who, NB) : 0;
+}
+bool bad_arith(const char* who, int arith) {
+  return arith != 0 && arith != 1 && OS2D_REFUSE(true, "%s: bad arith %d (0 = fp32, 1 = f16x3)", who, arith);
+}
+// bn_only: the entry point takes the layers with a BatchNorm alone
+bool bad_layer(const char* who, int layer, int P, bool bn_only, Layer* L) {
+  if ((!bn_only || layer_channels(layer)) && layer_shape(layer, P, L)) return false;
+  return OS2D_REFUSE(true, "%s: bad layer %d / P %d%s", who, layer, P, bn_only ? " (the layers with a BatchNorm: 1 or 2)" : "");
+}
+// planes: the launch puts NB * planes on a grid axis (1: NB itself, 0: neither)
+bool bad_conv_shape(const char* who, int NB, int H, int W, int planes) {
+  if (shape_ok(NB, H, W) && (size_t)NB * planes <= 65535) return false;
+  if (planes <= 1) return OS2D_REFUSE(true, "%s: bad shape NB=%d H=%d W=%d (W <= %d)", who, NB, H, W, OS2D_MAX_W_DIRECT7);
+  return OS2D_REFUSE(true, "%s: bad shape NB=%d H=%d W=%d (W <= %d, NB * %d <= 65535)", who, NB, H, W, OS2D_MAX_W_DIRECT7, planes);
+}
+bool workspace_too_small(const char* who, size_t have, size_t need) {
+  return have < need && OS2D_REFUSE(true, "%s: workspace %zu floats < %zu", who, have, need);
+}
 
 }  // namespace
 
@@ -571,22 +256,10 @@ int os2d_train_decode_backward(const float* corr, const float* params, const flo
                                int NB, int H, int W, int P, int inverse, int stride, int rec_field, float* dcorr, float* dparams,
                                void* stream) {
   os2d_clear_error();
-  if (!corr || !params || !dcorr || !dparams) {
-    os2d_set_error("os2d_train_decode_backward: null pointer");
-    return -1;
-  }
-  if (NB < 1 || H < 1 || W < 1 || (P != 6 && P != 4) || stride < 1 || rec_field < 1) {
-    os2d_set_error("os2d_train_decode_backward: bad shape NB=%d H=%d W=%d P=%d stride=%d rec_field=%d", NB, H, W, P, stride, rec_field);
-    return -1;
-  }
-  if (NB > 65535) {
-    os2d_set_error("os2d_train_decode_backward: NB=%d > 65535", NB);
-    return -3;
-  }
-  const float half_box = 0.5f * (float)(stride * (OS2D_T - 1) + rec_field);
-  hipLaunchKernelGGL(decode_backward_kernel<false>, dim3(blocks((size_t)H * W), NB), dim3(256), 0, os2d_stream(stream), corr, params, dcls,
-                     dcls_det, dloc, H, W, P, inverse ? 1 : 0, (float)stride, half_box, dcorr, dparams, DetSink{nullptr, nullptr, 0});
-  return os2d_launched("decode_backward_kernel");
+  const int rc = check_decode("os2d_train_decode_backward", corr && params && dcorr && dparams, NB, H, W, P, stride, rec_field);
+  if (rc) return rc;
+  return os2d_decode_backward_launch(corr, params, dcls, dcls_det, dloc, NB, H, W, P, inverse, stride, rec_field, dcorr, dparams,
+                                     os2d_stream(stream));
 }
 
 int os2d_train_decode_det_exponent(unsigned max_bits, int H, int W) {
@@ -594,78 +267,32 @@ int os2d_train_decode_det_exponent(unsigned max_bits, int H, int W) {
   return L < 0 ? OS2D_TRAIN_DET_REFUSED : os2d_det_exponent(max_bits, L);
 }
 
-// the accumulator, then the pair words
-static size_t det_acc_bytes(int NB, int H, int W) { return (size_t)NB * OS2D_K * H * W * sizeof(long long); }
 size_t os2d_train_decode_backward_det_workspace_bytes(int NB, int H, int W) {
   if (NB < 1 || NB > 65535 || os2d_det_log2_addends(H, W) < 0) return 0;
-  return (det_acc_bytes(NB, H, W) + (size_t)NB * sizeof(unsigned) + 255) / 256 * 256;
+  return os2d_det_workspace_bytes(NB, H, W);
 }
 
 int os2d_train_decode_backward_det(const float* corr, const float* params, const float* dcls, const float* dcls_det, const float* dloc,
                                    int NB, int H, int W, int P, int inverse, int stride, int rec_field, float* dcorr, float* dparams,
                                    void* workspace, size_t workspace_bytes, void* stream) {
   os2d_clear_error();
-  if (!corr || !params || !dcorr || !dparams || !workspace) {
-    os2d_set_error("os2d_train_decode_backward_det: null pointer");
-    return -1;
-  }
-  if (NB < 1 || H < 1 || W < 1 || (P != 6 && P != 4) || stride < 1 || rec_field < 1) {
-    os2d_set_error("os2d_train_decode_backward_det: bad shape NB=%d H=%d W=%d P=%d stride=%d rec_field=%d", NB, H, W, P, stride, rec_field);
-    return -1;
-  }
-  if (NB > 65535) {
-    os2d_set_error("os2d_train_decode_backward_det: NB=%d > 65535", NB);
-    return -3;
-  }
-  const int L = os2d_det_log2_addends(H, W);
-  if (L < 0) {
-    os2d_set_error("os2d_train_decode_backward_det: H*W=%lld > 2^%d locations: the fixed-point step would exceed 2^-30 of a pair's largest addend",
-                   (long long)H * W, OS2D_DET_MAX_LOG2 - 2);
-    return -3;
-  }
-  if (((uintptr_t)workspace & 7) != 0) {
-    os2d_set_error("os2d_train_decode_backward_det: workspace is not 8-byte aligned");
-    return -1;
-  }
-  const size_t need = os2d_train_decode_backward_det_workspace_bytes(NB, H, W);
-  if (workspace_bytes < need) {
-    os2d_set_error("os2d_train_decode_backward_det: workspace %zu bytes < %zu", workspace_bytes, need);
-    return -2;
-  }
-  const int HW = H * W;
-  const size_t cells = (size_t)OS2D_K * HW;
-  unsigned* words = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + det_acc_bytes(NB, H, W));
-  const DetSink sink{static_cast<unsigned long long*>(workspace), words, L};
-  const hipError_t err = hipMemsetAsync(workspace, 0, need, os2d_stream(stream));
-  if (err != hipSuccess) {
-    os2d_set_error("os2d_train_decode_backward_det: hipMemsetAsync of the workspace: %s", hipGetErrorString(err));
-    return -4;
-  }
-  int rc = 0;
-  if (dcls || dcls_det) {       // without either the words stay zero: no pair adds anything
-    hipLaunchKernelGGL(decode_det_max_kernel, dim3((HW + DET_MAX_CHUNK - 1) / DET_MAX_CHUNK, NB), dim3(256), 0, os2d_stream(stream), dcls,
-                       dcls_det, HW, words);
-    if ((rc = os2d_launched("decode_det_max_kernel"))) return rc;
-  }
-  const float half_box = 0.5f * (float)(stride * (OS2D_T - 1) + rec_field);
-  hipLaunchKernelGGL(decode_backward_kernel<true>, dim3(blocks((size_t)HW), NB), dim3(256), 0, os2d_stream(stream), corr, params, dcls,
-                     dcls_det, dloc, H, W, P, inverse ? 1 : 0, (float)stride, half_box, dcorr, dparams, sink);
-  if ((rc = os2d_launched("decode_backward_kernel (deterministic)"))) return rc;
-  if (!dcls && !dcls_det) return 0;
-  hipLaunchKernelGGL(decode_det_convert_kernel, dim3(blocks(cells), NB), dim3(256), 0, os2d_stream(stream), sink, cells, dcorr);
-  return os2d_launched("decode_det_convert_kernel");
+  const int rc = check_decode("os2d_train_decode_backward_det", corr && params && dcorr && dparams && workspace, NB, H, W, P, stride, rec_field);
+  if (rc) return rc;
+  if (os2d_det_log2_addends(H, W) < 0)
+    return OS2D_REFUSE(-3, "os2d_train_decode_backward_det: H*W=%lld > 2^%d locations: the fixed-point step would exceed 2^-30 of a pair's "
+                       "largest addend", (long long)H * W, OS2D_DET_MAX_LOG2 - 2);
+  if (((uintptr_t)workspace & 7) != 0) return OS2D_REFUSE(-1, "os2d_train_decode_backward_det: workspace is not 8-byte aligned");
+  const size_t need = os2d_det_workspace_bytes(NB, H, W);
+  if (workspace_bytes < need) return OS2D_REFUSE(-2, "os2d_train_decode_backward_det: workspace %zu bytes < %zu", workspace_bytes, need);
+  return os2d_decode_backward_det_launch(corr, params, dcls, dcls_det, dloc, NB, H, W, P, inverse, stride, rec_field, dcorr, dparams,
+                                         workspace, os2d_stream(stream));
 }
 
 int os2d_train_params_backward(const float* dparams, int NB, int P, int H, int W, float* dy, float* dbias, void* stream) {
   os2d_clear_error();
-  if (!dparams || !dy) {
-    os2d_set_error("os2d_train_params_backward: null pointer");
-    return -1;
-  }
-  if ((P != 6 && P != 4) || !shape_ok(NB, H, W) || (size_t)NB * P > 65535) {
-    os2d_set_error("os2d_train_params_backward: bad shape NB=%d P=%d H=%d W=%d", NB, P, H, W);
-    return -1;
-  }
+  if (null_pointer("os2d_train_params_backward", dparams && dy)) return -1;
+  if ((P != 6 && P != 4) || !shape_ok(NB, H, W) || (size_t)NB * P > 65535)
+    return OS2D_REFUSE(-1, "os2d_train_params_backward: bad shape NB=%d P=%d H=%d W=%d", NB, P, H, W);
   const int PL = os2d_plane(H, W);
   hipLaunchKernelGGL(compact_to_plane_kernel, dim3(blocks(PL), NB * P), dim3(256), 0, os2d_stream(stream), dparams, P, H, W, PL, dy);
   int rc = os2d_launched("compact_to_plane_kernel");
@@ -678,27 +305,18 @@ int os2d_train_bn_relu_backward(int layer, const float* dh, const float* h, cons
                                 const float* running_var, float eps, int NB, int H, int W, float* dy, float* dgamma, float* dbeta,
                                 float* dbias, void* stream) {
   os2d_clear_error();
-  Layer L;
-  if (layer != 1 && layer != 2) {
-    os2d_set_error("os2d_train_bn_relu_backward: layer %d has no BatchNorm (1 or 2)", layer);
-    return -1;
-  }
-  layer_shape(layer, 6, &L);
-  if (!dh || !h || !gamma || !beta || !running_var || !dy) {
-    os2d_set_error("os2d_train_bn_relu_backward: null pointer");
-    return -1;
-  }
-  if (!shape_ok(NB, H, W) || (size_t)NB * L.cout > 65535 || !(eps >= 0.f)) {
-    os2d_set_error("os2d_train_bn_relu_backward: bad shape NB=%d H=%d W=%d eps=%g", NB, H, W, (double)eps);
-    return -1;
-  }
+  const int C = layer_channels(layer);
+  if (C == 0) return OS2D_REFUSE(-1, "os2d_train_bn_relu_backward: layer %d has no BatchNorm (1 or 2)", layer);
+  if (null_pointer("os2d_train_bn_relu_backward", dh && h && gamma && beta && running_var && dy)) return -1;
+  if (!shape_ok(NB, H, W) || (size_t)NB * C > 65535 || !(eps >= 0.f))
+    return OS2D_REFUSE(-1, "os2d_train_bn_relu_backward: bad shape NB=%d H=%d W=%d eps=%g", NB, H, W, (double)eps);
   const int PL = os2d_plane(H, W);
-  hipLaunchKernelGGL(bn_relu_mask_kernel, dim3(blocks(PL), NB * L.cout), dim3(256), 0, os2d_stream(stream), dh, h, gamma, running_var, eps,
-                     L.cout, H, W, PL, dy);
+  hipLaunchKernelGGL(bn_relu_mask_kernel, dim3(blocks(PL), NB * C), dim3(256), 0, os2d_stream(stream), dh, h, gamma, running_var, eps, C, H, W,
+                     PL, dy);
   int rc = os2d_launched("bn_relu_mask_kernel");
   if (rc || (!dgamma && !dbeta && !dbias)) return rc;
-  hipLaunchKernelGGL(bn_relu_sums_kernel, dim3(L.cout), dim3(256), 0, os2d_stream(stream), dh, h, gamma, beta, running_var, eps, NB, L.cout, H,
-                     W, PL, dgamma, dbeta, dbias);
+  hipLaunchKernelGGL(bn_relu_sums_kernel, dim3(C), dim3(256), 0, os2d_stream(stream), dh, h, gamma, beta, running_var, eps, NB, C, H, W, PL,
+                     dgamma, dbeta, dbias);
   return os2d_launched("bn_relu_sums_kernel");
 }
 
@@ -710,49 +328,25 @@ size_t os2d_train_conv_data_workspace_floats(int layer, int P) {
 
 size_t os2d_train_conv_data_workspace_floats_ex(int arith, int layer, int P, int NB) {
   const size_t wf = os2d_train_conv_data_workspace_floats(layer, P);
-  if (arith == 0 || wf == 0) return arith == 0 ? wf : 0;
-  if (arith != 1 || NB < 1) return 0;
-  return wf + 1 + (size_t)NB;                 // the flipped filters, then the maxima words: the filters', one per pair of dy
+  if ((arith != 0 && arith != 1) || wf == 0 || (arith && NB < 1)) return 0;
+  return wf + conv_words(arith, NB);
 }
 
 int os2d_train_conv_backward_data_ex(int arith, int layer, int P, const float* w, const float* dy, int NB, int H, int W, float* dx,
                                      float* workspace, size_t workspace_floats, void* stream) {
   os2d_clear_error();
+  const char* who = "os2d_train_conv_backward_data";
   Layer L;
-  if (arith != 0 && arith != 1) {
-    os2d_set_error("os2d_train_conv_backward_data: bad arith %d (0 = fp32, 1 = f16x3)", arith);
+  if (bad_arith(who, arith) || bad_layer(who, layer, P, false, &L) || null_pointer(who, w && dy && dx && workspace) ||
+      bad_conv_shape(who, NB, H, W, 1))
     return -1;
-  }
-  if (!layer_shape(layer, P, &L)) {
-    os2d_set_error("os2d_train_conv_backward_data: bad layer %d / P %d", layer, P);
-    return -1;
-  }
-  if (!w || !dy || !dx || !workspace) {
-    os2d_set_error("os2d_train_conv_backward_data: null pointer");
-    return -1;
-  }
-  if (!shape_ok(NB, H, W) || NB > 65535) {
-    os2d_set_error("os2d_train_conv_backward_data: bad shape NB=%d H=%d W=%d (W <= %d)", NB, H, W, OS2D_MAX_W_DIRECT7);
-    return -1;
-  }
-  const int T2 = L.ks * L.ks;
-  const size_t wf = (size_t)L.cout * L.cin * T2;
-  const size_t need = arith ? wf + 1 + (size_t)NB : wf;
-  if (workspace_floats < need) {
-    os2d_set_error("os2d_train_conv_backward_data: workspace %zu floats < %zu", workspace_floats, need);
-    return -2;
-  }
-  hipLaunchKernelGGL(flip_weights_kernel, dim3(blocks(wf)), dim3(256), 0, os2d_stream(stream), w, L.cout, L.cin, T2, workspace);
-  int rc = os2d_launched("flip_weights_kernel");
+  const size_t wf = (size_t)L.cout * L.cin * L.ks * L.ks;
+  if (workspace_too_small(who, workspace_floats, wf + conv_words(arith, NB))) return -2;      // the flipped filters, then the words
+  hipLaunchKernelGGL(flip_weights_kernel, dim3(blocks(wf)), dim3(256), 0, os2d_stream(stream), w, L.cout, L.cin, L.ks * L.ks, workspace);
+  const int rc = os2d_launched("flip_weights_kernel");
   if (rc) return rc;
-  if (arith)
-    return os2d_f16x3_conv_data(workspace, dy, dx, L.cout, L.cin, L.ks, NB, H, W, reinterpret_cast<unsigned*>(workspace + wf),
-                                os2d_stream(stream));
-  const int PL = os2d_plane(H, W);
-  const Taps tp{L.ks, L.ks / 2, os2d_ws(W), T2};
-  const int K = L.cout * T2;
-  return gemm<false>(LdRows{workspace, K}, LdShifted{dy, (size_t)L.cout * PL, PL, tp}, StPlane{dx, (size_t)L.cin * PL, PL, H, W}, L.cin,
-                     PL, K, NB, 0, os2d_stream(stream), "conv data gradient");
+  return os2d_gemm_conv_data(arith, workspace, dy, dx, L.cout, L.cin, L.ks, NB, H, W, reinterpret_cast<unsigned*>(workspace + wf),
+                             os2d_stream(stream));
 }
 
 int os2d_train_conv_backward_data(int layer, int P, const float* w, const float* dy, int NB, int H, int W, float* dx,
@@ -760,108 +354,57 @@ int os2d_train_conv_backward_data(int layer, int P, const float* w, const float*
   return os2d_train_conv_backward_data_ex(0, layer, P, w, dy, NB, H, W, dx, workspace, workspace_floats, stream);
 }
 
-// the forward convolution of a layer whose BatchNorm takes batch statistics: the data gradient's GEMM with the roles of the
-// channel counts swapped, the raw (unflipped) filters as the A operand and the bias added in the store
+// the forward convolution of a layer whose BatchNorm takes batch statistics
 size_t os2d_train_conv_forward_workspace_floats(int arith, int layer, int P, int NB) {
   Layer L;
-  if ((layer != 1 && layer != 2) || !layer_shape(layer, P, &L) || NB < 1) return 0;
-  return arith == 0 ? 1 : arith == 1 ? 1 + (size_t)NB : 0;      // f16x3: the maxima words (the filters', one per pair of x)
+  if ((arith != 0 && arith != 1) || layer_channels(layer) == 0 || !layer_shape(layer, P, &L) || NB < 1) return 0;
+  return conv_forward_floats(arith, NB);
 }
 
 int os2d_train_conv_forward(int arith, int layer, int P, const float* w, const float* bias, const float* x, int NB, int H, int W, float* z,
                             float* workspace, size_t workspace_floats, void* stream) {
   os2d_clear_error();
+  const char* who = "os2d_train_conv_forward";
   Layer L;
-  if (arith != 0 && arith != 1) {
-    os2d_set_error("os2d_train_conv_forward: bad arith %d (0 = fp32, 1 = f16x3)", arith);
+  if (bad_arith(who, arith) || bad_layer(who, layer, P, true, &L) || null_pointer(who, w && bias && x && z && workspace) ||
+      bad_conv_shape(who, NB, H, W, L.cout))
     return -1;
-  }
-  if ((layer != 1 && layer != 2) || !layer_shape(layer, P, &L)) {
-    os2d_set_error("os2d_train_conv_forward: bad layer %d / P %d (the layers with a BatchNorm: 1 or 2)", layer, P);
-    return -1;
-  }
-  if (!w || !bias || !x || !z || !workspace) {
-    os2d_set_error("os2d_train_conv_forward: null pointer");
-    return -1;
-  }
-  if (!shape_ok(NB, H, W) || (size_t)NB * L.cout > 65535) {
-    os2d_set_error("os2d_train_conv_forward: bad shape NB=%d H=%d W=%d (W <= %d, NB * %d <= 65535)", NB, H, W, OS2D_MAX_W_DIRECT7, L.cout);
-    return -1;
-  }
-  const size_t need = arith ? 1 + (size_t)NB : 1;
-  if (workspace_floats < need) {
-    os2d_set_error("os2d_train_conv_forward: workspace %zu floats < %zu", workspace_floats, need);
-    return -2;
-  }
-  if (arith)
-    return os2d_f16x3_conv_forward(w, bias, x, input_planes(layer), z, L.cout, L.cin, L.ks, NB, H, W, reinterpret_cast<unsigned*>(workspace),
-                                   os2d_stream(stream));
-  const int PL = os2d_plane(H, W), T2 = L.ks * L.ks;
-  const Taps tp{L.ks, L.ks / 2, os2d_ws(W), T2};
-  return gemm<false>(LdRows{w, L.cin * T2}, LdShifted{x, (size_t)input_planes(layer) * PL, PL, tp},
-                     StPlane{z, (size_t)L.cout * PL, PL, H, W, bias}, L.cout, PL, L.cin * T2, NB, 0, os2d_stream(stream), "conv forward");
+  if (workspace_too_small(who, workspace_floats, conv_forward_floats(arith, NB))) return -2;
+  return os2d_gemm_conv_forward(arith, w, bias, x, input_planes(layer), z, L.cout, L.cin, L.ks, NB, H, W,
+                                reinterpret_cast<unsigned*>(workspace), os2d_stream(stream));
 }
 
 size_t os2d_train_conv_weight_slice_floats(int layer, int P) { return os2d_train_conv_data_workspace_floats(layer, P); }
 
-// f16x3: every slice of room carries WEIGHT_WORDS floats more; the maxima words take the first WEIGHT_WORDS floats of the workspace
-constexpr size_t WEIGHT_WORDS = 16;
 size_t os2d_train_conv_weight_slice_floats_ex(int arith, int layer, int P) {
   const size_t slice = os2d_train_conv_weight_slice_floats(layer, P);
-  if (arith == 0 || slice == 0) return arith == 0 ? slice : 0;
-  return arith == 1 ? slice + WEIGHT_WORDS : 0;
+  if ((arith != 0 && arith != 1) || slice == 0) return 0;
+  return slice + weight_words_room(arith);
 }
 
 int os2d_train_conv_backward_weight_ex(int arith, int layer, int P, const float* x, const float* dy, int NB, int H, int W, float* dw,
                                        float* workspace, size_t workspace_floats, void* stream) {
   os2d_clear_error();
+  const char* who = "os2d_train_conv_backward_weight";
   Layer L;
-  if (arith != 0 && arith != 1) {
-    os2d_set_error("os2d_train_conv_backward_weight: bad arith %d (0 = fp32, 1 = f16x3)", arith);
+  if (bad_arith(who, arith) || bad_layer(who, layer, P, false, &L) || null_pointer(who, x && dy && dw && workspace) ||
+      bad_conv_shape(who, NB, H, W, 0))
     return -1;
-  }
-  if (!layer_shape(layer, P, &L)) {
-    os2d_set_error("os2d_train_conv_backward_weight: bad layer %d / P %d", layer, P);
-    return -1;
-  }
-  if (!x || !dy || !dw || !workspace) {
-    os2d_set_error("os2d_train_conv_backward_weight: null pointer");
-    return -1;
-  }
-  if (!shape_ok(NB, H, W)) {
-    os2d_set_error("os2d_train_conv_backward_weight: bad shape NB=%d H=%d W=%d (W <= %d)", NB, H, W, OS2D_MAX_W_DIRECT7);
-    return -1;
-  }
-  const int T2 = L.ks * L.ks;
-  const size_t slice = (size_t)L.cout * L.cin * T2;
-  const int PL = os2d_plane(H, W);
-  const long long K = (long long)NB * PL;
-  if (K > 0x7fffffffLL) {
-    os2d_set_error("os2d_train_conv_backward_weight: NB * PLANE = %lld positions exceed the 32-bit index", K);
-    return -3;
-  }
-  const size_t room = arith ? slice + WEIGHT_WORDS : slice;
-  const int kstep = arith ? OS2D_F16X3_KSTEP : GK;
+  const size_t slice = (size_t)L.cout * L.cin * L.ks * L.ks;
+  const long long K = (long long)NB * os2d_plane(H, W);
+  if (K > 0x7fffffffLL) return OS2D_REFUSE(-3, "os2d_train_conv_backward_weight: NB * PLANE = %lld positions exceed the 32-bit index", K);
+  const size_t room = slice + weight_words_room(arith);
+  const int ks = kstep(arith);
   long long splits = (long long)(workspace_floats / room);
-  if (splits < 1) {
-    os2d_set_error("os2d_train_conv_backward_weight: workspace %zu floats < one slice of %zu", workspace_floats, room);
-    return -2;
-  }
+  if (splits < 1)
+    return OS2D_REFUSE(-2, "os2d_train_conv_backward_weight: workspace %zu floats < one slice of %zu", workspace_floats, room);
   if (splits > 64) splits = 64;
-  if (splits > (K + kstep - 1) / kstep) splits = (K + kstep - 1) / kstep;
-  const int ksplit = (int)(((K + splits - 1) / splits + kstep - 1) / kstep * kstep);
+  if (splits > (K + ks - 1) / ks) splits = (K + ks - 1) / ks;
+  const int ksplit = (int)(((K + splits - 1) / splits + ks - 1) / ks * ks);
   splits = (K + ksplit - 1) / ksplit;
-  float* part = arith ? workspace + WEIGHT_WORDS : workspace;
-  int rc;
-  if (arith) {
-    rc = os2d_f16x3_conv_weight(x, input_planes(layer), dy, part, L.cout, L.cin, L.ks, NB, H, W, (int)splits, ksplit,
-                                reinterpret_cast<unsigned*>(workspace), os2d_stream(stream));
-  } else {
-    const Taps tp{L.ks, L.ks / 2, os2d_ws(W), T2};
-    const int N = L.cin * T2;
-    rc = gemm<true>(LdPairRows{dy, (size_t)L.cout * PL, PL}, LdPairShifted{x, (size_t)input_planes(layer) * PL, PL, tp},
-                    StSlice{workspace, L.cout, N}, L.cout, N, (int)K, (int)splits, ksplit, os2d_stream(stream), "conv weight gradient");
-  }
+  float* part = workspace + weight_words_room(arith);
+  const int rc = os2d_gemm_conv_weight(arith, x, input_planes(layer), dy, part, L.cout, L.cin, L.ks, NB, H, W, (int)splits, ksplit,
+                                       reinterpret_cast<unsigned*>(workspace), os2d_stream(stream));
   if (rc) return rc;
   hipLaunchKernelGGL(split_sum_kernel, dim3(blocks(slice)), dim3(256), 0, os2d_stream(stream), part, (int)splits, slice, dw);
   return os2d_launched("split_sum_kernel");
@@ -874,14 +417,8 @@ int os2d_train_conv_backward_weight(int layer, int P, const float* x, const floa
 
 int os2d_train_norm225_backward(const float* corr, const float* dxn, int NB, int H, int W, float* dcorr, void* stream) {
   os2d_clear_error();
-  if (!corr || !dxn || !dcorr) {
-    os2d_set_error("os2d_train_norm225_backward: null pointer");
-    return -1;
-  }
-  if (!shape_ok(NB, H, W) || NB > 65535) {
-    os2d_set_error("os2d_train_norm225_backward: bad shape NB=%d H=%d W=%d", NB, H, W);
-    return -1;
-  }
+  if (null_pointer("os2d_train_norm225_backward", corr && dxn && dcorr)) return -1;
+  if (!shape_ok(NB, H, W) || NB > 65535) return OS2D_REFUSE(-1, "os2d_train_norm225_backward: bad shape NB=%d H=%d W=%d", NB, H, W);
   hipLaunchKernelGGL(norm225_backward_kernel, dim3(blocks((size_t)H * W), NB), dim3(256), 0, os2d_stream(stream), corr, dxn, H, W,
                      os2d_plane(H, W), dcorr);
   return os2d_launched("norm225_backward_kernel");
@@ -889,67 +426,41 @@ int os2d_train_norm225_backward(const float* corr, const float* dxn, int NB, int
 
 size_t os2d_train_corr_workspace_floats(int A, int C, int H, int W) {
   if (A < 1 || C < 1 || H < 1 || W < 1) return 0;
-  const size_t HW = (size_t)H * W;
-  return 2 * (size_t)A * HW + (size_t)A * C * HW;
+  return corr_workspace(0, A, 0, C, (size_t)H * W).total;
 }
 
 size_t os2d_train_corr_workspace_floats_ex(int arith, int A, int B, int C, int H, int W) {
-  const size_t base = os2d_train_corr_workspace_floats(A, C, H, W);
-  if (arith == 0 || base == 0) return arith == 0 ? base : 0;
-  if (arith != 1 || B < 1) return 0;
-  return base + 2 + (size_t)A + B;            // the maxima words: qp, the normalised image map, dcorr per image, dcorr per class
+  if ((arith != 0 && arith != 1) || os2d_train_corr_workspace_floats(A, C, H, W) == 0 || (arith && B < 1)) return 0;
+  return corr_workspace(arith, A, B, C, (size_t)H * W).total;
 }
 
 int os2d_train_corr_backward_ex(int arith, const float* fm, const float* qp, const float* dcorr, int A, int B, int C, int H, int W,
                                 float* dfm, float* dq, float* workspace, size_t workspace_floats, void* stream) {
   os2d_clear_error();
-  if (arith != 0 && arith != 1) {
-    os2d_set_error("os2d_train_corr_backward: bad arith %d (0 = fp32, 1 = f16x3)", arith);
-    return -1;
-  }
-  if (!fm || !qp || !dcorr || !workspace) {
-    os2d_set_error("os2d_train_corr_backward: null pointer");
-    return -1;
-  }
-  if (A < 1 || B < 1 || C < 1 || H < 1 || W < 1 || A > 65535 || B > 65535) {
-    os2d_set_error("os2d_train_corr_backward: bad shape A=%d B=%d C=%d H=%d W=%d", A, B, C, H, W);
-    return -1;
-  }
+  const char* who = "os2d_train_corr_backward";
+  if (bad_arith(who, arith) || null_pointer(who, fm && qp && dcorr && workspace)) return -1;
+  if (A < 1 || B < 1 || C < 1 || H < 1 || W < 1 || A > 65535 || B > 65535)
+    return OS2D_REFUSE(-1, "os2d_train_corr_backward: bad shape A=%d B=%d C=%d H=%d W=%d", A, B, C, H, W);
   const long long HW = (long long)H * W;
-  if ((long long)B * OS2D_K > 0x7fffffffLL || (long long)A * HW > 0x7fffffffLL) {
-    os2d_set_error("os2d_train_corr_backward: reduction length exceeds the 32-bit index");
-    return -3;
-  }
-  const size_t base = os2d_train_corr_workspace_floats(A, C, H, W);
-  const size_t need = arith ? base + 2 + (size_t)A + B : base;
-  if (workspace_floats < need) {
-    os2d_set_error("os2d_train_corr_backward: workspace %zu floats < %zu", workspace_floats, need);
-    return -2;
-  }
+  if ((long long)B * OS2D_K > 0x7fffffffLL || (long long)A * HW > 0x7fffffffLL)
+    return OS2D_REFUSE(-3, "os2d_train_corr_backward: reduction length exceeds the 32-bit index");
+  const CorrWorkspace ws = corr_workspace(arith, A, B, C, (size_t)HW);
+  if (workspace_too_small(who, workspace_floats, ws.total)) return -2;
   if (!dfm && !dq) return 0;
+  hipStream_t st = os2d_stream(stream);
   float* rinv = workspace;
-  float* dfh = rinv + 2 * (size_t)A * HW;     // the second A * HW floats are not used
-  hipLaunchKernelGGL(image_norm_kernel, dim3(blocks(HW), A), dim3(256), 0, os2d_stream(stream), fm, C, (int)HW, rinv);
+  float* dfh = workspace + ws.dfh;
+  unsigned* words = reinterpret_cast<unsigned*>(workspace + ws.words);
+  hipLaunchKernelGGL(image_norm_kernel, dim3(blocks(HW), A), dim3(256), 0, st, fm, C, (int)HW, rinv);
   int rc = os2d_launched("image_norm_kernel");
   if (rc) return rc;
-  if (arith) {
-    rc = os2d_f16x3_corr(fm, rinv, qp, dcorr, A, B, C, (int)HW, dfm ? dfh : nullptr, dq, reinterpret_cast<unsigned*>(workspace + base),
-                         os2d_stream(stream));
-    if (rc || !dfm) return rc;
-    hipLaunchKernelGGL(image_norm_backward_kernel, dim3(blocks(HW), A), dim3(256), 0, os2d_stream(stream), fm, dfh, C, (int)HW, dfm);
-    return os2d_launched("image_norm_backward_kernel");
-  }
+  if (arith && (rc = os2d_gemm_corr_maxima(dcorr, A, B, (int)HW, words, st))) return rc;
   if (dfm) {
-    rc = gemm<false>(LdClassT{qp, C}, LdCorrRows{dcorr, B, (int)HW}, StDense{dfh, C, (int)HW}, C, (int)HW, B * OS2D_K, A, 0, os2d_stream(stream),
-                     "correlation backward (image)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(image_norm_backward_kernel, dim3(blocks(HW), A), dim3(256), 0, os2d_stream(stream), fm, dfh, C, (int)HW, dfm);
-    rc = os2d_launched("image_norm_backward_kernel");
-    if (rc) return rc;
+    if ((rc = os2d_gemm_corr_image(arith, qp, dcorr, A, B, C, (int)HW, dfh, words, st))) return rc;
+    hipLaunchKernelGGL(image_norm_backward_kernel, dim3(blocks(HW), A), dim3(256), 0, st, fm, dfh, C, (int)HW, dfm);
+    if ((rc = os2d_launched("image_norm_backward_kernel"))) return rc;
   }
-  if (dq)
-    rc = gemm<true>(LdImageNorm{fm, rinv, C, (int)HW}, LdCorrCols{dcorr, B, (int)HW}, StDense{dq, C, OS2D_K}, C, OS2D_K, A * (int)HW, B,
-                    0, os2d_stream(stream), "correlation backward (class)");
+  if (dq) rc = os2d_gemm_corr_class(arith, fm, rinv, dcorr, A, B, C, (int)HW, dq, words, st);
   return rc;
 }
 
@@ -961,19 +472,9 @@ int os2d_train_corr_backward(const float* fm, const float* qp, const float* dcor
 int os2d_train_class_backward(const float* q15, const float* dq, int B, int C, float* const* dsrcs, const int* sizes,
                               float* workspace, size_t workspace_floats, void* stream) {
   os2d_clear_error();
-  if (!q15 || !dq || !dsrcs || !sizes || !workspace) {
-    os2d_set_error("os2d_train_class_backward: null pointer");
-    return -1;
-  }
-  if (B < 1 || C < 1 || B > 65535) {
-    os2d_set_error("os2d_train_class_backward: bad shape B=%d C=%d", B, C);
-    return -1;
-  }
-  const size_t need = (size_t)B * C * OS2D_K;
-  if (workspace_floats < need) {
-    os2d_set_error("os2d_train_class_backward: workspace %zu floats < %zu", workspace_floats, need);
-    return -2;
-  }
+  if (null_pointer("os2d_train_class_backward", q15 && dq && dsrcs && sizes && workspace)) return -1;
+  if (B < 1 || C < 1 || B > 65535) return OS2D_REFUSE(-1, "os2d_train_class_backward: bad shape B=%d C=%d", B, C);
+  if (workspace_too_small("os2d_train_class_backward", workspace_floats, (size_t)B * C * OS2D_K)) return -2;
   hipLaunchKernelGGL(class_norm_backward_kernel, dim3(1, B), dim3(256), 0, os2d_stream(stream), q15, dq, C, workspace);
   int rc = os2d_launched("class_norm_backward_kernel");
   if (rc) return rc;

@@ -1,4 +1,5 @@
-// Operand loaders and result stores of the backward GEMMs (train.hip: gemm16_kernel, fp32; gemm_f16x3.hip: the split-fp16 kernel).
+// Operand loaders and result stores of the backward GEMMs (train_gemm.hip: gemm16_kernel, fp32; gemm_f16x3_kernel, split-fp16),
+// the workspace layouts of their entry points and the five launch sites.
 //
 // A loader answers two questions about the same matrix:
 //   operator()(z, row, k)          one element (gemm16_kernel stages element by element);
@@ -210,23 +211,51 @@ struct LdCorrCols {
   }
 };
 
+// ---- k-step of either kernel: the split-K slices of the weight gradient are whole k-steps
+constexpr int GEMM16_KSTEP = 16, F16X3_KSTEP = 32;
+inline int kstep(int arith) { return arith ? F16X3_KSTEP : GEMM16_KSTEP; }
+
+// ---- the float workspaces of the *_ex entry points, each defined once for its size function, its "workspace too small" check
+// and its launch.  Maxima words exist at arith = 1 only; the sites clear (hipMemsetAsync) and fill them, nothing waits for the host.
+// data gradient: the flipped filters, then conv_words; forward convolution: conv_words alone (fp32: one float nobody reads)
+inline size_t conv_words(int arith, int NB) { return arith ? 1 + (size_t)NB : 0; }      // the filters', one per pair
+inline size_t conv_forward_floats(int arith, int NB) { return arith ? conv_words(arith, NB) : 1; }
+// weight gradient: weight_words_room floats (2 words: dy, x) in front of the split-K slices, and as many more per slice of room
+constexpr size_t WEIGHT_WORDS = 2;
+inline size_t weight_words_room(int arith) { return arith ? 16 : 0; }
+// correlation backward: rinv [A,HW] | A*HW floats not used | dfh [A,C,HW] | words: qp, the normalised image map, dcorr per
+// image (A), dcorr per class (B)
+inline size_t corr_words(int arith, int A, int B) { return arith ? 2 + (size_t)A + B : 0; }
+struct CorrWorkspace {
+  size_t dfh, words, total;       // rinv starts at 0
+};
+inline CorrWorkspace corr_workspace(int arith, int A, int B, int C, size_t HW) {
+  const size_t dfh = 2 * (size_t)A * HW, words = dfh + (size_t)A * C * HW;
+  return {dfh, words, words + corr_words(arith, A, B)};
+}
+
 }  // namespace os2d_train_gemm
 
-// ---- the split-fp16 route of the four GEMM call sites (gemm_f16x3.hip).  `words` are unsigned words of the caller's workspace
-// that these functions clear (hipMemsetAsync) and fill with maxima; nothing waits for the host.
-// conv data gradient: wt = the flipped filters [cin][cout*T2]; words: 1 + NB
-int os2d_f16x3_conv_data(const float* wt, const float* dy, float* dx, int cout, int cin, int ks, int NB, int H, int W, unsigned* words,
-                         hipStream_t stream);
+// ---- the five GEMM launch sites (train_gemm.hip), each for both arithmetics: arith 0 = gemm16_kernel (fp32), 1 = the maxima
+// pass of the site's operands + gemm_f16x3_kernel.  `words`: the site's maxima words (not read at arith 0).  Calls between the
+// units of the library, not exports of it: hidden.
+#pragma GCC visibility push(hidden)
+// conv data gradient: wt = the flipped filters [cin][cout*T2]
+int os2d_gemm_conv_data(int arith, const float* wt, const float* dy, float* dx, int cout, int cin, int ks, int NB, int H, int W,
+                        unsigned* words, hipStream_t stream);
 // forward convolution z = conv(x) + bias (the training forward of a layer whose BatchNorm takes batch statistics): w = the raw
 // filters [cout][cin*T2] - a forward convolution is the data gradient's shape with the channel counts swapped and unflipped
-// filters -, xplanes = planes per pair of x; words: 1 + NB (the filters', one per pair of x)
-int os2d_f16x3_conv_forward(const float* w, const float* bias, const float* x, int xplanes, float* z, int cout, int cin, int ks, int NB,
-                            int H, int W, unsigned* words, hipStream_t stream);
-// conv weight gradient into `splits` partial slices of ksplit positions (a multiple of OS2D_F16X3_KSTEP); xplanes = planes per
-// pair of x; words: 2
-#define OS2D_F16X3_KSTEP 32
-int os2d_f16x3_conv_weight(const float* x, int xplanes, const float* dy, float* part, int cout, int cin, int ks, int NB, int H, int W,
-                           int splits, int ksplit, unsigned* words, hipStream_t stream);
-// correlation backward; words: 2 + A + B (qp, the normalised image map, dcorr per image, dcorr per class)
-int os2d_f16x3_corr(const float* fm, const float* rinv, const float* qp, const float* dcorr, int A, int B, int C, int HW, float* dfh,
-                    float* dq, unsigned* words, hipStream_t stream);
+// filters -, xplanes = planes per pair of x
+int os2d_gemm_conv_forward(int arith, const float* w, const float* bias, const float* x, int xplanes, float* z, int cout, int cin, int ks,
+                           int NB, int H, int W, unsigned* words, hipStream_t stream);
+// conv weight gradient into `splits` partial slices of ksplit positions (a multiple of kstep(arith)); xplanes = planes per pair of x
+int os2d_gemm_conv_weight(int arith, const float* x, int xplanes, const float* dy, float* part, int cout, int cin, int ks, int NB, int H,
+                          int W, int splits, int ksplit, unsigned* words, hipStream_t stream);
+// correlation backward, image side (dfh = d of the normalised image map) and class side (dq).  At arith = 1
+// os2d_gemm_corr_maxima goes first: it clears the 2 + A + B words and takes the maxima of dcorr both sides scale it by.
+int os2d_gemm_corr_maxima(const float* dcorr, int A, int B, int HW, unsigned* words, hipStream_t stream);
+int os2d_gemm_corr_image(int arith, const float* qp, const float* dcorr, int A, int B, int C, int HW, float* dfh, unsigned* words,
+                         hipStream_t stream);
+int os2d_gemm_corr_class(int arith, const float* fm, const float* rinv, const float* dcorr, int A, int B, int C, int HW, float* dq,
+                         unsigned* words, hipStream_t stream);
+#pragma GCC visibility pop

@@ -1,5 +1,13 @@
-// The backward GEMMs of the head in split-fp16 ("f16x3") arithmetic on v_mfma_f32_32x32x16_f16 (train_gemm.h declares the four
-// launchers; train.hip's *_ex entry points call them at arith = 1).
+// The GEMMs of the training library in both arithmetics, and the five sites that launch them (train_gemm.h declares the sites;
+// the entry points of train.hip call them with their `arith`).
+//
+// arith 0, fp32: ONE tiled kernel on v_mfma_f32_16x16x4_f32 (gemm16_kernel): 64 x 64 output tile per 256-thread work-group
+// (4 waves, each 2 x 2 blocks of 16 x 16), k-steps of 16 staged in LDS element by element.  Operands are read through the small
+// loader functors of train_gemm.h, so the same kernel runs the transposed convolutions (B = the output gradient read at the tap
+// offsets of the zero-bordered plane layout), the forward convolution in front of a batch-statistics BatchNorm (the same launch
+// with the raw filters and the bias added in the store), the weight gradients (an implicit GEMM over K = NB * PLANE positions,
+// split-K, partial sums added in a fixed order) and the two correlation GEMMs (d F^ = Q^T d corr, d Q^ = d corr F^T).
+// arith 1, split-fp16 ("f16x3") on v_mfma_f32_32x32x16_f16 (gemm_f16x3_kernel), same loaders, same stores:
 //
 // Arithmetic.  Every fp32 operand value x is multiplied by its operand's power-of-two scale 2^e, split into fp16 hi = rn16(x 2^e)
 // and lo = rn16(x 2^e - hi) where it is staged into LDS, and a product of two fragments is lo*hi + hi*lo + hi*hi accumulated in
@@ -31,7 +39,77 @@ using namespace os2d_train_gemm;
 
 namespace {
 
-constexpr int FK = OS2D_F16X3_KSTEP;    // k-step
+// ------------------------------------------------------------------------------------------------ fp32-MFMA GEMM
+constexpr int GT = 64;   // output tile (M and N)
+constexpr int GK = GEMM16_KSTEP;   // k-step staged in LDS
+
+// C(z)[m][n] = sum_{k in [kb, ke)} A(z, m, k) * B(z, k, n).  ksplit > 0: z is a split-K slice, [kb, ke) = [z*ksplit, ...);
+// ksplit == 0: z is a batch index and the whole K is reduced.  B_KFAST: B's fastest-varying address is k (else n).
+template <class LA, class LB, class ST, bool B_KFAST>
+__global__ __launch_bounds__(256) void gemm16_kernel(LA la, LB lb, ST st, int M, int N, int K, int ksplit) {
+  __shared__ float As[GK][GT + 4];
+  __shared__ float Bs[GK][GT + 4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int wm = wv >> 1, wn = wv & 1;
+  const int m0 = blockIdx.y * GT, n0 = blockIdx.x * GT, z = blockIdx.z;
+  const int kb = ksplit > 0 ? z * ksplit : 0;
+  const int ke = ksplit > 0 ? min(K, kb + ksplit) : K;
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = kb; k0 < ke; k0 += GK) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int e = tid + r * 256;
+      const int kk = e & (GK - 1), mm = e >> 4;
+      const int m = m0 + mm, k = k0 + kk;
+      As[kk][mm] = (m < M && k < ke) ? la(z, m, k) : 0.f;
+      int bk, bn;
+      if (B_KFAST) {
+        bk = e & (GK - 1);
+        bn = e >> 4;
+      } else {
+        bn = e & (GT - 1);
+        bk = e >> 6;
+      }
+      const int n = n0 + bn, k2 = k0 + bk;
+      Bs[bk][bn] = (n < N && k2 < ke) ? lb(z, k2, n) : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < GK / 4; ++s) {
+      const int kr = s * 4 + (lane >> 4);
+      const float a0 = As[kr][wm * 32 + (lane & 15)], a1 = As[kr][wm * 32 + 16 + (lane & 15)];
+      const float b0 = Bs[kr][wn * 32 + (lane & 15)], b1 = Bs[kr][wn * 32 + 16 + (lane & 15)];
+      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m0 + wm * 32 + i * 16 + (lane >> 4) * 4 + r;   // C/D map of the 16x16 MFMA: row (lane>>4)*4+r, col lane&15
+        const int n = n0 + wn * 32 + j * 16 + (lane & 15);
+        if (m < M && n < N) st(z, m, n, acc[i][j][r]);
+      }
+}
+
+template <bool B_KFAST, class LA, class LB, class ST>
+int gemm(LA la, LB lb, ST st, int M, int N, int K, int Z, int ksplit, hipStream_t stream, const char* what) {
+  const dim3 grid((N + GT - 1) / GT, (M + GT - 1) / GT, Z);
+  hipLaunchKernelGGL((gemm16_kernel<LA, LB, ST, B_KFAST>), grid, dim3(256), 0, stream, la, lb, st, M, N, K, ksplit);
+  return os2d_launched(what);
+}
+// ------------------------------------------------------------------------------------------------ split-fp16 GEMM
+constexpr int FK = F16X3_KSTEP;    // k-step
 constexpr int FROW = FK + 8;            // halves per LDS row
 constexpr int FTN = 128;                // columns per work-group
 
@@ -276,69 +354,91 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
-int os2d_f16x3_conv_data(const float* wt, const float* dy, float* dx, int cout, int cin, int ks, int NB, int H, int W, unsigned* words,
-                         hipStream_t stream) {
-  const int PL = os2d_plane(H, W), T2 = ks * ks, K = cout * T2;
-  int rc = clear_words(words, 1 + (size_t)NB, stream);
+// ================================================================================================ the five sites
+// Each builds its operand loaders, its store and its dimensions ONCE and hands them to the kernel of the arithmetic asked for.
+// The `vec` hints of LdRows / LdPairRows are load8's: gemm16_kernel does not read them.
+
+// C(z)[m][n] = sum over (c < creduce, tap) of a[m][(c, tap)] * b[z][c][n + off(tap)] (+ bias[m]) on the plane layout: the data
+// gradient and the forward convolution (bplanes = planes per pair of b, of which the first creduce are read)
+static int conv_planes(int arith, const float* a, const float* bias, const float* b, int bplanes, float* out, int M, int creduce, int ks,
+                       int NB, int H, int W, unsigned* words, hipStream_t stream, const char* what, const char* what_f16x3) {
+  const int PL = os2d_plane(H, W), T2 = ks * ks, K = creduce * T2;
+  const auto la = LdRows{a, K, aligned16(a) && (K & 3) == 0};
+  const auto lb = LdShifted{b, (size_t)bplanes * PL, PL, Taps{ks, ks / 2, os2d_ws(W), T2}};
+  const auto st = StPlane{out, (size_t)M * PL, PL, H, W, bias};
+  if (!arith) return gemm<false>(la, lb, st, M, PL, K, NB, 0, stream, what);
+  int rc = clear_words(words, conv_words(arith, NB), stream);
   if (rc) return rc;
-  if ((rc = absmax(SrcPlain{wt, 0}, 1, (size_t)cin * K, MaxWord{words, 1, 1}, MaxWord{nullptr, 1, 1}, stream))) return rc;
-  if ((rc = absmax(SrcPlain{dy, (size_t)cout * PL}, NB, (size_t)cout * PL, MaxWord{words + 1, 1, NB}, MaxWord{nullptr, 1, 1}, stream))) return rc;
-  const Taps tp{ks, ks / 2, os2d_ws(W), T2};
-  return gemm_f16x3<false, true>(LdRows{wt, K, aligned16(wt) && (K & 3) == 0}, LdShifted{dy, (size_t)cout * PL, PL, tp},
-                           StPlane{dx, (size_t)cin * PL, PL, H, W}, ScaleWord{words, 1, 1}, ScaleWord{words + 1, 1, NB}, cin, PL, K, NB, 0,
-                           stream, "conv data gradient (f16x3)");
+  if ((rc = absmax(SrcPlain{a, 0}, 1, (size_t)M * K, MaxWord{words, 1, 1}, MaxWord{nullptr, 1, 1}, stream))) return rc;
+  if ((rc = absmax(SrcPlain{b, (size_t)bplanes * PL}, NB, (size_t)creduce * PL, MaxWord{words + 1, 1, NB}, MaxWord{nullptr, 1, 1}, stream)))
+    return rc;
+  return gemm_f16x3<false, true>(la, lb, st, ScaleWord{words, 1, 1}, ScaleWord{words + 1, 1, NB}, M, PL, K, NB, 0, stream, what_f16x3);
 }
 
-int os2d_f16x3_conv_forward(const float* w, const float* bias, const float* x, int xplanes, float* z, int cout, int cin, int ks, int NB,
-                            int H, int W, unsigned* words, hipStream_t stream) {
-  const int PL = os2d_plane(H, W), T2 = ks * ks, K = cin * T2;
-  int rc = clear_words(words, 1 + (size_t)NB, stream);
-  if (rc) return rc;
-  if ((rc = absmax(SrcPlain{w, 0}, 1, (size_t)cout * K, MaxWord{words, 1, 1}, MaxWord{nullptr, 1, 1}, stream))) return rc;
-  // the cin planes the layer reads of the xplanes a pair has
-  if ((rc = absmax(SrcPlain{x, (size_t)xplanes * PL}, NB, (size_t)cin * PL, MaxWord{words + 1, 1, NB}, MaxWord{nullptr, 1, 1}, stream))) return rc;
-  const Taps tp{ks, ks / 2, os2d_ws(W), T2};
-  return gemm_f16x3<false, true>(LdRows{w, K, aligned16(w) && (K & 3) == 0}, LdShifted{x, (size_t)xplanes * PL, PL, tp},
-                                 StPlane{z, (size_t)cout * PL, PL, H, W, bias}, ScaleWord{words, 1, 1}, ScaleWord{words + 1, 1, NB}, cout, PL,
-                                 K, NB, 0, stream, "conv forward (f16x3)");
+int os2d_gemm_conv_data(int arith, const float* wt, const float* dy, float* dx, int cout, int cin, int ks, int NB, int H, int W,
+                        unsigned* words, hipStream_t stream) {
+  return conv_planes(arith, wt, nullptr, dy, cout, dx, cin, cout, ks, NB, H, W, words, stream, "conv data gradient",
+                     "conv data gradient (f16x3)");
 }
 
-int os2d_f16x3_conv_weight(const float* x, int xplanes, const float* dy, float* part, int cout, int cin, int ks, int NB, int H, int W,
-                           int splits, int ksplit, unsigned* words, hipStream_t stream) {
+int os2d_gemm_conv_forward(int arith, const float* w, const float* bias, const float* x, int xplanes, float* z, int cout, int cin, int ks,
+                           int NB, int H, int W, unsigned* words, hipStream_t stream) {
+  return conv_planes(arith, w, bias, x, xplanes, z, cout, cin, ks, NB, H, W, words, stream, "conv forward", "conv forward (f16x3)");
+}
+
+int os2d_gemm_conv_weight(int arith, const float* x, int xplanes, const float* dy, float* part, int cout, int cin, int ks, int NB, int H,
+                          int W, int splits, int ksplit, unsigned* words, hipStream_t stream) {
   const int PL = os2d_plane(H, W), T2 = ks * ks, N = cin * T2;
-  int rc = clear_words(words, 2, stream);
+  const auto la = LdPairRows{dy, (size_t)cout * PL, PL, aligned16(dy)};
+  const auto lb = LdPairShifted{x, (size_t)xplanes * PL, PL, Taps{ks, ks / 2, os2d_ws(W), T2}};
+  const auto st = StSlice{part, cout, N};
+  if (!arith) return gemm<true>(la, lb, st, cout, N, NB * PL, splits, ksplit, stream, "conv weight gradient");
+  int rc = clear_words(words, WEIGHT_WORDS, stream);
   if (rc) return rc;
   // both operands are reduced over every pair: one word each (x: the cin planes the layer reads of the xplanes a pair has)
   if ((rc = absmax(SrcPlain{dy, (size_t)cout * PL}, NB, (size_t)cout * PL, MaxWord{words, 1, 1}, MaxWord{nullptr, 1, 1}, stream))) return rc;
   if ((rc = absmax(SrcPlain{x, (size_t)xplanes * PL}, NB, (size_t)cin * PL, MaxWord{words + 1, 1, 1}, MaxWord{nullptr, 1, 1}, stream))) return rc;
-  const Taps tp{ks, ks / 2, os2d_ws(W), T2};
-  return gemm_f16x3<true, true>(LdPairRows{dy, (size_t)cout * PL, PL, aligned16(dy)}, LdPairShifted{x, (size_t)xplanes * PL, PL, tp},
-                          StSlice{part, cout, N}, ScaleWord{words, 1, 1}, ScaleWord{words + 1, 1, 1}, cout, N, NB * PL, splits, ksplit, stream,
-                          "conv weight gradient (f16x3)");
+  return gemm_f16x3<true, true>(la, lb, st, ScaleWord{words, 1, 1}, ScaleWord{words + 1, 1, 1}, cout, N, NB * PL, splits, ksplit, stream,
+                                "conv weight gradient (f16x3)");
 }
 
-int os2d_f16x3_corr(const float* fm, const float* rinv, const float* qp, const float* dcorr, int A, int B, int C, int HW, float* dfh,
-                    float* dq, unsigned* words, hipStream_t stream) {
-  unsigned* w_qp = words;
-  unsigned* w_fm = words + 1;
-  unsigned* w_img = words + 2;
-  unsigned* w_cls = words + 2 + A;
-  int rc = clear_words(words, 2 + (size_t)A + B, stream);
+// the words of the correlation backward: qp, the normalised image map, dcorr per image, dcorr per class
+struct CorrWords {
+  unsigned *qp, *fm, *img, *cls;
+};
+static CorrWords split_corr_words(unsigned* words, int A) { return {words, words + 1, words + 2, words + 2 + A}; }
+
+int os2d_gemm_corr_maxima(const float* dcorr, int A, int B, int HW, unsigned* words, hipStream_t stream) {
+  const CorrWords w = split_corr_words(words, A);
+  const int rc = clear_words(words, corr_words(1, A, B), stream);
   if (rc) return rc;
   // one maximum per pair of dcorr, combined per image (pair / B) and per class (pair % B) by the atomics themselves
-  if ((rc = absmax(SrcPlain{dcorr, (size_t)OS2D_K * HW}, (size_t)A * B, (size_t)OS2D_K * HW, MaxWord{w_img, B, A}, MaxWord{w_cls, 1, B}, stream)))
-    return rc;
-  if (dfh) {
-    // rows 225 .. 255 of a class operand row are zeros: reading them moves no maximum
-    if ((rc = absmax(SrcPlain{qp, (size_t)C * OS2D_QROWS}, B, (size_t)C * OS2D_QROWS, MaxWord{w_qp, 1, 1}, MaxWord{nullptr, 1, 1}, stream))) return rc;
-    rc = gemm_f16x3<false, false>(LdClassT{qp, C}, LdCorrRows{dcorr, B, HW}, StDense{dfh, C, HW}, ScaleWord{w_qp, 1, 1}, ScaleWord{w_img, 1, A}, C, HW,
-                           B * OS2D_K, A, 0, stream, "correlation backward (image, f16x3)");
-    if (rc) return rc;
-  }
-  if (dq) {
-    if ((rc = absmax(SrcImageNorm{fm, rinv, (size_t)C, (size_t)HW}, A, (size_t)C * HW, MaxWord{w_fm, 1, 1}, MaxWord{nullptr, 1, 1}, stream))) return rc;
-    rc = gemm_f16x3<true, false>(LdImageNorm{fm, rinv, C, HW}, LdCorrCols{dcorr, B, HW}, StDense{dq, C, OS2D_K}, ScaleWord{w_fm, 1, 1}, ScaleWord{w_cls, 1, B},
-                          C, OS2D_K, A * HW, B, 0, stream, "correlation backward (class, f16x3)");
-  }
-  return rc;
+  return absmax(SrcPlain{dcorr, (size_t)OS2D_K * HW}, (size_t)A * B, (size_t)OS2D_K * HW, MaxWord{w.img, B, A}, MaxWord{w.cls, 1, B}, stream);
+}
+
+int os2d_gemm_corr_image(int arith, const float* qp, const float* dcorr, int A, int B, int C, int HW, float* dfh, unsigned* words,
+                         hipStream_t stream) {
+  const auto la = LdClassT{qp, C};
+  const auto lb = LdCorrRows{dcorr, B, HW};
+  const auto st = StDense{dfh, C, HW};
+  if (!arith) return gemm<false>(la, lb, st, C, HW, B * OS2D_K, A, 0, stream, "correlation backward (image)");
+  const CorrWords w = split_corr_words(words, A);
+  // rows 225 .. 255 of a class operand row are zeros: reading them moves no maximum
+  const int rc = absmax(SrcPlain{qp, (size_t)C * OS2D_QROWS}, B, (size_t)C * OS2D_QROWS, MaxWord{w.qp, 1, 1}, MaxWord{nullptr, 1, 1}, stream);
+  if (rc) return rc;
+  return gemm_f16x3<false, false>(la, lb, st, ScaleWord{w.qp, 1, 1}, ScaleWord{w.img, 1, A}, C, HW, B * OS2D_K, A, 0, stream,
+                                  "correlation backward (image, f16x3)");
+}
+
+int os2d_gemm_corr_class(int arith, const float* fm, const float* rinv, const float* dcorr, int A, int B, int C, int HW, float* dq,
+                         unsigned* words, hipStream_t stream) {
+  const auto la = LdImageNorm{fm, rinv, C, HW};
+  const auto lb = LdCorrCols{dcorr, B, HW};
+  const auto st = StDense{dq, C, OS2D_K};
+  if (!arith) return gemm<true>(la, lb, st, C, OS2D_K, A * HW, B, 0, stream, "correlation backward (class)");
+  const CorrWords w = split_corr_words(words, A);
+  const int rc = absmax(SrcImageNorm{fm, rinv, (size_t)C, (size_t)HW}, A, (size_t)C * HW, MaxWord{w.fm, 1, 1}, MaxWord{nullptr, 1, 1}, stream);
+  if (rc) return rc;
+  return gemm_f16x3<true, false>(la, lb, st, ScaleWord{w.fm, 1, 1}, ScaleWord{w.cls, 1, B}, C, OS2D_K, A * HW, B, 0, stream,
+                                 "correlation backward (class, f16x3)");
 }

@@ -84,19 +84,45 @@ def _wgrad_splits(NB, PL):
     return max(1, min(64, (NB * PL + 4095) // 4096))
 
 
+def _corr_front_f32(lib, head, fm, corr, shape, s):
+    """The fp32 correlation front: fills ``corr``; returns (rnorm [NB,226,PLANE], sumsq), which the caller keeps to its end."""
+    A, B, C, H, W, P, PL = shape
+    sumsq = torch.empty(A * H * W, dtype=torch.float32, device=fm.device)
+    rnorm = torch.empty(A * B * 226 * PL, dtype=torch.float32, device=fm.device)
+    _lib.check(lib.os2d_fm_sumsq(_ptr(fm), _ptr(sumsq), A, C, H, W, s), "os2d_fm_sumsq")
+    _lib.check(lib.os2d_corr(_ptr(fm), _ptr(head._qp), _ptr(sumsq), _ptr(corr), _ptr(rnorm), A, B, C, H, W, s), "os2d_corr")
+    return rnorm, sumsq
+
+
+def _corr_front_f16x3(lib, head, fm, corr, shape, s):
+    """The split-fp16 correlation front: fills ``corr``; returns (the blocked rnorm, the workspace: the caller frees it)."""
+    A, B, C, H, W, P, PL = shape
+    qs = head._split_class_operand()
+    ws = torch.empty(int(lib.os2d_corr_f16x3_workspace_bytes(A, C, H, W)), dtype=torch.uint8, device=fm.device)
+    rshb = torch.empty(A * B * int(lib.os2d_shb_bytes(225, H, W)), dtype=torch.uint8, device=fm.device)
+    _lib.check(lib.os2d_corr_f16x3(_ptr(fm), _ptr(qs), _ptr(corr), _ptr(rshb), A, B, C, H, W, _ptr(ws), ws.numel(), s), "os2d_corr_f16x3")
+    return rshb, ws
+
+
+def _planes_from_shb(buf, exp, channels, out_channels, shape, s):
+    """A split-half blocked activation buffer as the fp32 planes [NB,out_channels,PLANE] the backward reads (exact)."""
+    A, B, C, H, W, P, PL = shape
+    out = torch.empty(A * B * out_channels * PL, dtype=torch.float32, device=buf.device)
+    _train_lib.check(_train_lib.load().os2d_train_planes_from_shb(_ptr(buf), _ptr(exp), A * B, channels, out_channels, H, W, _ptr(out), s),
+                     "os2d_train_planes_from_shb")
+    return out
+
+
 def _stages_f32(lib, head, fm, corr, prm, shape, s):
     """The strict-fp32 stages up to the transformation parameters: fills ``corr`` and ``prm``, returns the activations
     (rnorm [NB,226,PLANE], h1 [NB,128,PLANE], h2 [NB,64,PLANE]) as flat fp32 tensors."""
     A, B, C, H, W, P, PL = shape
-    NB, HW = A * B, H * W
+    NB = A * B
     f32 = dict(dtype=torch.float32, device=fm.device)
     w1, b1, w2, b2, w3, b3 = head.aligner.parameter_regressor.packed("f32")
-    sumsq = torch.empty(A * HW, **f32)
-    rnorm = torch.empty(NB * 226 * PL, **f32)
+    rnorm, sumsq = _corr_front_f32(lib, head, fm, corr, shape, s)
     h1 = torch.empty(NB * 128 * PL, **f32)
     h2 = torch.empty(NB * 64 * PL, **f32)
-    _lib.check(lib.os2d_fm_sumsq(_ptr(fm), _ptr(sumsq), A, C, H, W, s), "os2d_fm_sumsq")
-    _lib.check(lib.os2d_corr(_ptr(fm), _ptr(head._qp), _ptr(sumsq), _ptr(corr), _ptr(rnorm), A, B, C, H, W, s), "os2d_corr")
     for layer, src, wp, bp, dst in ((1, rnorm, w1, b1, h1), (2, h1, w2, b2, h2), (3, h2, w3, b3, prm)):
         _lib.check(lib.os2d_transform_conv(layer, _ptr(src), _ptr(wp), _ptr(bp), _ptr(dst), NB, P, H, W, s),
                    "os2d_transform_conv")
@@ -113,40 +139,30 @@ def _stages_f16x3(lib, head, fm, corr, prm, shape, s):
     A, B, C, H, W, P, PL = shape
     NB = A * B
     dev = fm.device
-    tl = _train_lib.load()
     regressor = head.aligner.parameter_regressor
     w1, b1, w2, b2, w3, b3 = regressor.packed("f16x3")
     exps = regressor.activation_exponents()
-    qs = head._split_class_operand()
     status = _lib.host_ptr(head._status_word())
 
     def shb(channels):
         return torch.empty(NB * int(lib.os2d_shb_bytes(channels, H, W)), dtype=torch.uint8, device=dev)
 
-    def planes(buf, exp, channels, out_channels):
-        out = torch.empty(NB * out_channels * PL, dtype=torch.float32, device=dev)
-        _train_lib.check(tl.os2d_train_planes_from_shb(_ptr(buf), _ptr(exp), NB, channels, out_channels, H, W, _ptr(out), s),
-                         "os2d_train_planes_from_shb")
-        return out
-
     def conv(layer, src, wp, bp, dst):
         _lib.check(lib.os2d_transform_conv_f16x3(layer, _ptr(src), _ptr(wp), _ptr(bp), _ptr(dst), NB, P, H, W, 3, status, s),
                    "os2d_transform_conv_f16x3")
 
-    ws = torch.empty(int(lib.os2d_corr_f16x3_workspace_bytes(A, C, H, W)), dtype=torch.uint8, device=dev)
-    rshb = shb(225)
-    _lib.check(lib.os2d_corr_f16x3(_ptr(fm), _ptr(qs), _ptr(corr), _ptr(rshb), A, B, C, H, W, _ptr(ws), ws.numel(), s), "os2d_corr_f16x3")
+    rshb, ws = _corr_front_f16x3(lib, head, fm, corr, shape, s)
     del ws
     h1shb = shb(128)
     conv(1, rshb, w1, b1, h1shb)
-    rnorm = planes(rshb, exps[0], 225, 226)
+    rnorm = _planes_from_shb(rshb, exps[0], 225, 226, shape, s)
     del rshb
     h2shb = shb(64)
     conv(2, h1shb, w2, b2, h2shb)
-    h1 = planes(h1shb, exps[1], 128, 128)
+    h1 = _planes_from_shb(h1shb, exps[1], 128, 128, shape, s)
     del h1shb
     conv(3, h2shb, w3, b3, prm)
-    h2 = planes(h2shb, exps[2], 64, 64)
+    h2 = _planes_from_shb(h2shb, exps[2], 64, 64, shape, s)
     del h2shb
     return rnorm, h1, h2
 
@@ -175,21 +191,14 @@ def _stages_live(lib, head, fm, corr, prm, shape, s, live, forward_precision):
     tl = _train_lib.load()
     regressor = head.aligner.parameter_regressor
     arith = TRAIN_FORWARD_PRECISIONS.index(forward_precision)
-    rnorm = torch.empty(NB * 226 * PL, **f32)
     if arith:
-        qs = head._split_class_operand()
-        ws = torch.empty(int(lib.os2d_corr_f16x3_workspace_bytes(A, C, H, W)), dtype=torch.uint8, device=dev)
-        rshb = torch.empty(NB * int(lib.os2d_shb_bytes(225, H, W)), dtype=torch.uint8, device=dev)
-        _lib.check(lib.os2d_corr_f16x3(_ptr(fm), _ptr(qs), _ptr(corr), _ptr(rshb), A, B, C, H, W, _ptr(ws), ws.numel(), s), "os2d_corr_f16x3")
+        rshb, ws = _corr_front_f16x3(lib, head, fm, corr, shape, s)
         # the exponent of the normalised correlation is a constant of the library: it does not depend on the BatchNorms
         exp0 = torch.full((225,), int(lib.os2d_rnorm_exp()), dtype=torch.int32, device=dev)
-        _train_lib.check(tl.os2d_train_planes_from_shb(_ptr(rshb), _ptr(exp0), NB, 225, 226, H, W, _ptr(rnorm), s),
-                         "os2d_train_planes_from_shb")
+        rnorm = _planes_from_shb(rshb, exp0, 225, 226, shape, s)
         del ws, rshb
     else:
-        sumsq = torch.empty(A * HW, **f32)
-        _lib.check(lib.os2d_fm_sumsq(_ptr(fm), _ptr(sumsq), A, C, H, W, s), "os2d_fm_sumsq")
-        _lib.check(lib.os2d_corr(_ptr(fm), _ptr(head._qp), _ptr(sumsq), _ptr(corr), _ptr(rnorm), A, B, C, H, W, s), "os2d_corr")
+        rnorm, sumsq = _corr_front_f32(lib, head, fm, corr, shape, s)
     src, acts, kept = rnorm, [], []
     layers = ((1, regressor.conv[0], regressor.conv[1], 128), (2, regressor.conv[3], regressor.conv[4], 64))
     for (layer, conv, bn, cout), is_live in zip(layers, live):

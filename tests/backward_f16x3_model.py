@@ -1,4 +1,4 @@
-"""CPU model of the split-fp16 ("f16x3") arithmetic of the backward GEMMs (os2d_amd/csrc_train/gemm_f16x3.hip), test
+"""CPU model of the split-fp16 ("f16x3") arithmetic of the backward GEMMs (os2d_amd/csrc_train/train_gemm.hip), test
 infrastructure only.
 
 Scale rule.  An operand's scale is 2^e with e from the fp32 bit pattern of its largest magnitude: e = 141 - biased exponent puts

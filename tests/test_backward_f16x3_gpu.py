@@ -1,5 +1,5 @@
 """GPU: the backward GEMMs of libos2d_train.so in split-fp16 ("f16x3") arithmetic - the *_ex entry points of include/os2d_train.h
-at arith = 1 (os2d_amd/csrc_train/gemm_f16x3.hip) - against the float64 models of tests/backward_model.py, on the shapes of
+at arith = 1 (os2d_amd/csrc_train/train_gemm.hip) - against the float64 models of tests/backward_model.py, on the shapes of
 tests/test_backward_stages_gpu.py (whose inputs and cached float64 references are shared), and through autograd against the CPU
 oracle on the small cases of tests/test_head_backward_gpu.py.
 
