@@ -25,11 +25,14 @@ namespace {
 
 constexpr int C3_THR = 256;
 constexpr int C3_NT = 256;          // plane cells per work-group (64 per wave = 4 blocks of 16)
-constexpr int C3_G = 8;             // 8-channel input groups (64 channels)
+constexpr Os2dLayer C3_L = os2d_layer(3);
+constexpr int C3_G = C3_L.groups;   // 8-channel input groups (64 channels)
 constexpr int C3_TAPS = 28;         // tap slots: 7 k-steps x 4
+static_assert(C3_L.ks == 5 && C3_TAPS == 2 * C3_L.steps, "the packed weights hold two taps per k-step of the table");
+static_assert(C3_L.rows == 32, "the kernel reads the weight scale of row m at packed_b[32 + m]");
 constexpr int C3_ROWS = 8;          // output rows kept in LDS (P <= 8; MFMA rows 8 .. 15 re-read rows 0 .. 7 and are dropped)
 constexpr int C3_WUNITS = C3_TAPS * 2 * C3_ROWS;   // weight units of one group kept in LDS: 448
-constexpr int C3_WG = C3_TAPS * 2 * 32;       // ... in the packed global layout (32 rows)
+constexpr int C3_WG = C3_TAPS * 2 * C3_L.rows;       // ... in the packed global layout (32 rows)
 
 #ifndef OS2D_C3_BUFS
 #define OS2D_C3_BUFS 1

@@ -364,10 +364,19 @@ int launch(const void* in, const void* wp, const float* bp, Os2dRangeFlag status
   return os2d_launched("conv f16x3");
 }
 
+// one layer of the table (os2d_common.h) with MT output rows and NI 32-column tiles per wave of a work-group: kernel size, packed rows,
+// groups and channels are the table's; SS = the k-steps of an LDS stage, whole stages being what the weights are packed to
+template <int LAYER, int MT, int NI, int TERMS = 3, bool STRIP = false>
+int launch_layer(const void* in, const void* wp, const float* bp, Os2dRangeFlag status, void* out, int NB, int H, int W, hipStream_t stream) {
+  constexpr Os2dLayer L = os2d_layer(LAYER);
+  constexpr int SS = LAYER == 1 ? 5 : 7, STEPS = (L.ks * L.ks + 1) / 2;
+  static_assert((STEPS + SS - 1) / SS * SS == L.steps, "the packed k-steps of a group are whole LDS stages");
+  return launch<L.ks, L.rows, MT, 1, 4, NI, SS, true, TERMS, 0, 2, STRIP>(in, wp, bp, status, out, NB, L.groups, L.cout, H, W, stream);
+}
+
 }  // namespace
 
-// layer 1: 7x7, 29 input groups (225 ch), 128 out;  layer 2: 5x5, 16 groups, 64 out; both write SHB.  Layer 3 is forwarded to
-// its own kernel (conv3_f16x3.hip).
+// layers 1 and 2 of the table write SHB.  Layer 3 is forwarded to its own kernel (conv3_f16x3.hip).
 //
 // Small grids (a handful of classes: fewer work-groups of the standard shape than 1.5 per CU) use finer work-groups -
 // 128 positions instead of 256 and 32 output channels per group - so that a call with ONE class (the reference's own
@@ -378,23 +387,12 @@ int os2d_launch_conv_f16x3(int layer, const void* in, const void* wp, const floa
                            int P, int H, int W, int terms, hipStream_t stream) {
   // the last layer has its own kernel (16-row MFMA, conv3_f16x3.hip), one shape for every batch size
   if (layer == 3) return os2d_launch_conv3_f16x3(in, wp, bp, out, NB, P, H, W, stream);
+  if (layer != 1 && layer != 2) return OS2D_REFUSE(-1, "os2d_launch_conv_f16x3: bad layer %d", layer);
   if (layer == 2 && W > OS2D_MAX_W_LINEAR5)      // wider than the linear slab takes: column strips, one shape for every batch size
-    return launch<5, 64, 64, 1, 4, 2, 7, true, 3, 0, 2, true>(in, wp, bp, status, out, NB, 16, 64, H, W, stream);
+    return launch_layer<2, 64, 2, 3, true>(in, wp, bp, status, out, NB, H, W, stream);
   const long long std_groups = (long long)((H * os2d_ws(W) + 255) / 256) * NB;
-  if (std_groups * (layer == 1 ? 2 : 1) < 384) {  // measured crossover at 60x80: finer shapes win up to 9 classes
-    if (layer == 1 && terms == 2)
-      return launch<7, 128, 32, 1, 4, 1, 5, true, 2>(in, wp, bp, status, out, NB, 29, 128, H, W, stream);
-    switch (layer) {
-      case 1: return launch<7, 128, 32, 1, 4, 1, 5, true>(in, wp, bp, status, out, NB, 29, 128, H, W, stream);
-      case 2: return launch<5, 64, 32, 1, 4, 1, 7, true>(in, wp, bp, status, out, NB, 16, 64, H, W, stream);
-      default: break;
-    }
-  }
-  if (layer == 1 && terms == 2)
-    return launch<7, 128, 64, 1, 4, 2, 5, true, 2>(in, wp, bp, status, out, NB, 29, 128, H, W, stream);
-  switch (layer) {
-    case 1: return launch<7, 128, 64, 1, 4, 2, 5, true>(in, wp, bp, status, out, NB, 29, 128, H, W, stream);
-    case 2: return launch<5, 64, 64, 1, 4, 2, 7, true>(in, wp, bp, status, out, NB, 16, 64, H, W, stream);
-    default: os2d_set_error("os2d_launch_conv_f16x3: bad layer %d", layer); return -1;
-  }
+  const bool fine = std_groups * (layer == 1 ? 2 : 1) < 384;  // measured crossover at 60x80: finer shapes win up to 9 classes
+  if (layer == 2) return fine ? launch_layer<2, 32, 1>(in, wp, bp, status, out, NB, H, W, stream) : launch_layer<2, 64, 2>(in, wp, bp, status, out, NB, H, W, stream);
+  if (terms == 2) return fine ? launch_layer<1, 32, 1, 2>(in, wp, bp, status, out, NB, H, W, stream) : launch_layer<1, 64, 2, 2>(in, wp, bp, status, out, NB, H, W, stream);
+  return fine ? launch_layer<1, 32, 1>(in, wp, bp, status, out, NB, H, W, stream) : launch_layer<1, 64, 2>(in, wp, bp, status, out, NB, H, W, stream);
 }

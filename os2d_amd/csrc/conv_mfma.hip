@@ -229,20 +229,25 @@ int launch(const float* in, const float* wp, const float* bp, float* out, int NB
   return os2d_launched("conv");
 }
 
+// one layer of the table (os2d_common.h): layer 1 in stages of one kernel row on 2 x 2 waves, the 5x5 layers in one stage per channel
+// pair on 1 x 4; layers 1 and 2 +ReLU, plane out; layer 3 (rows padded to 32 in the packed weights) compact [NB][P][H*W] out
+template <int LAYER, bool STRIP = false>
+int launch_layer(const float* in, const float* wp, const float* bp, float* out, int NB, int P, int H, int W, hipStream_t stream) {
+  constexpr Os2dLayer L = os2d_layer(LAYER);
+  constexpr bool first = LAYER == 1, last = LAYER == 3;
+  return launch<L.ks, first ? 1 : L.ks, L.rows, first ? 2 : 1, first ? 2 : 4, !last, last, STRIP>(in, wp, bp, out, NB, L.planes(), last ? P : L.cout, H, W,
+                                                                                             stream);
+}
+
 }  // namespace
 
-// layer 1: 7x7 225(226)->128 +ReLU, plane out; layer 2: 5x5 128->64 +ReLU, plane out;
-// layer 3: 5x5 64->P (rows padded to 32 in the packed weights), compact [NB][P][H*W] out.
 int os2d_launch_conv(int layer, const float* in, const float* wp, const float* bp, float* out, int NB, int P, int H,
                      int W, hipStream_t stream) {
-  if (layer != 1 && W > OS2D_MAX_W_LINEAR5) {     // wider than the linear slab takes: column strips
-    if (layer == 2) return launch<5, 5, 64, 1, 4, true, false, true>(in, wp, bp, out, NB, 128, 64, H, W, stream);
-    if (layer == 3) return launch<5, 5, 32, 1, 4, false, true, true>(in, wp, bp, out, NB, 64, P, H, W, stream);
-  }
+  const bool strips = W > OS2D_MAX_W_LINEAR5;     // wider than the linear slab of a 5x5 layer takes: column strips
   switch (layer) {
-    case 1: return launch<7, 1, 128, 2, 2, true, false>(in, wp, bp, out, NB, OS2D_KP, 128, H, W, stream);
-    case 2: return launch<5, 5, 64, 1, 4, true, false>(in, wp, bp, out, NB, 128, 64, H, W, stream);
-    case 3: return launch<5, 5, 32, 1, 4, false, true>(in, wp, bp, out, NB, 64, P, H, W, stream);
-    default: os2d_set_error("os2d_launch_conv: bad layer %d", layer); return -1;
+    case 1: return launch_layer<1>(in, wp, bp, out, NB, P, H, W, stream);
+    case 2: return strips ? launch_layer<2, true>(in, wp, bp, out, NB, P, H, W, stream) : launch_layer<2>(in, wp, bp, out, NB, P, H, W, stream);
+    case 3: return strips ? launch_layer<3, true>(in, wp, bp, out, NB, P, H, W, stream) : launch_layer<3>(in, wp, bp, out, NB, P, H, W, stream);
+    default: return OS2D_REFUSE(-1, "os2d_launch_conv: bad layer %d", layer);
   }
 }

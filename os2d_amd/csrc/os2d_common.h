@@ -34,6 +34,24 @@
 #define OS2D_RNORM_EXP 12    // the relu+L2-normalised correlation (|x| <= 1) is stored as fp16 hi|lo of x * 2^12
 #define OS2D_STATUS_F16_RANGE 1  // sticky status bit: a split-fp16 activation left the fp16 range (non-finite input)
 
+// The three layers of the TransformNet (reference head.py:612-629), the ONE place their geometry is written: the packing and size
+// entry points, the head call, the host launch tables of conv_mfma.hip / conv_f16x3.hip / conv3_f16x3.hip and the training
+// library read it; a kernel that keeps a constant of its own ties it to the table with a static_assert.
+struct Os2dLayer {
+  int cout, cin, ks;  // layer 3: cout = P (6 or 4)
+  int rows;           // output rows of the packed weights and of each third of the packed bias: cout padded
+  int groups;         // 8-channel groups of the input (split-half blocked activations, split-fp16 weights)
+  int steps;          // split-fp16 packing: k-steps (two taps each) of one group, padded to whole LDS stages of conv_f16x3.hip
+                      // (layer 1: 5 stages of 5, layer 2: 2 of 7) / to the 7 four-tap steps of conv3_f16x3.hip
+  constexpr int planes() const { return (cin + 1) / 2 * 2; }  // channels of the fp32 input buffer: whole pairs (layer 1: OS2D_KP)
+};
+constexpr Os2dLayer os2d_layer(int layer /* 1 .. 3 */, int P = 6) {
+  return layer == 1 ? Os2dLayer{128, OS2D_K, 7, 128, OS2D_G, 25} : layer == 2 ? Os2dLayer{64, 128, 5, 64, 16, 14} : Os2dLayer{P, 64, 5, 32, 8, 14};
+}
+static_assert(os2d_layer(1).planes() == OS2D_KP && os2d_layer(1).groups == (OS2D_K + 7) / 8 && os2d_layer(2).groups * 8 == os2d_layer(2).cin &&
+                  os2d_layer(3).groups * 8 == os2d_layer(3).cin && os2d_layer(2).cin == os2d_layer(1).cout && os2d_layer(3).cin == os2d_layer(2).cout,
+              "layer table");
+
 // Where a split-fp16 kernel reports an activation outside the fp16 range / a non-finite input, and WHAT it stores there.
 // Per-stage entry points: the caller's word, value OS2D_STATUS_F16_RANGE.  os2d_head_forward_ex: a word of the call's
 // workspace and the call's EPOCH - sample_decode_kernel, the last kernel of the call, compares the words with the epoch and

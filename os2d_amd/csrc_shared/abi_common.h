@@ -24,6 +24,8 @@ static inline int os2d_refuse(const char* text) {
   os2d_set_error("%s", text);
   return -1;
 }
+// a failed check in one statement: the formatted text becomes the thread's last error, the value is `rc`
+#define OS2D_REFUSE(rc, ...) (os2d_set_error(__VA_ARGS__), (rc))
 
 #ifndef OS2D_HOST_EMU
 #include <hip/hip_runtime.h>
