@@ -7,6 +7,14 @@
  * Packing: detections of image n are rows det_offsets[n] .. det_offsets[n+1]-1 of boxes[D][4] (xmin, ymin, xmax, ymax, fp32),
  * scores[D] (fp32), labels[D] (int32); ground truth likewise with gt_offsets[N+1], gt_labels[G] (int32) and
  * gt_difficult[G] (uint8).  Labels lie in [0, L).
+ *
+ * Labels outside [0, L) are tolerated, not validated (that would need a synchronisation): such a ground-truth box is not
+ * counted; such a detection is filed BEHIND every class in the per-class ordering, so the numbers of the classes 0 .. L-1
+ * are those of the same call without it, and it stays in the joint ordering.  The match step has no L and only compares
+ * labels: such a detection can match only a ground-truth box of the same out-of-range label (which count_gt did not
+ * count); with ground-truth labels in range it matches nothing (match 0) and is a false positive of the joint class.
+ * Boxes whose area under the +1 convention is not positive (xmax + 1 <= xmin) give a NaN or negative IoU and are outside
+ * the contract.
  */
 #ifndef OS2D_EVAL_H
 #define OS2D_EVAL_H
@@ -34,15 +42,19 @@ int os2d_eval_match(const float* det_boxes, const float* det_scores, const int* 
 
 /* Stable sorts of the detection indices: perm_joint[D] by descending score, perm_class[D] by (label, descending score);
  * ties keep increasing index.  sorted_labels[D] = labels[perm_class], class_offsets[L+1] = first position of every label in
- * it.  label_bits: bits needed for L - 1. */
+ * it.  label_bits: bits needed for L - 1; more are allowed and change nothing.  A detection whose label is outside [0, L)
+ * is sorted with the key L: those rows are the positions class_offsets[L] .. D-1 of perm_class, in descending score, and
+ * sorted_labels holds L there (so class_offsets[L] is the number of detections with a label in range).  D = 0 zeroes
+ * class_offsets and touches nothing else.  The workspace holds nothing the caller may rely on afterwards. */
 size_t os2d_eval_sort_workspace_bytes(int D);
 int os2d_eval_sort(const float* det_scores, const int* det_labels, int D, int L, int label_bits, unsigned int* perm_joint,
                    unsigned int* perm_class, int* sorted_labels, int* class_offsets, void* workspace, size_t workspace_bytes,
                    void* stream);
 
-/* Precision / recall curves of one ordering.  seg: the label of every position (sorted_labels), or NULL for one segment of
- * all D positions; n_pos / rec_last are indexed by that label (index 0 when seg is NULL).  tpfp[D] (uint64, tp in the high
- * word) may be NULL.  rec_last[s] receives the last recall of a segment; entries of segments without positions are left. */
+/* Precision / recall curves of one ordering.  seg: the label of every position (sorted_labels), non-decreasing, any int
+ * (a label outside [0, L), -1 included, has n_pos 0 and no rec_last / acc entry), or NULL for one segment of all D
+ * positions; n_pos / rec_last are indexed by that label (index 0 when seg is NULL).  tpfp[D] (uint64, tp in the high word)
+ * may be NULL.  rec_last[s] receives the last recall of a segment; entries of segments without positions are left. */
 size_t os2d_eval_scan_workspace_bytes(int D);
 int os2d_eval_prec_rec(const signed char* match, const unsigned int* perm, const int* seg, const int* n_pos, int L, int D,
                        unsigned long long* tpfp, double* prec, double* rec, double* rec_last, void* workspace,

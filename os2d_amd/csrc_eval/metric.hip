@@ -76,7 +76,9 @@ template <class P, bool STORE>
 __device__ __forceinline__ Seg<typename P::T> tile_scan(const P& p, int D, typename P::T carry) {
   typedef typename P::T T;
   const long long first = (long long)blockIdx.x * EVAL_TILE + (long long)threadIdx.x * EVAL_ITEMS;
-  int s[EVAL_ITEMS + 2];   // segment of the positions first-1 .. first+EVAL_ITEMS (-1 outside the array)
+  // segment of the positions first-1 .. first+EVAL_ITEMS.  Outside the array the value is a filler that decides nothing: the
+  // first position is a head and the last a tail by their index, so a segment may carry any label, -1 included.
+  int s[EVAL_ITEMS + 2];
 #pragma unroll
   for (int k = 0; k < EVAL_ITEMS + 2; ++k) {
     const long long i = first - 1 + k;
@@ -91,7 +93,7 @@ __device__ __forceinline__ Seg<typename P::T> tile_scan(const P& p, int D, typen
   for (int k = 0; k < EVAL_ITEMS; ++k) {
     const long long i = first + k;
     if (i < D) {
-      const bool head = s[k + 1] != s[k];
+      const bool head = i == 0 || s[k + 1] != s[k];
       const T x = p.load((int)(P::REV ? D - 1 - i : i), head);
       run.v = head ? x : P::op(run.v, x);
       run.f |= head ? 1 : 0;
@@ -107,7 +109,7 @@ __device__ __forceinline__ Seg<typename P::T> tile_scan(const P& p, int D, typen
 #pragma unroll
     for (int k = 0; k < EVAL_ITEMS; ++k) {
       const long long i = first + k;
-      if (i < D) p.store((int)(P::REV ? D - 1 - i : i), own[k] ? v[k] : P::op(ex.v, v[k]), s[k + 2] != s[k + 1], s[k + 1]);
+      if (i < D) p.store((int)(P::REV ? D - 1 - i : i), own[k] ? v[k] : P::op(ex.v, v[k]), i == D - 1 || s[k + 2] != s[k + 1], s[k + 1]);
     }
   }
   return total;

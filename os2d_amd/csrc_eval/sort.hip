@@ -1,8 +1,9 @@
 // VOC evaluation, step 2 (gfx950): a stable LSD radix sort of (key, index) pairs with 8-bit digits, over all D detections.
 //
-// Four passes over os2d_score_key give the joint-classes order (descending score), ceil(label_bits / 8) further passes over
-// the label give the per-class order; equal keys keep increasing index (image order, then index within the image) because
-// every pass is stable.  Neither order depends on an IoU threshold.
+// Four passes over os2d_score_key give the joint-classes order (descending score), further passes over the label key give the
+// per-class order; equal keys keep increasing index (image order, then index within the image) because every pass is stable.
+// Neither order depends on an IoU threshold.  The label key of a label outside [0, L) is L: such rows sort behind every
+// class, in descending score, so the passes cover the bits of L (and label_bits, if the caller asks for more).
 //
 // One pass = radix_hist_kernel (digit histogram of a tile of EVAL_TILE keys in LDS, stored digit-major), radix_scan_kernel
 // (exclusive scan of the 256 x tiles counts: one work-group, 4096 counts per round) and radix_scatter_kernel.  In the scatter
@@ -23,10 +24,13 @@ __global__ __launch_bounds__(EVAL_THREADS) void sort_init_kernel(const float* __
   idx[i] = (u32)i;
 }
 
-__global__ __launch_bounds__(EVAL_THREADS) void gather_labels_kernel(const int* __restrict__ labels, const u32* __restrict__ perm, int D,
+// label key: the label, or L for a label outside [0, L) - low digits alone would file label 256 among those of label 0
+__global__ __launch_bounds__(EVAL_THREADS) void gather_labels_kernel(const int* __restrict__ labels, const u32* __restrict__ perm, int D, int L,
                                                                       u32* __restrict__ keys) {
   const int i = blockIdx.x * EVAL_THREADS + threadIdx.x;
-  if (i < D) keys[i] = (u32)labels[perm[i]];
+  if (i >= D) return;
+  const u32 l = (u32)labels[perm[i]];
+  keys[i] = l < (u32)L ? l : (u32)L;
 }
 
 __global__ __launch_bounds__(EVAL_THREADS) void radix_hist_kernel(const u32* __restrict__ keys, int D, int shift, u32* __restrict__ hist, int ntiles) {
@@ -201,9 +205,11 @@ int os2d_eval_sort(const float* det_scores, const int* det_labels, int D, int L,
   if (int rc = radix_pass(key_a, idx_a, key_b, idx_b, D, 16, hist, st)) return rc;
   if (int rc = radix_pass(key_b, idx_b, key_a, perm_joint, D, 24, hist, st)) return rc;
   // label: starts from the joint order, so equal labels stay in descending score
-  hipLaunchKernelGGL(gather_labels_kernel, flat, dim3(EVAL_THREADS), 0, st, det_labels, perm_joint, D, key_a);
+  hipLaunchKernelGGL(gather_labels_kernel, flat, dim3(EVAL_THREADS), 0, st, det_labels, perm_joint, D, L, key_a);
   if (int rc = os2d_launched("gather_labels_kernel")) return rc;
-  const int passes = label_bits <= 8 ? 1 : (label_bits + 7) / 8;
+  int key_bits = label_bits;   // the largest key is L, not L - 1
+  while (key_bits < 31 && ((u32)L >> key_bits) != 0) ++key_bits;
+  const int passes = key_bits <= 8 ? 1 : (key_bits + 7) / 8;
   const u32* kin = key_a;
   const u32* iin = perm_joint;
   for (int p = 0; p < passes; ++p) {

@@ -20,6 +20,12 @@ sort.
 Labels are non-negative integers below ``num_labels``.  The arrays have length ``num_labels``; when it is not given it is
 the reference's "largest label seen + 1", which needs the largest detection label from the device (one synchronisation).
 Labels that were never seen have AP NaN and ``prec`` / ``rec`` None, so a larger ``num_labels`` changes no scalar.
+
+Detection labels live on the device and are not validated.  A detection whose label is outside ``[0, num_labels)`` (a
+``num_labels`` that is too small) can match only a ground-truth box of the same label - none when the ground-truth labels
+are in range, which host-side ground truth is checked for; it then counts as a false positive of the joint class - and is sorted
+behind every class with the key ``num_labels`` (``sorted_labels`` holds ``num_labels`` for those rows, and
+``class_offsets[num_labels]`` is the number of detections in range): the per-class numbers are those without it.
 """
 import ctypes
 
