@@ -30,10 +30,12 @@
 // per lane, 32 consecutive units per half-wave (conflict-free), lanes 32 - 63 take the next k group.  The constant matrices
 // (FqT, Fp2, E2, Gq: functions of (P, Q) only) are built once per transform size by dft_matrices_kernel from float64 tables.
 //
-// Scales (all powers of two; exact): x * 2^15 (x <= 1), DFT matrices * 2^14 (Gq: 2^13, its entries reach 2), the row
-// spectrum R * 2^8 (|R| <= window width <= 96), forward output X = acc * 2^-22; inverse: every image's spectrum is scaled by
-// its own power of two that puts its largest |component| into [2^13, 2^14) (the dynamic range of Y is far larger than that of
-// the rigorous bound), T * 2^-(14 + ceil(log2 P) + 1), output = acc * 2^(ceil(log2 P) + 1 - 13) / (scale * P * Q).
+// Scales (all powers of two; exact; the exponents are the constants DFT_E* of dft_plan.h, every factor below an expression of
+// them): x * 2^DFT_EX = 2^15 (x <= 1), DFT matrices * 2^DFT_EF = 2^14 (Gq: 2^DFT_EGQ = 2^13, its entries reach 2), the row
+// spectrum R * 2^DFT_ER = 2^8 (|R| <= window width <= 96), forward output X = acc * 2^-(DFT_ER + DFT_EF) = 2^-22; inverse: every
+// image's spectrum is scaled by its own power of two that puts its largest |component| into [2^DFT_EY, 2^(DFT_EY + 1)) =
+// [2^13, 2^14) (the dynamic range of Y is far larger than that of the rigorous bound), T * 2^-(DFT_EF + eT), eT =
+// ceil(log2 P) + 1, output = acc * 2^(eT - DFT_EGQ) / (scale * P * Q).
 //
 // Radix 2 in the column direction of the FORWARD transform for P = 64 (the instantiations with 8 k-steps: every plan with
 // Pp = 64 has P = 64, see dft_plan_transform).  One decimation step makes the dense 64-point matrix block-diagonal:
@@ -58,9 +60,7 @@
 #error "the includer defines DFT_DEV, DFT_TID, DFT_BID, DFT_GRID, DFT_LDS, DFT_BARRIER, DFT_MFMA, DFT_SHFL_XOR, DFT_SHFL_XOR_U32, DFT_BALLOT, DFT_FLAG, DFT_FLAG_SET, DFT_RAISE, DFT_UNIFORM"
 #endif
 
-#ifndef DFT_HD
-#define DFT_HD static inline      /* host + device helpers (the device build says __host__ __device__) */
-#endif
+/* (DFT_HD, host + device helpers - the device build says __host__ __device__: its default is in dft_plan.h) */
 #ifndef DFT_MEMBER
 #define DFT_MEMBER inline         /* member functions (the device build says __device__ __forceinline__) */
 #endif
@@ -97,231 +97,11 @@
 #endif
 
 #include "tile_common.h"
+#include "dft_plan.h"      // what the host decides, and what planner and kernels share: plan, LDS layout, capacity, scales
 
 namespace os2d_dft {
 
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));      // 4 floats at any float address (one dwordx4 load)
-
-constexpr int DFT_THR = 512, DFT_WAVES = 8;
-constexpr int DFT_G = 4;            // images per work-group iteration
-constexpr int DFT_MAXP = 64;        // transform rows (P <= 64: the 2P rows of step 2 / step A are at most four 32-row tiles)
-constexpr int DFT_MAXV = 48;        // half-spectrum columns (2V <= 96: three 32-column tiles; Q <= 94)
-constexpr int DFT_MAXWK = 96;       // window columns rounded up to 16
-constexpr int DFT_KREG = 8;         // k-steps of the register-resident operand (2 * Pp / 16 <= 8)
-// output forms of the inverse kernel (its ``zero_borders`` argument): split-fp16 activation units, the same + the zero border
-// cells of the planes, or fp32 channel planes [pair][channel][H * W] scaled to <= 1 - what the forward kernel reads
-constexpr int DFT_OUT_SHB = 0, DFT_OUT_SHB_BORDERS = 1, DFT_OUT_PLANES = 2;
-
-struct DftPlan {
-  int H, W;                        // map
-  int P, Q, V, NBINS;              // transform size, V = Q/2 + 1; bins = v * P + u padded to a multiple of 8
-  int T, TY, TX, TH, TW;           // overlap-save tiles (T = TY * TX = 1: the whole map in one transform)
-  int oy, ox;                      // 3 along a tiled axis (window starts 3 cells before the tile; outputs sit at offset 3), else 0
-  int LH, LW;                      // rows / columns of the window a tile loads (TH + 6 | H, TW + 6 | W)
-  int RH;                          // rows of the inverse that are needed (oy + TH | H)
-  int Pp;                          // P rounded up to 8: rows of a window in the operand arrays (k of step 2 / step A = 2 * Pp)
-  int Wk;                          // LW rounded up to 16: k of step 1
-  int N1;                          // 2 V rounded up to 32: columns of step 1
-  int M2;                          // 2 P rounded up to 32: rows of step 2
-  int Mx;                          // G * Pp rounded up to 32: rows of step 1 = (img, h)
-  int N2;                          // G * V rounded up to 32: columns of step 2 / step A = (img, v)
-  int MA;                          // 2 * RH rounded up to 32: rows of step A = (h, re | im)
-  int MB;                          // G * (MA / 2) : rows of step B = (h, img)
-  int KB;                          // 2 V rounded up to 16: k of step B
-  int NBo;                         // columns of step B that are needed (ox + TW | W) rounded up to 32
-  int G;                           // images per work-group iteration of both kernels: 4, or 8 for the small transforms (dft_plan_g8)
-  int eT;                          // ceil(log2 P) + 1
-  int fast;                        // 1: W % 4 == 0 and untiled (16-byte loads of the correlation rows)
-  unsigned inv_cg, inv_t, inv_tx, inv_c4, inv_v, inv_pq, inv_og, inv_kg, inv_pp;   // ceil(2^32 / d) (0 where d == 1)
-  // LDS (bytes)
-  int lds_const, lds_union, lds_total;
-};
-
-DFT_HD int dft_round_up(int x, int m) { return (x + m - 1) / m * m; }
-DFT_HD unsigned dft_magic(unsigned d) { return d > 1 ? (unsigned)(((1ull << 32) + d - 1) / d) : 0u; }
-
-// sizes of the constant operand arrays of a (P, Q) transform, in 16-byte units: they depend on P and Q only, so every map
-// (and every tiling) that uses the transform shares them
-DFT_HD int dft_units_fqt(int P, int Q) { return (dft_round_up(Q, 16) / 8) * 2 * dft_round_up(Q + 2, 32); }
-// P = 64 (radix 2 in the forward kernel): Fp2 is a block of DFT_R2_MATU units - the 64 x 32 real matrix of the 32-point transform
-// [k group = 4][hi|lo][64 rows: cos | sin] in its first half, zeros behind it - followed by DFT_R2_TWU units of twiddles:
-// float [32][re|im] = exp(-2 pi i u / 64)
-constexpr int DFT_R2_P = 64, DFT_R2_MATU = 8 * 2 * 64, DFT_R2_TWU = 16;
-// the 1024 bytes behind the union region of LDS (lds_total): the inverse kernel keeps its per-image maxima in the first 256, the
-// forward kernel of the 64-row transform its twiddles (DFT_R2_TWU units = 256 bytes) from this offset
-constexpr int DFT_R2_LDS_TW = 512;
-DFT_HD bool dft_radix2(int P) { return P == DFT_R2_P; }
-DFT_HD int dft_units_fp2(int P, int Q) {
-  return dft_radix2(P) ? DFT_R2_MATU + DFT_R2_TWU : (2 * dft_round_up(P, 8) / 8) * 2 * dft_round_up(2 * P, 32);
-}
-DFT_HD int dft_units_e2(int P, int Q) { return (2 * dft_round_up(P, 8) / 8) * 2 * dft_round_up(2 * P, 32); }
-DFT_HD int dft_units_gq(int P, int Q) { return (dft_round_up(Q + 2, 16) / 8) * 2 * dft_round_up(Q, 32); }
-DFT_HD size_t dft_matrices_units(int P, int Q) {
-  return (size_t)dft_units_fqt(P, Q) + dft_units_fp2(P, Q) + dft_units_e2(P, Q) + dft_units_gq(P, Q);
-}
-
-// plan of ONE transform: window LH x LW -> P x Q, RH rows of the inverse needed, NBo output columns needed
-static inline bool dft_plan_transform(int LH, int LW, int RH, int ncols, int minP, int minQ, int G, DftPlan* pl) {
-  pl->G = G;
-  pl->P = dft_round_up(minP, 4);
-  // 60 rows pad to the operand arrays of 64 (Pp) anyway and would be the only other size with 8 k-steps in step 2 / step A: it
-  // takes the 64-row transform, so that 8 k-steps always mean the radix-2 product (7 % more bins under the "exact" policy only)
-  if (pl->P == 60) pl->P = DFT_R2_P;
-  pl->Q = dft_round_up(minQ, 2);
-  pl->V = pl->Q / 2 + 1;
-  pl->NBINS = dft_round_up(pl->P * pl->V, 8);
-  pl->LH = LH;
-  pl->LW = LW;
-  pl->RH = RH;
-  pl->Pp = dft_round_up(pl->P, 8);
-  pl->Wk = dft_round_up(LW, 16);
-  pl->N1 = dft_round_up(2 * pl->V, 32);
-  pl->M2 = dft_round_up(2 * pl->P, 32);
-  pl->Mx = dft_round_up(G * pl->Pp, 32);
-  pl->N2 = dft_round_up(G * pl->V, 32);
-  pl->MA = dft_round_up(2 * RH, 32);
-  pl->MB = G * (pl->MA / 2);
-  pl->KB = dft_round_up(2 * pl->V, 16);
-  pl->NBo = dft_round_up(ncols, 32);
-  int e = 0;
-  while ((1 << e) < pl->P) ++e;
-  pl->eT = e + 1;
-  if (pl->P > DFT_MAXP || pl->V > DFT_MAXV || pl->Wk > DFT_MAXWK || LH > pl->P || LW > pl->Q || RH > pl->P) return false;
-  // LDS: constants FqT | Gq are resident (whichever kernel runs takes its own: the larger decides the common figure);
-  // the union region holds, one after the other, x | R2 | X staging (forward) and Y2 | Tt (inverse)
-  const int fqt = (pl->Wk / 8) * 2 * pl->N1 * 16, gq = (pl->KB / 8) * 2 * pl->NBo * 16;
-  const int x = (pl->Wk / 8) * 2 * (pl->Mx + 1) * 16, r2 = (2 * pl->Pp / 8) * 2 * (pl->N2 + 1) * 16;
-  const int xs = pl->V * (pl->P * 8 * G + 16);
-  const int y2 = r2, tt = (pl->KB / 8) * 2 * (pl->MB + 1) * 16;
-  int u = x;
-  if (r2 > u) u = r2;
-  if (xs > u) u = xs;
-  if (y2 > u) u = y2;
-  if (tt > u) u = tt;
-  if (G == 8) {
-    if (dft_radix2(pl->P)) return false;      // (the 64-row transform keeps its half-size matrix in registers: 4 images)
-    // EIGHT images per iteration (round 6): the fixed phases of an iteration - six barriers, the fill and drain of
-    // four products, the burst of the next window's requests - do not shrink with the transform, so the small transforms of the
-    // pyramid paid 1.3 - 1.9x per location.  With 8 images the products have 20 - 24 tiles (three per wave: the tile grids of
-    // step 2 / step A no longer match the fixed "row tile in registers" ownership, so Fp2 / E2 live in LDS next to FqT / Gq
-    // and every product takes the LDS-LDS path), the inverse kernel owns all 8 channels of an activation unit and writes whole
-    // 16-byte units.  Fits the transforms up to 48 x 62.
-    const int fp2 = (2 * pl->Pp / 8) * 2 * pl->M2 * 16;      // = the size of E2 (MAfull = M2 rows)
-    const int ca = fqt + fp2, cb = gq + fp2;
-    pl->lds_const = ca > cb ? ca : cb;
-    pl->lds_union = dft_round_up(u, 256);
-    pl->lds_total = pl->lds_const + pl->lds_union + 1024;
-    const int t1 = (pl->Mx / 32) * (pl->N1 / 32), t2 = (pl->M2 / 32) * (pl->N2 / 32), tA = (pl->MA / 32) * (pl->N2 / 32),
-              tB = (pl->MB / 32) * (pl->NBo / 32);
-    const int npos = pl->Pp * (pl->Wk / 4), nitem = G * pl->V * (pl->Pp / 8);
-    return pl->lds_total <= 160 * 1024 && t1 <= 24 && t2 <= 24 && tA <= 24 && tB <= 24 && npos <= 2 * DFT_THR && nitem <= 3 * DFT_THR;
-  }
-  pl->lds_const = fqt > gq ? fqt : gq;
-  pl->lds_union = dft_round_up(u, 256);
-  pl->lds_total = pl->lds_const + pl->lds_union + 1024;      // + per-image maxima / scales (inverse) | twiddles at DFT_R2_LDS_TW (forward, P = 64)
-  return pl->lds_total <= 160 * 1024;
-}
-
-static inline void dft_set_tiles(DftPlan* pl, int H, int W, int TY, int TX, int TH, int TW) {
-  pl->H = H;
-  pl->W = W;
-  pl->TY = TY;
-  pl->TX = TX;
-  pl->T = TY * TX;
-  pl->TH = TH;
-  pl->TW = TW;
-  pl->oy = TY > 1 ? 3 : 0;
-  pl->ox = TX > 1 ? 3 : 0;
-  pl->fast = (pl->T == 1 && (W & 3) == 0) ? 1 : 0;
-  pl->inv_t = dft_magic((unsigned)pl->T);
-  pl->inv_tx = dft_magic((unsigned)TX);
-  pl->inv_c4 = dft_magic((unsigned)(pl->Wk / 4));
-  pl->inv_v = dft_magic((unsigned)pl->V);
-  pl->inv_pq = dft_magic((unsigned)(pl->P / 4 * pl->G * 2));
-  pl->inv_kg = dft_magic((unsigned)(pl->Pp / 8));
-  pl->inv_pp = dft_magic((unsigned)pl->Pp);
-}
-
-// Transform sizes.  The weight spectra of the per-bin GEMM cost 0.24 MB per bin and transform size (654 MB for 64 x 84), and a
-// dataset fed at its own aspect ratios and 7 pyramid scales meets hundreds of map sizes (reference os2d/data/dataloader.py:326,
-// os2d/config.py:194).  Since every map can be cut into overlap-save tiles, the planner may restrict itself to a handful of
-// CANONICAL sizes and pay in bins instead of in resident spectra (35.6 GB cached for 52 FFT-friendly sizes):
-//   policy 1 (default)  the six sizes below - the exact transforms of the 7-scale pyramid of a 1280 x 960 image (levels 30x40 ..
-//                       60x80 whole, 72x96 / 84x112 / 96x128 as 2 x 2 tiles): 10,220 bins = 2.4 GB of weight spectra in total
-//   policy 0            any P % 4 == 0, even Q: the smallest transform per map (fewest bins; one set of spectra per size)
-// $OS2D_DFT_SIZES = canonical | exact selects it for the process (read once).
-struct DftSize {
-  int P, Q;
-};
-static const DftSize DFT_CANONICAL[6] = {{36, 46}, {44, 54}, {48, 62}, {52, 68}, {56, 70}, {64, 84}};
-
-// The whole map in one transform when it fits (P >= H + 3, Q >= W + 3: the zero padding is the halo), otherwise the tiling
-// with the fewest bins in total; an axis is either untiled or cut into >= 2 tiles of ceil(n / k) outputs whose window is 6
-// longer.
-static inline bool dft_make_plan_policy(int H, int W, int canonical, DftPlan* out, int G = DFT_G) {
-  bool found = false;
-  long best = 0;
-  for (int TY = 1; TY <= 48; ++TY)
-    for (int TX = 1; TX <= 48; ++TX) {
-      const int TH = (H + TY - 1) / TY, TW = (W + TX - 1) / TX;
-      if ((TY > 1 && (TY - 1) * TH >= H) || (TX > 1 && (TX - 1) * TW >= W)) continue;     // an empty last tile
-      const int LH = TY > 1 ? TH + 6 : H, LW = TX > 1 ? TW + 6 : W;
-      const int minP = TY > 1 ? TH + 6 : H + 3, minQ = TX > 1 ? TW + 6 : W + 3;
-      if (minP > DFT_MAXP || minQ > 2 * (DFT_MAXV - 1)) continue;
-      for (int k = 0; k < (canonical ? 6 : 1); ++k) {
-        if (canonical && (DFT_CANONICAL[k].P < minP || DFT_CANONICAL[k].Q < minQ)) continue;
-        DftPlan c = {};
-        if (!dft_plan_transform(LH, LW, TY > 1 ? TH + 3 : H, TX > 1 ? TW + 3 : W, canonical ? DFT_CANONICAL[k].P : minP,
-                                canonical ? DFT_CANONICAL[k].Q : minQ, G, &c))
-          continue;
-        dft_set_tiles(&c, H, W, TY, TX, TH, TW);
-        const long cost = (long)c.T * c.NBINS;
-        if (!found || cost < best) {
-          found = true;
-          best = cost;
-          *out = c;
-        }
-      }
-    }
-  return found;
-}
-
-#ifndef OS2D_HOST_EMU
-static inline int dft_size_policy() {
-  static const int policy = [] {
-    const char* e = getenv("OS2D_DFT_SIZES");
-    return (e && (e[0] == 'e' || e[0] == '0')) ? 0 : 1;
-  }();
-  return policy;
-}
-#else
-static inline int dft_size_policy() { return emu_dft_policy; }
-#endif
-static inline bool dft_make_plan(int H, int W, DftPlan* out) { return dft_make_plan_policy(H, W, dft_size_policy(), out); }
-// The plan of the same map with 8 images per iteration: the SAME tiling and transform size as ``base`` (= dft_make_plan: the spectra
-// layouts do not depend on G), its own operand sizes; false when the transform is too large for it (then both kernels take 4).
-static inline bool dft_plan_g8(const DftPlan& base, DftPlan* out) {
-  DftPlan c = {};
-  if (!dft_plan_transform(base.LH, base.LW, base.RH, base.TX > 1 ? base.TW + 3 : base.W, base.P, base.Q, 8, &c)) return false;
-  dft_set_tiles(&c, base.H, base.W, base.TY, base.TX, base.TH, base.TW);
-  *out = c;
-  return true;
-}
-
-// Spectra in quads of bins, BLOCKED by 64 pairs (the pair tile of the per-bin GEMM):
-//   [pair' / 64][bins / 4][pair' % 64][channel stride][4] complex64, the last block holding NBT % 64 pairs (no padding: the
-//   buffers keep their size NBT x bins x channels).
-// With one block - up to 64 pairs - this is [bins / 4][pair'][channel][4].  With 1024 pairs the quads of one pair were 7.6 MB
-// (X) / 4 MB (Y) apart: every 128-byte run of a transform iteration in its own DRAM page and translation entry; blocked, the
-// distance is that of the 64-pair case (475 / 262 KB) whatever the batch, and a GEMM work-group's operands are one contiguous
-// slab.  Returns the float offset of (pair', quad 0, channel 0); *qstride = floats between consecutive quads of that pair.
-constexpr int DFT_PBLK = 64;
-DFT_HD size_t dft_spectra_pair0(int pr, int NBT, int NQ, int cstride, size_t* qstride) {
-  const int pb = pr / DFT_PBLK, pl = pr - pb * DFT_PBLK;
-  const int nbl = NBT - pb * DFT_PBLK < DFT_PBLK ? NBT - pb * DFT_PBLK : DFT_PBLK;
-  *qstride = (size_t)nbl * cstride * 8;
-  return ((size_t)pb * DFT_PBLK * NQ + pl) * cstride * 8;
-}
 
 // ---------------------------------------------------------------------------------------------------- device helpers
 DFT_DEV int dft_div(int x, unsigned magic) { return magic ? (int)(((unsigned long long)(unsigned)x * magic) >> 32) : x; }
@@ -479,7 +259,7 @@ DFT_DEV void dft_product_lds_any(f32x16* acc, int ntiles, int ks0, int ks1, cons
 
 // ---------------------------------------------------------------------------------------------------- constant matrices
 // thread per unit; tw tables: double [n][2] = (cos, sin) of -2 pi m / n.  Layouts (units of 8 halves along k):
-//   FqT [k = w / 8][hi|lo][n = 2 v + ri < N1]         value(w, n) = E_Q[v w].{re, im}                     * 2^14
+//   FqT [k = w / 8][hi|lo][n = 2 v + ri < N1]         value(w, n) = E_Q[v w].{re, im}                     * 2^14 (DFT_SCALE_F; Fp2, E2 too)
 //   Fp2 [k = (ri * Pp + h) / 8][hi|lo][m = 2 u + ro]  value = ro == 0 ? (ri == 0 ? cos : sin) : (ri == 0 ? -sin : cos) of 2 pi u h / P
 //   E2  [k = (ri * Pp + u) / 8][hi|lo][m = 2 h + ro]  value = ro == 0 ? (ri == 0 ? cos : -sin) : (ri == 0 ? sin : cos)
 //   Gq  [k = (2 v + ri) / 8][hi|lo][n = w]            value = a_v * E_Q[v w].{re, im}, a_0 = a_{Q/2} = 1, else 2   * 2^13
@@ -513,32 +293,32 @@ DFT_DEV void dft_matrix_unit(int which, int unit, int P, int Q, const double* tw
     double x = 0.0;
     if (which == 0) {                  // FqT: k = w, col = 2 v + ri
       const int v = col >> 1, ri = col & 1;
-      if (k < Q && v < V) x = twQ[2 * (int)(((long long)v * k) % Q) + ri] * 16384.0;
+      if (k < Q && v < V) x = twQ[2 * (int)(((long long)v * k) % Q) + ri] * DFT_SCALE_F;
     } else if (r2) {                   // Fp2 of the 64-row transform: cos | sin rows, k permuted to the accumulator order
       const int h = 8 * (2 * (kidx >> 1) + (t >> 2)) + 4 * (kidx & 1) + (t & 3), u = col & 31;
       if (kidx < 4) {                  // P = Pp = 32 here: units [kidx = 2 a + half-wave][hi|lo][64 rows], the rest of the block zero
         const int a = (int)(((long long)u * h) % P) * tws;
-        x = (col < 32 ? twP[2 * a] : -twP[2 * a + 1]) * 16384.0;       // cos, sin of +2 pi u h / 32
+        x = (col < 32 ? twP[2 * a] : -twP[2 * a + 1]) * DFT_SCALE_F;       // cos, sin of +2 pi u h / 32
       }
     } else if (which == 1) {           // Fp2: k = ri * Pp + h, col (row of the product) = 2 u + ro
       const int ri = k / Pp, h = k - ri * Pp, u = col >> 1, ro = col & 1;
       if (h < P && u < P && ri < 2) {
         const int a = (int)(((long long)u * h) % P) * tws;
         const double c = twP[2 * a], s = -twP[2 * a + 1];          // cos, sin of +2 pi u h / P
-        x = (ro == 0 ? (ri == 0 ? c : s) : (ri == 0 ? -s : c)) * 16384.0;
+        x = (ro == 0 ? (ri == 0 ? c : s) : (ri == 0 ? -s : c)) * DFT_SCALE_F;
       }
     } else if (which == 2) {           // E2: k = ri * Pp + u, col = 2 h + ro
       const int ri = k / Pp, u = k - ri * Pp, h = col >> 1, ro = col & 1;
       if (u < P && h < P && ri < 2) {
         const int a = (int)(((long long)u * h) % P);
         const double c = twP[2 * a], s = -twP[2 * a + 1];
-        x = (ro == 0 ? (ri == 0 ? c : -s) : (ri == 0 ? s : c)) * 16384.0;
+        x = (ro == 0 ? (ri == 0 ? c : -s) : (ri == 0 ? s : c)) * DFT_SCALE_F;
       }
     } else {                           // Gq: k = 2 v + ri, col = w
       const int v = k >> 1, ri = k & 1;
       if (v < V && col < Q) {
         const double a = (v == 0 || 2 * v == Q) ? 1.0 : 2.0;
-        x = a * twQ[2 * (int)(((long long)v * col) % Q) + ri] * 8192.0;
+        x = a * twQ[2 * (int)(((long long)v * col) % Q) + ri] * DFT_SCALE_GQ;
       }
     }
     vals[t] = x;
@@ -572,24 +352,24 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
                               const u32x4* FqT, const u32x4* Fp2, const DftPlan& pl, int C, int Cpad, int NBT, int iters) {
   constexpr int THR = NW * 64;
   constexpr bool ALDS = G == 8;    // the row operand of step 2 lives in LDS
-  constexpr bool R2 = !ALDS && KS2 == 8;      // P = 64: radix 2 (the head of this file)
+  constexpr bool R2 = !ALDS && KS2 == DFT_R2_KS;      // P = 64: radix 2 (the head of this file)
   unsigned char* smem = DFT_LDS;
   const int tid = DFT_TID, lane = tid & 63, l31 = lane & 31, hw = lane >> 5;
   const int wv = DFT_UNIFORM(tid >> 6);      // wave-uniform (a scalar register): the tile ownership below is real branching, not exec masks
   const int P = pl.P, V = pl.V, Pp = pl.Pp, Wk = pl.Wk, N1 = pl.N1, Mx = pl.Mx, N2 = pl.N2, LH = pl.LH, LW = pl.LW, W = pl.W, H = pl.H;
-  const int MxS = Mx + 1, N2S = N2 + 1;
+  const int MxS = dft_pitch_x(pl), N2S = dft_pitch_n2(pl);      // pitches of x | R2 (units)
   const int CG = (C + G - 1) / G, HW = H * W;
   const bool unit_norm = invn == nullptr;      // the input is already normalised (every sample in [0, 1]): x = relu(corr)
   u32x4* ldsF = reinterpret_cast<u32x4*>(smem);                                   // FqT [Wk / 8][2][N1]
   u32x4* ldsU = reinterpret_cast<u32x4*>(smem + pl.lds_const);                    // x | R2 | X staging
   unsigned char* ldsUb = smem + pl.lds_const;
-  const int nF = (Wk / 8) * 2 * N1;
+  const int nF = dft_lds_fqt(pl);
   for (int i = tid; i < nF; i += THR) ldsF[i] = FqT[i];
-  const unsigned char* ldsTw = smem + pl.lds_const + pl.lds_union + DFT_R2_LDS_TW;           // R2: the twiddles, float [32][re|im]
-  if (R2 && tid < DFT_R2_TWU) reinterpret_cast<u32x4*>(smem + pl.lds_const + pl.lds_union + DFT_R2_LDS_TW)[tid] = Fp2[DFT_R2_MATU + tid];
+  const unsigned char* ldsTw = dft_lds_tail_ptr(smem, pl) + DFT_TAIL_TW;                // R2: the twiddles, float [32][re|im]
+  if (R2 && tid < DFT_R2_TWU) reinterpret_cast<u32x4*>(dft_lds_tail_ptr(smem, pl) + DFT_TAIL_TW)[tid] = Fp2[DFT_R2_MATU + tid];
   u32x4* ldsP = ldsF + nF;                                                         // ALDS: Fp2 [2 Pp / 8][2][M2]
   if (ALDS)
-    for (int i = tid; i < (2 * Pp / 8) * 2 * pl.M2; i += THR) ldsP[i] = Fp2[i];
+    for (int i = tid; i < dft_lds_rowop(Pp, pl.M2); i += THR) ldsP[i] = Fp2[i];
 
   // the wave's tiles.  step 1: (row tile of x, column tile of FqT), round robin - with 8 row tiles a wave keeps ONE row tile
   // and its A fragment serves all column tiles; step 2: row tile wv & 3 of Fp2 in REGISTERS, column tiles (wv >> 2) + 2 j
@@ -629,7 +409,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
 
   // ---- register prefetch of the next iteration's window: position slot s of a thread = (row r, 4 columns c4) of the window,
   // all G images; raw values only (any arithmetic here would make the compiler wait for each load where it is issued)
-  constexpr int NSLOT = ALDS ? 2 : 3 * 512 / THR;              // ceil(Pp * Wk / 4 / THR) <= 64 * 24 / THR (G = 8: <= 48 * 16 / 512)
+  constexpr int NSLOT = ALDS ? DFT_SLOTS_G8 : DFT_SLOTS_G4 * DFT_THR / THR;      // ceil(Pp * Wk / 4 / THR): dft_plan.h, capacity
   const int npos = Pp * (Wk / 4);
   f32x4 pc[NSLOT][G], pn[NSLOT];
 #define DFT_FWD_ITER(IT)                                                                                     \
@@ -721,7 +501,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const bool ok = FAST ? (r_ < LH && 4 * c4_ < LW) : (r_ < LH && y_ >= 0 && y_ < H && 4 * c4_ + e < LW && x_ + e >= 0 && x_ + e < W);
-            nsc[e] = ok ? (unit_norm ? 32768.0f : pn[s][e] * 32768.0f) : 0.f;
+            nsc[e] = ok ? (unit_norm ? DFT_SCALE_X : pn[s][e] * DFT_SCALE_X) : 0.f;
           }
 #pragma unroll
           for (int g = 0; g < G; ++g) {
@@ -747,11 +527,11 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
     DFT_STAMP(0)
 
     // ---- step 1: R^T = x . FqT; this wave's tiles t = wv + 8 j of the mt1n x nt1n grid
-    f32x16 acc[3];
-    int tm[3], tn[3];
+    f32x16 acc[DFT_ACC_TILES];
+    int tm[DFT_ACC_TILES], tn[DFT_ACC_TILES];
     int nt1w = 0;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
+    for (int j = 0; j < DFT_ACC_TILES; ++j) {
       const int t = wv + NW * j;
       const bool mine = t < mt1n * nt1n;
       tn[j] = mine ? t / mt1n : 0;
@@ -772,12 +552,12 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
       // consecutive k of its half-wave: runs q = 2 a, 2 a + 1 of a lane ARE the fragment of k-step a once Fp2's k order is
       // h' = 8 (2 a + t / 4) + 4 (lane >> 5) + t % 4 (dft_matrix_unit).  No LDS round trip of R, no barrier up to the staging.
       const int img = wv >> 1, par = wv & 1;
-      half8 bh[3][2], bl[3][2];
+      half8 bh[DFT_ACC_TILES][2], bl[DFT_ACC_TILES][2];
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
+      for (int j = 0; j < DFT_ACC_TILES; ++j) {
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
-          const float sc = 1.0f / 2097152.0f;      // 2^-21 = 2^8 / (2^15 * 2^14)
+          const float sc = DFT_SCALE_R;      // 2^-21 = 2^8 / (2^15 * 2^14)
           u32x2 h0, l0, h1, l1;
           dft_split4(acc[j][8 * a] * sc, acc[j][8 * a + 1] * sc, acc[j][8 * a + 2] * sc, acc[j][8 * a + 3] * sc, &h0, &l0);
           dft_split4(acc[j][8 * a + 4] * sc, acc[j][8 * a + 5] * sc, acc[j][8 * a + 6] * sc, acc[j][8 * a + 7] * sc, &h1, &l1);
@@ -793,10 +573,10 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
       // im lane takes it negated - and hold Re | Im of 16 u each; 2^-22 = 1 / (2^8 * 2^14) rides on the two operands (exact).
       // One column tile at a time: two accumulators live.  E (even rows) is staged at u, O at 32 + u, as the butterfly reads them,
       // in the layout of the XS phase below - a lane writes the 4-byte Re or Im of its 16 u.
-      const int XS = P * 8 * G + 16;
-      const float sc2 = 1.0f / 4194304.0f, sg = (l31 & 1) ? -sc2 : sc2;
+      const int XS = dft_pitch_xs(P, G);
+      const float sc2 = DFT_SCALE_XOUT, sg = (l31 & 1) ? -sc2 : sc2;
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
+      for (int j = 0; j < DFT_ACC_TILES; ++j) {
         f32x16 cr, sr;
 #pragma unroll
         for (int r = 0; r < 16; ++r) cr[r] = sr[r] = 0.f;
@@ -824,7 +604,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
       // ---- R: R * 2^8 as units [k = (ri * Pp + h) / 8][hi|lo][n2 = img * V + v]; this lane owns column n = 2 v + ri of its
       // tiles and, per accumulator run, 4 consecutive h of one image: half a unit
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
+      for (int j = 0; j < DFT_ACC_TILES; ++j) {
         if (tm[j] < 0) continue;
         const int n = tn[j] * 32 + l31, v = n >> 1, ri = n & 1;
 #pragma unroll
@@ -835,7 +615,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
           const int img = dft_div(mb, pl.inv_pp), h0 = mb - img * Pp + 4 * hw;
           if (v < V && img < G) {
             u32x2 hi, lo;
-            const float sc = 1.0f / 2097152.0f;      // 2^-21 = 2^8 / (2^15 * 2^14)
+            const float sc = DFT_SCALE_R;      // 2^-21 = 2^8 / (2^15 * 2^14)
             dft_split4(acc[j][4 * q] * sc, acc[j][4 * q + 1] * sc, acc[j][4 * q + 2] * sc, acc[j][4 * q + 3] * sc, &hi, &lo);
             const int kg = ri * (Pp / 8) + (h0 >> 3);
             unsigned char* dst = ldsUb + ((size_t)(kg * 2) * N2S + img * V + v) * 16 + (h0 & 4) * 2;
@@ -849,11 +629,11 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
 
       // ---- step 2: X = Fp2 . R2 (Fp2 fragments in registers); this wave's column tiles (wv >> 2) + 2 j of row tile wv & 3
       // (ALDS: tiles t = wv + NW j of the mt2n x nt2n grid, row tile fastest - as dft_product_lds counts them)
-      f32x16 xc[3];
-      int un[3], um[3];      // column / row tile of accumulator j, -1: none
+      f32x16 xc[DFT_ACC_TILES];
+      int un[DFT_ACC_TILES], um[DFT_ACC_TILES];      // column / row tile of accumulator j, -1: none
       int nt2w = 0;
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
+      for (int j = 0; j < DFT_ACC_TILES; ++j) {
         const int t = wv + NW * j;
         const int nt = ALDS ? t / mt2n : (wv >> 2) + (NW / 4) * j;
         const bool mine = ALDS ? t < mt2n * nt2n : (nt < nt2n && mt2 < mt2n);
@@ -887,10 +667,10 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
       DFT_STAMP(3)
 
       // ---- XS: X = acc * 2^-22 staged as [v][u / 4][img][u % 4][re|im] (+16 bytes per v: consecutive lanes = consecutive v land
-      // in different banks); a lane owns (img, v) and per accumulator run two consecutive u
-      const int XS = P * 8 * G + 16;
+      // in different banks: dft_pitch_xs); a lane owns (img, v) and per accumulator run two consecutive u
+      const int XS = dft_pitch_xs(P, G);
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
+      for (int j = 0; j < DFT_ACC_TILES; ++j) {
         if (un[j] < 0) continue;
         const int n2 = un[j] * 32 + l31;
         const int img = dft_div(n2, pl.inv_v), v = n2 - img * V;
@@ -898,7 +678,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
         for (int q = 0; q < 4; ++q) {
           const int u0 = (um[j] * 32 + 8 * q + 4 * hw) >> 1;
           if (img < G && u0 < P) {
-            const float sc = 1.0f / 4194304.0f;      // 2^-22 = 1 / (2^8 * 2^14)
+            const float sc = DFT_SCALE_XOUT;      // 2^-22 = 1 / (2^8 * 2^14)
             f32x4 o;
             o[0] = xc[j][4 * q] * sc;
             o[1] = xc[j][4 * q + 1] * sc;
@@ -914,7 +694,7 @@ DFT_DEV void dft_forward_body(const float* corr,      // [NB][C][H * W]
 
     // ---- ST: 16-byte pieces, 8 per quad of bins = the 128 contiguous bytes of the 4 channels; then the padding bins
     {
-      const int XS = P * 8 * G + 16;      // the staging pitch of both paths above
+      const int XS = dft_pitch_xs(P, G);      // the staging pitch of both paths above
       const int per_v = (P / 4) * (G * 2), npieces = V * per_v;
       size_t qstride;                                            // floats between consecutive quads of bins
       float* dstbase = X + dft_spectra_pair0(pr_, NBT, pl.NBINS / 4, Cpad, &qstride) + (size_t)c0_ * 8;
@@ -972,23 +752,23 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
   const int tid = DFT_TID, lane = tid & 63, l31 = lane & 31, hw = lane >> 5;
   const int wv = DFT_UNIFORM(tid >> 6);
   const int P = pl.P, V = pl.V, Pp = pl.Pp, N2 = pl.N2, MB = pl.MB, KB = pl.KB, NBo = pl.NBo, H = pl.H, W = pl.W;
-  const int N2S = N2 + 1, MBS = MB + 1;
+  const int N2S = dft_pitch_n2(pl), MBS = dft_pitch_tt(pl);      // pitches of Y2 and Tt (units)
   const int OG = Cout / G;
   constexpr bool ALDS = G == 8;      // the row operand of step A lives in LDS
   constexpr int LG = G == 8 ? 3 : 2; // log2 G
   u32x4* ldsG = reinterpret_cast<u32x4*>(smem);                                   // Gq [KB / 8][2][NBo]
   u32x4* ldsU = reinterpret_cast<u32x4*>(smem + pl.lds_const);                    // Y2 | Tt
   unsigned char* ldsUb = smem + pl.lds_const;
-  float* smaxw = reinterpret_cast<float*>(smem + pl.lds_const + pl.lds_union);      // [8 waves][G]: |Y| maxima
-  const int nG = (KB / 8) * 2 * NBo, NQ = dft_round_up(pl.Q, 32);     // the Gq array has round_up(Q, 32) columns, NBo of them are needed
+  float* smaxw = reinterpret_cast<float*>(dft_lds_tail_ptr(smem, pl) + DFT_TAIL_MAX);      // [DFT_WAVES][G]: |Y| maxima
+  const int nG = dft_lds_gq(pl), NQ = dft_round_up(pl.Q, 32);     // the Gq array has round_up(Q, 32) columns, NBo of them are needed
   for (int i = tid; i < nG; i += DFT_THR) {
     const int kh = i / NBo, n = i - kh * NBo;
     ldsG[i] = Gq[(size_t)kh * NQ + n];
   }
-  const int MAfull = dft_round_up(2 * P, 32);                    // row count of the E2 array
+  const int MAfull = dft_round_up(2 * P, 32);                    // row count of the E2 array (= pl.M2)
   u32x4* ldsE = ldsG + nG;                                      // ALDS: E2 [2 Pp / 8][2][MAfull]
   if (ALDS)
-    for (int i = tid; i < (2 * Pp / 8) * 2 * MAfull; i += DFT_THR) ldsE[i] = E2[i];
+    for (int i = tid; i < dft_lds_rowop(Pp, MAfull); i += DFT_THR) ldsE[i] = E2[i];
 
   const int mtAn = pl.MA / 32, ntAn = N2 / 32, ksAn = 2 * Pp / 16;
   const int mtBn = MB / 32, ntBn = NBo / 32, ksBn = KB / 16;
@@ -1010,7 +790,7 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
   }
 
   // ---- register prefetch: item = (img, v, octet of u) -> the two quads of bins u0 .. u0 + 7 of column v: 2 x 32 bytes
-  constexpr int NITEM = 3;                                      // ceil(G * V * Pp / 8 / 512) <= 4 * 48 * 8 / 512 (G = 8: 8 * 32 * 6 / 512)
+  constexpr int NITEM = DFT_ITEMS;                              // ceil(G * V * Pp / 8 / DFT_THR): dft_plan.h, capacity
   const int uoct = Pp / 8, nitem = G * V * uoct;
   f32x4 py[NITEM][4];
 #define DFT_INV_PREFETCH(IT, TID) DFT_INV_PREFETCH_ITEMS(IT, TID, 0, NITEM)
@@ -1089,7 +869,7 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
     DFT_STAMP(0)
     float simg = 1.f, cinv[4] = {0.f, 0.f, 0.f, 0.f};      // cinv: of this lane's 4 channels in the epilogue (G = 8: 4 hw .. 4 hw + 3)
     {
-      // scale of an image: 2^(13 - E), E = floor(log2(max)): the largest component lands in [2^13, 2^14)
+      // scale of an image: 2^(DFT_EY - E), E = floor(log2(max)): the largest component lands in [2^13, 2^14)
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         float m = 0.f;
@@ -1098,11 +878,11 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
         int E = (int)((__builtin_bit_cast(unsigned, m) >> 23) & 0xffu) - 127;
         if (!(m > 0.f) || E < -100) E = -100;
         if (E > 100) E = 100;
-        const float s = __builtin_bit_cast(float, (unsigned)(13 - E + 127) << 23);
-        const float sinv = __builtin_bit_cast(float, (unsigned)(E - 13 + 127) << 23);
+        const float s = __builtin_bit_cast(float, (unsigned)(DFT_EY - E + 127) << 23);
+        const float sinv = __builtin_bit_cast(float, (unsigned)(E - DFT_EY + 127) << 23);
         if (g == (tl & (G - 1))) simg = s;
         // output = acc * 2^(eT - 13) / (scale * P * Q)
-        const float ci = sinv * __builtin_bit_cast(float, (unsigned)(pl.eT - 13 + 127) << 23) / (float)(P * pl.Q);
+        const float ci = sinv * __builtin_bit_cast(float, (unsigned)(pl.eT - DFT_EGQ + 127) << 23) / (float)(P * pl.Q);
         if (G == 4 || (g >> 2) == hw) cinv[g & 3] = ci;      // (compile-time g: a select per value, no indexed register array)
       }
     }
@@ -1145,11 +925,11 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
 
     // ---- step A: T = E2 . Y2 (E2 fragments in registers)
     // (ALDS: tiles t = wv + 8 j of the mtAn x ntAn grid, row tile fastest - as dft_product_lds counts them)
-    f32x16 ta[3];
-    int an[3], am[3];      // column / row tile of accumulator j, -1: none
+    f32x16 ta[DFT_ACC_TILES];
+    int an[DFT_ACC_TILES], am[DFT_ACC_TILES];      // column / row tile of accumulator j, -1: none
     int ntaw = 0;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
+    for (int j = 0; j < DFT_ACC_TILES; ++j) {
       const int t = wv + DFT_WAVES * j;
       const int nt = ALDS ? t / mtAn : (wv >> 2) + 2 * j;
       const bool mine = ALDS ? t < mtAn * ntAn : (nt < ntAn && mtA < mtAn);
@@ -1180,9 +960,9 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
     // run (re, im) of two consecutive h: 4 bytes of a unit each.  The k beyond 2 V of the last units are zeroed (Gq has zero
     // rows there, but 0 * NaN-patterned garbage is NaN).
     {
-      const float sc = __builtin_bit_cast(float, (unsigned)(127 - 14 - pl.eT) << 23);
+      const float sc = __builtin_bit_cast(float, (unsigned)(127 - DFT_EF - pl.eT) << 23);
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
+      for (int j = 0; j < DFT_ACC_TILES; ++j) {
         if (an[j] < 0) continue;
         const int n = an[j] * 32 + l31;
         const int img = dft_div(n, pl.inv_v), v = n - img * V;
@@ -1210,11 +990,11 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
     DFT_STAMP(3)
 
     // ---- step B: y = Tt . Gq; this wave's tiles t = wv + 8 j of the mtBn x ntBn grid
-    f32x16 yc[3];
-    int bm[3], bn[3];
+    f32x16 yc[DFT_ACC_TILES];
+    int bm[DFT_ACC_TILES], bn[DFT_ACC_TILES];
     int ntbw = 0;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
+    for (int j = 0; j < DFT_ACC_TILES; ++j) {
       const int t = wv + DFT_WAVES * j;
       const bool mine = t < mtBn * ntBn;
       bn[j] = mine ? t / mtBn : 0;
@@ -1264,7 +1044,7 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
         }
       }
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
+      for (int j = 0; j < DFT_ACC_TILES; ++j) {
         if (bm[j] < 0) continue;
         const int wwin = bn[j] * 32 + l31, tw = wwin - ox;
 #pragma unroll
@@ -1288,7 +1068,7 @@ DFT_DEV void dft_inverse_body(const float* Y,        // [NBT / 64][NBINS / 4][64
               if (inside) {
                 float* dst = reinterpret_cast<float*>(out) + ((size_t)nb * Cout + o0 + (G == 8 ? 4 * hw : 0)) * ((size_t)H * W) + (size_t)h * W + w;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) dst[(size_t)g * H * W] = t[g] * (1.0f / 32768.0f);
+                for (int g = 0; g < 4; ++g) dst[(size_t)g * H * W] = t[g] * DFT_SCALE_PLANES;
               }
               continue;
             }

@@ -58,11 +58,12 @@ namespace {
 
 using namespace os2d_dft;
 
-// KS = k-steps of the product whose row operand lives in registers (step 2 / step A: 2 Pp / 16): a template parameter for the
-// canonical transform sizes (5 .. 8: straight-line products, exactly as many fragment registers as the size needs), 0 = any
-// size behind uniform guards ($OS2D_DFT_SIZES=exact).  KS = 8 is the 64-row transform and nothing else (dft_plan_transform): the
-// forward instantiations run the radix-2 form of step 2 - per wave the 32-point transform of its own step-1 rows, handed over in
-// registers (2 k-steps, a 64 x 32 real row operand), and a butterfly (dft_mfma.h)
+// KS = k-steps of the product whose row operand lives in registers (step 2 / step A), as dft_ksteps_param (dft_plan.h) chooses
+// it for a plan: a template parameter for the canonical transform sizes (5 .. 8: straight-line products, exactly as many
+// fragment registers as the size needs), 0 = any size behind uniform guards ($OS2D_DFT_SIZES=exact) and the plans of 8 images.
+// KS = 8 is the 64-row transform and nothing else (dft_plan_transform): the forward instantiations run the radix-2 form of
+// step 2 - per wave the 32-point transform of its own step-1 rows, handed over in registers (2 k-steps, a 64 x 32 real row
+// operand), and a butterfly (dft_mfma.h)
 template <bool TILED, bool FAST, int G, int NW, int KS>
 __global__ __launch_bounds__(NW * 64, 8 / NW) void dft_forward_kernel(const float* __restrict__ corr, const float* __restrict__ invn,
                                                                       float* __restrict__ X, const u32x4* __restrict__ FqT,
@@ -89,9 +90,9 @@ dft_forward_fn dft_forward_variant(const DftPlan& pl) {
 template <int G, int NW>
 dft_forward_fn dft_forward_pick(const DftPlan& pl) {
   if constexpr (G == 8) {
-    return dft_forward_variant<G, NW, 0>(pl);      // (Fp2 in LDS: no register-resident k-steps to count)
+    return dft_forward_variant<G, NW, 0>(pl);      // (Fp2 in LDS: dft_ksteps_param is 0, and no other instantiation is built)
   } else {
-    switch (2 * pl.Pp / 16) {      // k-steps of step 2
+    switch (dft_ksteps_param(pl)) {
       case 5: return dft_forward_variant<G, NW, 5>(pl);
       case 6: return dft_forward_variant<G, NW, 6>(pl);
       case 7: return dft_forward_variant<G, NW, 7>(pl);
@@ -106,7 +107,7 @@ dft_inverse_fn dft_inverse_variant(const DftPlan& pl) {
 }
 dft_inverse_fn dft_inverse_pick(const DftPlan& pl) {
   if (pl.G == 8) return dft_inverse_variant<0, 8>(pl);
-  switch (2 * pl.Pp / 16) {      // k-steps of step A
+  switch (dft_ksteps_param(pl)) {
     case 5: return dft_inverse_variant<5>(pl);
     case 6: return dft_inverse_variant<6>(pl);
     case 7: return dft_inverse_variant<7>(pl);
@@ -210,7 +211,7 @@ int os2d_launch_dft_forward(const float* corr, const float* inv, float* X, const
     os2d_set_error("dft_forward: channel stride %d < %d", Cpad, dft_round_up(C, G));
     return -1;
   }
-  if (G == 4 && pl.Pp == 64 && !dft_radix2(pl.P)) {
+  if (dft_ksteps_param(pl) == DFT_R2_KS && !dft_radix2(pl.P)) {
     os2d_set_error("dft_forward: a plan of 8 k-steps with %d rows (the radix-2 kernel takes 64)", pl.P);
     return -3;
   }

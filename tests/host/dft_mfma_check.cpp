@@ -1,58 +1,9 @@
 // Host check of os2d_amd/csrc/dft_mfma.h on the SPMD emulator (spmd_emu.h): the forward and the inverse transform kernels -
 // the same source the GPU runs - against float64 DFTs, for an untiled fast-path map, a map whose width is not a multiple of 4,
 // a small map and tiled maps (ragged tiles).  Built and run by tests/test_dft_mfma_host.py.   usage: dft_mfma_check [H W C NB]...
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "spmd_emu.h"
-
-#define OS2D_HOST_EMU 1
-static int emu_dft_policy = 0;      // 0: smallest transform per map, 1: the canonical sizes
-#define DFT_DEV static inline
-#define DFT_TID emu::tid()
-#define DFT_BID emu::bid()
-#define DFT_GRID emu::grid()
-#define DFT_LDS emu::lds()
-#define DFT_BARRIER() emu::group_barrier()
-#define DFT_MFMA(a, b, c) emu::mfma_32x32x16_f16(a, b, c)
-#define DFT_SHFL_XOR(v, m) emu::shfl_xor(v, m)
-#define DFT_SHFL_XOR_U32(v, m) emu::shfl_xor_u32(v, m)
-#define DFT_BALLOT(p) emu::ballot(p)
-#define DFT_FLAG int*
-#define DFT_FLAG_SET(f) ((f) != nullptr)
-#define DFT_RAISE(p) (*(p) = 1)
-#define DFT_UNIFORM(x) (x)
-#include "dft_mfma.h"
-
-// The spectra layouts, stated independently of the kernels' helper (include/os2d_hip.h): blocks of 64 pairs,
-// [pair / 64][quad of bins][pair % 64 (last block: what is left)][channel][4 bins][re | im]
-static size_t spec_index(int bin, int pair, int NBT, int nquads, int chans, int c) {
-  const int blk = pair / 64, in_blk = pair % 64, held = std::min(64, NBT - 64 * blk);
-  return ((((size_t)blk * 64 * nquads + (size_t)(bin / 4) * held + in_blk) * chans + c) * 4 + (bin & 3)) * 2;
-}
+#include "dft_emu.h"      // the hooks on the emulator (policy 0: the smallest transform per map), dft_mfma.h, spec_index, table, frand, ws_of / base_of / plane_of
 
 using namespace os2d_dft;
-
-static std::vector<double> table(int n) {
-  std::vector<double> t(2 * n);
-  for (int m = 0; m < n; ++m) {
-    t[2 * m] = std::cos(-2.0 * M_PI * m / n);
-    t[2 * m + 1] = std::sin(-2.0 * M_PI * m / n);
-  }
-  return t;
-}
-
-static double frand(unsigned& s) {
-  s = s * 1664525u + 1013904223u;
-  return ((s >> 8) & 0xffffff) / double(1 << 24);
-}
-
-static int os2d_ws(int W) { return W + 3; }
-static int os2d_base(int W) { return dft_round_up(3 * os2d_ws(W) + 3, 4); }
-static int os2d_plane(int H, int W) { return dft_round_up(os2d_base(W) + (H + 3) * os2d_ws(W) + 3, 64); }
 
 static int check_case(int H, int W, int C, int NB, int grid) {
   DftPlan pl;
@@ -91,12 +42,12 @@ static int check_case(int H, int W, int C, int NB, int grid) {
     std::fill(X.begin(), X.end(), 777.0f);
     emu::launch(grid, 512, fp.lds_total, [&] {
       if (G == 4) {
-        // the k-step count of step 2 as a template parameter where the device build has one (dft_mfma.hip: dft_forward_pick)
+        // the instantiation dft_ksteps_param chooses for the plan, as dft_forward_pick of the device build (dft_mfma.hip)
 #define FWD4(KS)                                                                                                             \
   if (fp.T > 1) dft_forward_body<true, false, 4, 8, KS>(corr.data(), invn.data(), X.data(), FqT, Fp2, fp, C, Cpad, NBT, itf);  \
   else if (fp.fast) dft_forward_body<false, true, 4, 8, KS>(corr.data(), invn.data(), X.data(), FqT, Fp2, fp, C, Cpad, NBT, itf); \
   else dft_forward_body<false, false, 4, 8, KS>(corr.data(), invn.data(), X.data(), FqT, Fp2, fp, C, Cpad, NBT, itf);
-        switch (2 * fp.Pp / 16) {
+        switch (dft_ksteps_param(fp)) {
           case 5: FWD4(5) break;
           case 6: FWD4(6) break;
           case 7: FWD4(7) break;
@@ -170,7 +121,7 @@ static int check_case(int H, int W, int C, int NB, int grid) {
   }
 
   // ---------------- inverse (Cout = 16 output channels: 4 / 2 groups)
-  const int Cout = 16, MTP = 128, PLANE = os2d_plane(H, W), Ws = os2d_ws(W), BASE = os2d_base(W);
+  const int Cout = 16, MTP = 128, PLANE = plane_of(H, W), Ws = ws_of(W), BASE = base_of(W);
   std::vector<float> Y((size_t)(pl.NBINS / 4) * NBT * Cout * 8);
   for (size_t i = 0; i < Y.size(); ++i) {
     const double mag = std::exp(6.0 * frand(seed) - 2.0);              // a wide dynamic range between bins
@@ -238,7 +189,7 @@ static int check_case(int H, int W, int C, int NB, int grid) {
       if (ip.T > 1) dft_inverse_body<true, 0, 8>(Y.data(), bp.data(), MTP, out.data(), E2, Gq, ip, Cout, NBT, PLANE, Ws, BASE, iters_i, &flag, 1);
       else dft_inverse_body<false, 0, 8>(Y.data(), bp.data(), MTP, out.data(), E2, Gq, ip, Cout, NBT, PLANE, Ws, BASE, iters_i, &flag, 1);
     } else
-    switch (2 * ip.Pp / 16) {      // as dft_inverse_pick of the device build
+    switch (dft_ksteps_param(ip)) {      // as dft_inverse_pick of the device build
       case 5: INV(5) break;
       case 6: INV(6) break;
       case 7: INV(7) break;

@@ -13,57 +13,10 @@
 // 2e-6 max|X| + 1e-5, inverse 1.5e-6 of the channel's largest output; the round trip is bounded by their sum (every bin off by the
 // forward bound moves an output by at most that bound: the inverse averages P Q bins).
 // Built and run by tests/test_dft_radix2_host.py.
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "spmd_emu.h"
-
-#define OS2D_HOST_EMU 1
-static int emu_dft_policy = 1;      // the canonical sizes
-#define DFT_DEV static inline
-#define DFT_TID emu::tid()
-#define DFT_BID emu::bid()
-#define DFT_GRID emu::grid()
-#define DFT_LDS emu::lds()
-#define DFT_BARRIER() emu::group_barrier()
-#define DFT_MFMA(a, b, c) emu::mfma_32x32x16_f16(a, b, c)
-#define DFT_SHFL_XOR(v, m) emu::shfl_xor(v, m)
-#define DFT_SHFL_XOR_U32(v, m) emu::shfl_xor_u32(v, m)
-#define DFT_BALLOT(p) emu::ballot(p)
-#define DFT_FLAG int*
-#define DFT_FLAG_SET(f) ((f) != nullptr)
-#define DFT_RAISE(p) (*(p) = 1)
-#define DFT_UNIFORM(x) (x)
-#include "dft_mfma.h"
+#define DFT_EMU_POLICY 1      // the canonical sizes
+#include "dft_emu.h"      // the hooks on the emulator, dft_mfma.h, spec_index, table, frand, ws_of / base_of / plane_of
 
 using namespace os2d_dft;
-
-// the spectra layout, stated independently of the kernels' helper: [pair / 64][quad of bins][pair % 64][channel][4 bins][re | im]
-static size_t spec_index(int bin, int pair, int NBT, int nquads, int chans, int c) {
-  const int blk = pair / 64, in_blk = pair % 64, held = std::min(64, NBT - 64 * blk);
-  return ((((size_t)blk * 64 * nquads + (size_t)(bin / 4) * held + in_blk) * chans + c) * 4 + (bin & 3)) * 2;
-}
-
-static std::vector<double> table(int n) {
-  std::vector<double> t(2 * n);
-  for (int m = 0; m < n; ++m) {
-    t[2 * m] = std::cos(-2.0 * M_PI * m / n);
-    t[2 * m + 1] = std::sin(-2.0 * M_PI * m / n);
-  }
-  return t;
-}
-
-static double frand(unsigned& s) {
-  s = s * 1664525u + 1013904223u;
-  return ((s >> 8) & 0xffffff) / double(1 << 24);
-}
-
-static int ws_of(int W) { return W + 3; }
-static int base_of(int W) { return dft_round_up(3 * ws_of(W) + 3, 4); }
-static int plane_of(int H, int W) { return dft_round_up(base_of(W) + (H + 3) * ws_of(W) + 3, 64); }
 
 constexpr int H = 60, W = 80, NB = 2, C = 5, CPAD = 8, COUT = 8, MTP = 128, HW = H * W, GRID = 2;
 

@@ -13,6 +13,8 @@
 #include <string.h>
 
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <functional>
 #include <thread>
 #include <vector>
@@ -118,12 +120,16 @@ inline int readlane(int v, int lane) {
   return r;
 }
 
-// run `body` as a grid of `grid` work-groups of `nthreads` work items with `lds_bytes` of LDS (groups one after the other)
+// run `body` as a grid of `grid` work-groups of `nthreads` work items with `lds_bytes` of LDS (groups one after the other).
+// LDS_GUARD bytes behind the budget are checked when a group has finished: a kernel that writes beyond what its host code
+// asked for ends the program.  (4 KB, not a cache line: a region left out of a budget starts that far behind it - the 1 KB
+// tail of the transforms - and 64 bytes let such a write reach the heap before the check could report it.)
+constexpr size_t LDS_GUARD = 4096;
 inline void launch(int grid, int nthreads, size_t lds_bytes, const std::function<void()>& body) {
   for (int b = 0; b < grid; ++b) {
     Group g;
     g.nthreads = nthreads;
-    g.lds.assign(lds_bytes + 64, 0xA5);      // garbage, not zeros: a kernel must not rely on a cleared LDS
+    g.lds.assign(lds_bytes + LDS_GUARD, 0xA5);      // garbage, not zeros: a kernel must not rely on a cleared LDS
     pthread_barrier_init(&g.bar, nullptr, nthreads);
     g.waves = std::vector<WaveScratch>((nthreads + WAVE - 1) / WAVE);
     for (size_t w = 0; w < g.waves.size(); ++w) {
@@ -137,6 +143,12 @@ inline void launch(int grid, int nthreads, size_t lds_bytes, const std::function
         body();
       });
     for (auto& th : threads) th.join();
+    for (size_t i = 0; i < LDS_GUARD; ++i)
+      if (g.lds[lds_bytes + i] != 0xA5) {
+        std::printf("LDS OVERRUN: work-group %d wrote at offset %zu, %zu bytes beyond its budget of %zu\n", b, lds_bytes + i, i, lds_bytes);
+        std::fflush(stdout);
+        std::exit(3);
+      }
     pthread_barrier_destroy(&g.bar);
     for (auto& w : g.waves) pthread_barrier_destroy(&w.bar);
   }
