@@ -1,6 +1,6 @@
 /* os2d_train.h -- C ABI of libos2d_train.so: the backward pass of the OS2D head (reference os2d/modeling/head.py:308-435 under
  * autograd) for the MI355X (gfx950), strict fp32, and - since ABI version 2 - the target assignment and the training
- * objective (the last section of this file).
+ * objective, hard-patch mining, and the gradient clip + optimiser step (the last sections of this file).
  *
  * The forward of a training step is the "f32" route of libos2d_hip.so, run stage by stage (os2d_fm_sumsq, os2d_corr,
  * os2d_transform_conv x 3, os2d_sample_decode) so that its intermediates stay alive: corr [NB,225,HW], the relu + L2
@@ -286,6 +286,64 @@ int os2d_train_mine_select(int A, int B, int L, const int* level_hw, const int* 
                            const float* const* loc_loss, const unsigned char* const* flags, const float* const* cls_preds,
                            const float* const* corners, int crop_w, int crop_h, float iou_thr, int K, int* out_count, int* out_index,
                            float* out_values, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ==== Gradient clip, NaN guard and the SGD / Adam step (csrc_train/optim.hip; torch.nn.utils.clip_grad_norm_ followed by the
+ * reference's `if not math.isnan(grad_norm): optimizer.step()`, os2d/engine/train.py:104-108).  fp32
+ * parameters, gradients and state, dense.  One launch serves a TABLE of at most OS2D_TRAIN_OPTIM_MAX_TENSORS tensors, passed in the
+ * kernel arguments; a work-group owns one chunk of OS2D_TRAIN_OPTIM_CHUNK elements of one tensor.  Chunks are numbered over all
+ * the tables of a step: a tensor of numel elements takes os2d_train_optim_chunks chunks from its first_chunk on, and the records
+ * of a table follow each other without a gap (checked).  A step is
+ *     sumsq (per table)  ->  finalize  ->  [prepare (per table, Adam)]  ->  update (per table)
+ * on one stream; nothing synchronises with the host, no floating-point atomics, every sum in a fixed order: two runs on the same
+ * input give the same bits.  Every entry point checks its arguments before it launches anything: -1 for a null pointer, a
+ * tensor count outside 0 .. OS2D_TRAIN_OPTIM_MAX_TENSORS, a negative numel, records that do not follow each other, an `aligned`
+ * mark on pointers that are not 16-byte aligned, max_norm <= 0; -2 for a partials buffer that is too small.                  */
+#define OS2D_TRAIN_OPTIM_MAX_TENSORS 60
+#define OS2D_TRAIN_OPTIM_CHUNK 4096
+#define OS2D_TRAIN_OPTIM_SGD 0
+#define OS2D_TRAIN_OPTIM_ADAM 1
+typedef struct {
+  float* param;        /* [numel] */
+  float* grad;         /* [numel]; the update writes grad * coef back */
+  float* state1;       /* SGD: momentum_buffer (not read when momentum == 0); Adam: exp_avg */
+  float* state2;       /* Adam: exp_avg_sq */
+  float* step;         /* Adam: the tensor's step count, one float on the device */
+  long long numel;     /* 0 is allowed: no chunk, no access */
+  float lr;
+  float weight_decay;
+  int first_chunk;     /* index of the tensor's first chunk among all chunks of the step */
+  int aligned;         /* 1: param, grad and the state pointers are all 16-byte aligned (16-byte accesses); 0: 4-byte accesses */
+} os2d_train_optim_tensor;
+
+int os2d_train_optim_max_tensors(void);               /* OS2D_TRAIN_OPTIM_MAX_TENSORS */
+size_t os2d_train_optim_chunks(long long numel);      /* ceil(numel / OS2D_TRAIN_OPTIM_CHUNK); 0 for numel <= 0 */
+
+/* ---- partials[first_chunk + j] = the sum of the squares of chunk j of each tensor's grad, in double (an fp32 square is exact in
+ * double; per thread, then over the work-group, in a fixed order).  partials holds partials_count doubles: the chunks of ALL tables. */
+int os2d_train_optim_sumsq(const os2d_train_optim_tensor* tensors, int n, double* partials, size_t partials_count, void* stream);
+
+/* ---- one work-group adds partials[0 .. partials_count) in index order in double and writes record [4] floats:
+ *   record[0] norm = (float)sqrt(sum);
+ *   record[1] coef = min(max_norm / (norm + 1e-6f), 1.0f) in fp32 (NaN for a NaN norm); max_norm = +infinity: 1.0f, no clipping;
+ *   record[2] skip = 1.0f when norm is NaN, else 0.0f (an infinite norm does not skip);   record[3] = 0.                          */
+int os2d_train_optim_finalize(const double* partials, size_t partials_count, float max_norm, float* record, void* stream);
+
+/* ---- Adam, between finalize and update, one thread per tensor of the table: unless record says skip, *step += 1 and
+ * factors[2 i] = (float)(lr / bc1), factors[2 i + 1] = (float)sqrt(bc2), bc = 1 - beta^step in double.  factors: 2 n floats.    */
+int os2d_train_optim_prepare(const os2d_train_optim_tensor* tensors, int n, const float* record, double beta1, double beta2,
+                             float* factors, void* stream);
+
+/* ---- per element g = grad * record[1], written back to grad; then, unless record says skip, in fp32, one rounding per operation,
+ * correctly rounded division and square root, d = g + weight_decay * p (d = g when weight_decay == 0):
+ *   OS2D_TRAIN_OPTIM_SGD  (dampening 0, no Nesterov; momentum_or_beta1 = momentum, beta2 / eps / factors not used):
+ *       buf = momentum * buf + d;  p = p - lr * buf            (momentum == 0: p = p - lr * d, state1 is not touched)
+ *   OS2D_TRAIN_OPTIM_ADAM (L2 weight decay, no amsgrad; factors of this table as prepare wrote them):
+ *       m = m + (d - m) * (1 - beta1);  v = beta2 * v + ((1 - beta2) * d) * d;
+ *       den = sqrt(v) / factors[2 i + 1] + eps;  p = p - factors[2 i] * (m / den)
+ * with (float)momentum, (float)beta2, (float)(1 - beta1), (float)(1 - beta2), (float)eps.  On a skipped step parameters and state
+ * keep their bits.                                                                                                             */
+int os2d_train_optim_update(int method, const os2d_train_optim_tensor* tensors, int n, const float* record, const float* factors,
+                            double momentum_or_beta1, double beta2, double eps, void* stream);
 
 #ifdef __cplusplus
 }

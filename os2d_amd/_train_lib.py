@@ -15,6 +15,16 @@ _f = ctypes.c_float
 _sz = ctypes.c_size_t
 _d = ctypes.c_double
 
+
+class OptimTensor(ctypes.Structure):
+    """os2d_train_optim_tensor of include/os2d_train.h: one tensor of a multi-tensor optimiser launch (64 bytes)."""
+    _fields_ = [("param", _p), ("grad", _p), ("state1", _p), ("state2", _p), ("step", _p), ("numel", ctypes.c_longlong),
+                ("lr", _f), ("weight_decay", _f), ("first_chunk", _i), ("aligned", _i)]
+
+
+OPTIM_MAX_TENSORS, OPTIM_CHUNK = 60, 4096      # OS2D_TRAIN_OPTIM_MAX_TENSORS, OS2D_TRAIN_OPTIM_CHUNK
+OPTIM_SGD, OPTIM_ADAM = 0, 1
+
 SIGNATURES = {
     "os2d_train_abi_version": (_i, []),
     "os2d_train_last_error": (ctypes.c_char_p, []),
@@ -54,6 +64,12 @@ SIGNATURES = {
     "os2d_train_objective_forward": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _f, _d, _p, _p, _p, _p, _p,
                                           _p, _sz, _p]),
     "os2d_train_objective_backward": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _p, _p, _p, _p]),
+    "os2d_train_optim_max_tensors": (_i, []),
+    "os2d_train_optim_chunks": (_sz, [ctypes.c_longlong]),
+    "os2d_train_optim_sumsq": (_i, [_p, _i, _p, _sz, _p]),
+    "os2d_train_optim_finalize": (_i, [_p, _sz, _f, _p, _p]),
+    "os2d_train_optim_prepare": (_i, [_p, _i, _p, _d, _d, _p, _p]),
+    "os2d_train_optim_update": (_i, [_i, _p, _i, _p, _p, _d, _d, _d, _p]),
 }
 
 LIBRARY = NativeLibrary(build.TRAIN, SIGNATURES, ABI_VERSION, "os2d_train_abi_version", "os2d_train_last_error", "the head's backward pass")

@@ -60,7 +60,10 @@ TRAIN_CSRC = os.path.join(HERE, "csrc_train")
 # mining.hip needs no flag: every function of it that rounds (csrc/detect_common.h, mining_crop.h) switches contraction off itself
 # shb_planes.hip: the split-half blocked activations of an f16x3 training forward as the fp32 planes the backward reads
 # bn_live.hip: batch-statistics BatchNorm of the TransformNet (statistics, normalise + ReLU, backward through the statistics)
-TRAIN = Library("libos2d_train.so", TRAIN_CSRC, ["train.hip", "train_gemm.hip", "decode_backward.hip", "objective.hip", "mining.hip", "shb_planes.hip", "bn_live.hip"],
+# optim.hip: gradient norm, clip, NaN guard and the SGD / Adam step as multi-tensor kernels; needs no flag either: every function
+#            of it that rounds switches contraction off itself
+TRAIN = Library("libos2d_train.so", TRAIN_CSRC, ["train.hip", "train_gemm.hip", "decode_backward.hip", "objective.hip", "mining.hip", "shb_planes.hip", "bn_live.hip",
+                                                 "optim.hip"],
                 FLAGS + PACKED_OFF,
                 {"objective.hip": ["-ffp-contract=off"]},
                 [TRAIN_CSRC, CSRC, SHARED], "os2d_train.h", "OS2D_TRAIN_LIB")

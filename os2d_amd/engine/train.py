@@ -32,7 +32,9 @@ def train_one_batch(net, criterion, optimizer, box_coder, images, class_images, 
     ``cls_preds_for_neg`` = the transform-detached scores (unless ``train_transform_on_negs``), backward, gradient-norm
     clipping, and an optimiser step unless the norm is NaN.  ``loc_targets`` / ``class_targets`` are the encoded targets of
     the batch; None = encoded here with ``box_coder.encode_batch``.  Returns the criterion's losses with "grad_norm" added
-    (device scalars: nothing here waits for the device except the NaN check of the norm, as in the reference)."""
+    (device scalars).  An optimiser with ``clip_and_step`` (os2d_amd/engine/optimization.py: DeviceSGD, DeviceAdam) clips,
+    checks and steps on the device over ITS parameters, and nothing here waits for the device; with any other optimiser the
+    NaN check of the norm is a host wait, as in the reference."""
     optimizer.zero_grad()
     loc, cls, cls_det, fm_size, _ = forward_train(net, images, class_images, fine_tune_features=fine_tune_features)
     if loc_targets is None or class_targets is None:
@@ -41,8 +43,11 @@ def train_one_batch(net, criterion, optimizer, box_coder, images, class_images, 
     losses = criterion(loc, loc_targets, cls, class_targets, cls_targets_remapped=remapped,
                        cls_preds_for_neg=None if train_transform_on_negs else cls_det)
     losses["loss"].backward()
-    grad_norm = torch.nn.utils.clip_grad_norm_(get_trainable_parameters(net), max_grad_norm, norm_type=2)
-    if not math.isnan(float(grad_norm)):
-        optimizer.step()
+    if hasattr(optimizer, "clip_and_step"):
+        grad_norm = optimizer.clip_and_step(max_grad_norm)
+    else:
+        grad_norm = torch.nn.utils.clip_grad_norm_(get_trainable_parameters(net), max_grad_norm, norm_type=2)
+        if not math.isnan(float(grad_norm)):
+            optimizer.step()
     losses["grad_norm"] = grad_norm
     return losses
