@@ -101,7 +101,9 @@ int os2d_head_forward(const float* fm, const float* qp, const float* w1, const f
  *   weight_exp [Cout]  the folded weights w[o][c] * 2^-in_exp[c] of output channel o are multiplied by 2^weight_exp[o]
  *                   before the hi/lo split; choose the largest exponent that keeps their maximum <= 16384.
  * packed_b [3*MT] receives per output row the folded bias, 2^-weight_exp (applied to the accumulator) and 2^out_exp.
- * Buffer sizes: os2d_packed_conv_bytes, os2d_packed_bias_floats.                                                      */
+ * Buffer sizes: os2d_packed_conv_bytes, os2d_packed_bias_floats.
+ * os2d_train_range_plan (include/os2d_train.h) computes all three on the device from the raw parameters: weight_exp = its
+ * wexp<layer>, in_exp / out_exp = its e1, e2 (layer 1: in_exp = os2d_rnorm_exp() for all 225 channels).                */
 size_t os2d_packed_conv_bytes(int layer, int precision);
 int os2d_rnorm_exp(void);
 int os2d_pack_conv_f16x3(int layer /*1|2|3*/, int P, const float* w, const float* b, const float* bn_weight,

@@ -345,6 +345,28 @@ int os2d_train_optim_prepare(const os2d_train_optim_tensor* tensors, int n, cons
 int os2d_train_optim_update(int method, const os2d_train_optim_tensor* tensors, int n, const float* record, const float* factors,
                             double momentum_or_beta1, double beta2, double eps, void* stream);
 
+/* ---- the range plan of the split-fp16 ("f16x3") packing on the device - what a parameter change makes stale every step: the
+ * exponents os2d_pack_conv_f16x3 (include/os2d_hip.h) takes, from the raw fp32 parameters (w1 [128,225,7,7], w2 [64,128,5,5],
+ * w3 [P,64,5,5] and the biases of layers 1 and 2; bn<l>_* = NULL for a layer without BatchNorm, all four or none; bn<l>_eps is
+ * BatchNorm2d.eps as a DOUBLE).  Eval-mode BatchNorm fold, bounds and exponents in float64 throughout: three dependent launches on
+ * `stream`, no host wait, no atomics - two calls on the same parameters give the same bits.
+ *   exps   [os2d_train_range_plan_ints() = 520] int32:
+ *          wexp1 [128] | e1 [128] | unit_exp [128] | wexp2 [64] | e2 [64] | wexp3 [8] (entries of wexp3 past P are zero)
+ *            B1[o] = 7 * ||w1'[o]||_2 + |b1'[o]|                       (w', b': BatchNorm folded; the input has norm <= 1)
+ *            B2[o] = min(sum_c B1[c] * ||w2'[o,c]||_1, 5 * ||B1||_2 * ||w2'[o]||_2) + |b2'[o]|
+ *            e<l>[o]   = floor(log2(32768 / B<l>[o]))                  the layer's out_exp, the next layer's in_exp
+ *            unit_exp  = e1 - 15                                       (bound * 2^unit_exp <= 1)
+ *            wexp<l>[o] = floor(log2(16384 / max_c |w<l>'[o,c]| * 2^-in_exp[c]))     (layer 1: in_exp = 12, os2d_rnorm_exp())
+ *          each floor(log2) exact (the exponent field), clamped to [-60, 60]; 0 for a zero, NaN or infinite bound / maximum;
+ *   bounds [os2d_train_range_plan_doubles() = 192] float64, 8-byte aligned: B1 [128] | B2 [64].
+ * The change is additive: OS2D_TRAIN_ABI_VERSION stays 2.                                                                      */
+size_t os2d_train_range_plan_ints(void);
+size_t os2d_train_range_plan_doubles(void);
+int os2d_train_range_plan(int P, const float* w1, const float* b1, const float* bn1_weight, const float* bn1_bias,
+                          const float* bn1_running_mean, const float* bn1_running_var, double bn1_eps, const float* w2,
+                          const float* b2, const float* bn2_weight, const float* bn2_bias, const float* bn2_running_mean,
+                          const float* bn2_running_var, double bn2_eps, const float* w3, int* exps, double* bounds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

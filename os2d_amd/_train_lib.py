@@ -70,6 +70,9 @@ SIGNATURES = {
     "os2d_train_optim_finalize": (_i, [_p, _sz, _f, _p, _p]),
     "os2d_train_optim_prepare": (_i, [_p, _i, _p, _d, _d, _p, _p]),
     "os2d_train_optim_update": (_i, [_i, _p, _i, _p, _p, _d, _d, _d, _p]),
+    "os2d_train_range_plan_ints": (_sz, []),
+    "os2d_train_range_plan_doubles": (_sz, []),
+    "os2d_train_range_plan": (_i, [_i] + [_p] * 6 + [_d] + [_p] * 6 + [_d] + [_p] * 4),
 }
 
 LIBRARY = NativeLibrary(build.TRAIN, SIGNATURES, ABI_VERSION, "os2d_train_abi_version", "os2d_train_last_error", "the head's backward pass")

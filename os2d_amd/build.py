@@ -62,8 +62,10 @@ TRAIN_CSRC = os.path.join(HERE, "csrc_train")
 # bn_live.hip: batch-statistics BatchNorm of the TransformNet (statistics, normalise + ReLU, backward through the statistics)
 # optim.hip: gradient norm, clip, NaN guard and the SGD / Adam step as multi-tensor kernels; needs no flag either: every function
 #            of it that rounds switches contraction off itself
+# range_plan.hip: BatchNorm fold, bounds and exponents of the f16x3 packing in float64 - what a parameter change makes stale every
+#                 step (here and not in libos2d_hip.so, whose kernel set is pinned); contraction off in its own functions as well
 TRAIN = Library("libos2d_train.so", TRAIN_CSRC, ["train.hip", "train_gemm.hip", "decode_backward.hip", "objective.hip", "mining.hip", "shb_planes.hip", "bn_live.hip",
-                                                 "optim.hip"],
+                                                 "optim.hip", "range_plan.hip"],
                 FLAGS + PACKED_OFF,
                 {"objective.hip": ["-ffp-contract=off"]},
                 [TRAIN_CSRC, CSRC, SHARED], "os2d_train.h", "OS2D_TRAIN_LIB")

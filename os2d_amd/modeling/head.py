@@ -29,7 +29,7 @@ import weakref
 import torch
 import torch.nn as nn
 
-from .. import _lib
+from .. import _lib, _train_lib
 from ..structures.feature_map import FeatureMapSize
 from .box_coder import BoxGridGenerator
 from . import head_train
@@ -47,6 +47,18 @@ PRECISIONS = {"f32": 0, "f16x3": 1, "f16x2": 2, "fft": 3, "fftx3": 4, "fft32": 5
 FFT_MODES = ("fft", "fftx3", "fft32")
 FP32_MODES = ("f32", "fft32")           # no fp16 value anywhere: fp32-MFMA correlation and 5x5 layers
 DEFAULT_PRECISION = "fftx3"
+RANGE_PLAN_ROUTES = ("device", "torch")         # who computes the exponents of the f16x3 packing: os2d_train_range_plan | range_plan()
+DEFAULT_RANGE_PLAN = "device"                   # measured: DESIGN.md section 10.3 (re-pack 0.93 - 1.2 ms -> 0.20 - 0.23 ms, tools/time_repack.py)
+
+
+def resolve_range_plan_route(route=None):
+    """"device": one os2d_train_range_plan call (libos2d_train.so; three launches, no float64 torch operator); "torch": ``TransformationNet.range_plan``,
+    the float64 reference.  Default from $OS2D_RANGE_PLAN, else DEFAULT_RANGE_PLAN."""
+    if route is None:
+        route = os.environ.get("OS2D_RANGE_PLAN", DEFAULT_RANGE_PLAN)
+    if route not in RANGE_PLAN_ROUTES:
+        raise ValueError("range plan route must be one of {}, got {!r}".format(RANGE_PLAN_ROUTES, route))
+    return route
 
 
 def resolve_precision(precision=None):
@@ -101,6 +113,9 @@ class TransformationNet(nn.Module):
     BatchNorm, ReLU, Conv 128->64 k5, BatchNorm, ReLU) and ``linear`` = Conv 64->output_dim k5, the latter
     initialised to the identity transform.  The compute is the MFMA implicit-GEMM kernels; ``packed()`` folds
     eval-mode BatchNorm and re-lays the filters out for them (cached until a parameter changes)."""
+
+    # who computes the exponents of ``packed("f16x3")``: one of RANGE_PLAN_ROUTES; None: follow $OS2D_RANGE_PLAN
+    range_plan_route = None
 
     def __init__(self, output_dim=6, use_cuda=True, normalization="batchnorm", kernel_sizes=[7, 5],
                  channels=[128, 64], input_feature_dim=15 * 15, num_groups=16):
@@ -274,6 +289,56 @@ class TransformationNet(nn.Module):
         return dict(in_exp=[e0, e1, e2], out_exp=[e1, e2, None], unit_exp=e1 - 15,
                     weight_exp=[weight_exp(w1, e0), weight_exp(w2, e1), weight_exp(w3, e2)], bounds=(bound1, bound2))
 
+    _RANGE_PLAN_FIELDS = (128, 128, 128, 64, 64, 8)     # wexp1 | e1 | unit_exp | wexp2 | e2 | wexp3: include/os2d_train.h, os2d_train_range_plan
+
+    def _range_plan_buffers(self):
+        """(exps, bounds) of ONE os2d_train_range_plan call on the current stream: the int32 exponents in the layout of
+        include/os2d_train.h and the float64 bounds B1 | B2 as their int64 bit patterns - no float64 tensor exists until somebody
+        asks for the bounds (``range_plan_device``).  Cached under the key of the packing until a parameter changes; the entry
+        carries the event of the launches, so another stream may consume it."""
+        key = ("range_plan",) + self._state_key()
+        dev = self.check_ready()
+        cached = self._packed_cache.get("range_plan")
+        if cached is not None and cached.key == key:
+            return cached.get(dev)
+        lib = _train_lib.load()
+        assert sum(self._RANGE_PLAN_FIELDS) == lib.os2d_train_range_plan_ints()
+        with torch.cuda.device(dev):
+            held, args = [], [self.output_dim]
+            for conv, bn in ((self.conv[0], self.conv[1]), (self.conv[3], self.conv[4])):
+                held += [_require_device_f32(t.detach(), "TransformNet parameter")
+                         for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+                args += [_lib.ptr(t) for t in held[-6:]] + [ctypes.c_double(float(bn.eps))]      # the Python float, as ``_folded``
+            held.append(_require_device_f32(self.linear.weight.detach(), "TransformNet parameter"))
+            exps = torch.empty(lib.os2d_train_range_plan_ints(), dtype=torch.int32, device=dev)
+            bounds = torch.empty(lib.os2d_train_range_plan_doubles(), dtype=torch.int64, device=dev)
+            _train_lib.check(lib.os2d_train_range_plan(*args, _lib.ptr(held[-1]), _lib.ptr(exps), _lib.ptr(bounds), _lib.current_stream(dev)),
+                             "os2d_train_range_plan")
+            result = (exps, bounds)
+            self._packed_cache["range_plan"] = _StreamOrdered(key, result, dev)
+        return result
+
+    def _plan_views(self, exps, bounds):
+        """The dict of ``range_plan`` as views of the buffers of ``_range_plan_buffers`` (``bounds``: float64 [192] or None)."""
+        wexp1, e1, unit_exp, wexp2, e2, wexp3 = exps.split(self._RANGE_PLAN_FIELDS)
+        e0 = torch.full((225,), _lib.load().os2d_rnorm_exp(), dtype=torch.int32, device=exps.device)
+        return dict(in_exp=[e0, e1, e2], out_exp=[e1, e2, None], unit_exp=unit_exp, weight_exp=[wexp1, wexp2, wexp3[:self.output_dim]],
+                    bounds=None if bounds is None else tuple(bounds.split((128, 64))))
+
+    def range_plan_device(self):
+        """``range_plan`` computed on the device from the raw fp32 parameters (os2d_amd/csrc_train/range_plan.hip): BatchNorm fold, bounds
+        and exponents in float64, one os2d_train_range_plan call on the current stream, no host wait and no torch operator on the
+        parameters.  Same dict; the values are views of the call's two device buffers.  The exponents equal those of
+        ``range_plan`` unless a quotient lies within rounding noise of a power of two (the kernel takes the exact floor of log2)."""
+        exps, bounds = self._range_plan_buffers()
+        return self._plan_views(exps, bounds.view(torch.float64))
+
+    def _f16x3_plan(self):
+        """The plan ``packed("f16x3")`` and ``spectra2`` use, from the route of ``range_plan_route`` (its bounds only on "torch")."""
+        if resolve_range_plan_route(self.range_plan_route) == "torch":
+            return self.range_plan()
+        return self._plan_views(self._range_plan_buffers()[0], None)
+
     def packed(self, precision=None):
         """Packed TransformNet for the kernels: (w1, b1, w2, b2, w3, b3).
         precision "f32": os2d_pack_conv layouts; "f16x3": the split-half layout of os2d_pack_conv_f16x3 with the scales
@@ -297,7 +362,7 @@ class TransformationNet(nn.Module):
             cur = torch.cuda.current_stream(dev)
             out = []
             P = self.output_dim
-            plan = self.range_plan() if precision == "f16x3" else None
+            plan = self._f16x3_plan() if precision == "f16x3" else None
             if plan is not None:
                 # the exponents of the activation buffers this packing reads and writes (``activation_exponents``)
                 act = tuple(e.to(dev).contiguous() for e in (plan["in_exp"][0], plan["out_exp"][0], plan["out_exp"][1]))
@@ -377,7 +442,7 @@ class TransformationNet(nn.Module):
         2^-unit_exp[c] of ``range_plan``: the layer-1 inverse transform stores channel c times 2^unit_exp[c] (<= 1)."""
         def build(P, Q, nbins, dev):
             _, (w2, _), _ = self._folded()                       # float64 [64,128,5,5]: the BatchNorm fold
-            unit_exp = self.range_plan()["unit_exp"].to(w2.device).double()
+            unit_exp = self._f16x3_plan()["unit_exp"].to(w2.device).double()
             w2 = nn.functional.pad(w2 * torch.exp2(-unit_exp).view(1, -1, 1, 1), (1, 1, 1, 1))
             return build_weight_spectra(w2, 128, 64, P, Q, nbins, True, dev)
         return self._cached_spectra(H, W, True, ("conv2",), build)
