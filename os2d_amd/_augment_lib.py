@@ -23,5 +23,5 @@ SIGNATURES = {
     "os2d_augment_color": (_i, [_p, _i, _i, _ll, _i, _p, _p, _p, _p, _i, _p, _p]),
 }
 
-LIBRARY = NativeLibrary(build.AUGMENT, SIGNATURES, ABI_VERSION, "os2d_augment_abi_version", "os2d_augment_last_error", "the device training images")
-lib_path, load, check = LIBRARY.lib_path, LIBRARY.load, LIBRARY.check
+LIBRARY = NativeLibrary(build.AUGMENT, SIGNATURES, ABI_VERSION, "os2d_augment_abi_version", "os2d_augment_last_error", "the device training images", __name__)
+lib_path, load, check, call = LIBRARY.lib_path, LIBRARY.load, LIBRARY.check, LIBRARY.call

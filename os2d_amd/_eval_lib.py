@@ -27,5 +27,5 @@ SIGNATURES = {
     "os2d_eval_finalise": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
 }
 
-LIBRARY = NativeLibrary(build.EVAL, SIGNATURES, ABI_VERSION, "os2d_eval_abi_version", "os2d_eval_last_error", "the device evaluation")
-lib_path, load, check = LIBRARY.lib_path, LIBRARY.load, LIBRARY.check
+LIBRARY = NativeLibrary(build.EVAL, SIGNATURES, ABI_VERSION, "os2d_eval_abi_version", "os2d_eval_last_error", "the device evaluation", __name__)
+lib_path, load, check, call = LIBRARY.lib_path, LIBRARY.load, LIBRARY.check, LIBRARY.call

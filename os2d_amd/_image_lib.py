@@ -18,5 +18,5 @@ SIGNATURES = {
     "os2d_image_resample": (_i, [_p, _i, _i, _i, _ll, _ll, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _p, _p, _i, _p]),
 }
 
-LIBRARY = NativeLibrary(build.IMAGE, SIGNATURES, ABI_VERSION, "os2d_image_abi_version", "os2d_image_last_error", "the device image pyramid")
-lib_path, load, check = LIBRARY.lib_path, LIBRARY.load, LIBRARY.check
+LIBRARY = NativeLibrary(build.IMAGE, SIGNATURES, ABI_VERSION, "os2d_image_abi_version", "os2d_image_last_error", "the device image pyramid", __name__)
+lib_path, load, check, call = LIBRARY.lib_path, LIBRARY.load, LIBRARY.check, LIBRARY.call

@@ -6,7 +6,7 @@ loudly (``Os2dLibraryError``, os2d_amd/_native.py).  Build it with ``python -m o
 import ctypes
 
 from . import build
-from ._native import NativeLibrary, Os2dLibraryError  # noqa: F401  (Os2dLibraryError: imported from here by the package)
+from ._native import NativeLibrary, Os2dLibraryError, ptr, host_ptr, current_stream  # noqa: F401  (re-exported: tests and tools use them from here)
 
 ABI_VERSION = 9
 
@@ -94,32 +94,5 @@ SIGNATURES = {
 }
 
 
-LIBRARY = NativeLibrary(build.HIP, SIGNATURES, ABI_VERSION, "os2d_abi_version", "os2d_last_error", "the OS2D head")
-lib_path, load, check = LIBRARY.lib_path, LIBRARY.load, LIBRARY.check
-
-
-def ptr(t):
-    """Device address of a contiguous float32 CUDA/HIP tensor (None -> NULL)."""
-    if t is None:
-        return None
-    import torch
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (torch.float32, torch.float64, torch.uint8, torch.int32, torch.int64)
-            and t.is_contiguous()):
-        raise ValueError("expected a contiguous device tensor, got {}".format(
-            (type(t).__name__, getattr(t, "device", None), getattr(t, "dtype", None))))
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def host_ptr(t):
-    """Address of a PINNED host tensor (hipHostMalloc memory is mapped into the device address space under the same
-    address: kernels may store to it); None -> NULL."""
-    if t is None:
-        return None
-    if not t.is_pinned():
-        raise ValueError("expected a pinned host tensor")
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def current_stream(device):
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+LIBRARY = NativeLibrary(build.HIP, SIGNATURES, ABI_VERSION, "os2d_abi_version", "os2d_last_error", "the OS2D head", __name__)
+lib_path, load, check, call = LIBRARY.lib_path, LIBRARY.load, LIBRARY.check, LIBRARY.call

@@ -75,5 +75,5 @@ SIGNATURES = {
     "os2d_train_range_plan": (_i, [_i] + [_p] * 6 + [_d] + [_p] * 6 + [_d] + [_p] * 4),
 }
 
-LIBRARY = NativeLibrary(build.TRAIN, SIGNATURES, ABI_VERSION, "os2d_train_abi_version", "os2d_train_last_error", "the head's backward pass")
-lib_path, load, check = LIBRARY.lib_path, LIBRARY.load, LIBRARY.check
+LIBRARY = NativeLibrary(build.TRAIN, SIGNATURES, ABI_VERSION, "os2d_train_abi_version", "os2d_train_last_error", "the head's backward pass", __name__)
+lib_path, load, check, call = LIBRARY.lib_path, LIBRARY.load, LIBRARY.check, LIBRARY.call

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from .. import _augment_lib, _image_lib
+from .._native import STREAM, raw_ptr
 from ..structures.feature_map import FeatureMapSize
 from .pyramid import DEFAULT_SCALES
 
@@ -212,18 +213,10 @@ def _resample(x, window, hflip, vflip, ow, oh, lut, filter="bilinear", padded=Fa
     else:
         out = torch.empty((A, 3, oh, ow), dtype=torch.float32, device=device)
     # a window that may leave the image: the same kernel template, instantiated in libos2d_augment.so
-    entry = _augment_lib.load().os2d_augment_resample_padded if padded else _image_lib.load().os2d_image_resample
-    p = ctypes.c_void_p
-    with torch.cuda.device(device):
-        stream = p(torch.cuda.current_stream(device).cuda_stream)
-        rc = entry(p(x.data_ptr()), A, img_w, img_h, x.stride(1), x.stride(0), x0, y0, w, h, int(bool(hflip)), int(bool(vflip)),
-                   p(xcoef.data_ptr()), p(xb.data_ptr()), p(xb_host.ctypes.data), kx, p(ycoef.data_ptr()), p(yb.data_ptr()),
-                   p(yb_host.ctypes.data), ky, ow, oh, p(lut.data_ptr()) if lut is not None else None, p(out.data_ptr()),
-                   int(lut is None), stream)
-    if padded:
-        _augment_lib.check(rc, "os2d_augment_resample_padded")
-    else:
-        _image_lib.check(rc, "os2d_image_resample")
+    lib, entry = (_augment_lib, "os2d_augment_resample_padded") if padded else (_image_lib, "os2d_image_resample")
+    # x goes in by its strides (_as_batch lets padded rows through); the host copies of the bounds are numpy arrays
+    lib.call(entry, raw_ptr(x), A, img_w, img_h, x.stride(1), x.stride(0), x0, y0, w, h, int(bool(hflip)), int(bool(vflip)), xcoef, xb,
+             xb_host.ctypes.data, kx, ycoef, yb, yb_host.ctypes.data, ky, ow, oh, lut, out, int(lut is None), STREAM)
     return out
 
 
@@ -307,13 +300,7 @@ def distort_image(image_u8, ops, to_float=False, img_normalization=IMAGENET_NORM
     sums = torch.empty(_augment_lib.COLOR_SLOTS, dtype=torch.int64, device=device) if any(k == CONTRAST for k, _ in ops) else None
     kinds = (ctypes.c_int * max(len(ops), 1))(*[k for k, _ in ops])
     factors = (ctypes.c_double * max(len(ops), 1))(*[f for _, f in ops])
-    p = ctypes.c_void_p
-    with torch.cuda.device(device):
-        stream = p(torch.cuda.current_stream(device).cuda_stream)
-        rc = _augment_lib.load().os2d_augment_color(p(x.data_ptr()), w, h, x.stride(1), len(ops), kinds, factors,
-                                                p(lut.data_ptr()) if lut is not None else None, p(out.data_ptr()), int(lut is None),
-                                                p(sums.data_ptr()) if sums is not None else None, stream)
-    _augment_lib.check(rc, "os2d_augment_color")
+    _augment_lib.call("os2d_augment_color", raw_ptr(x), w, h, x.stride(1), len(ops), kinds, factors, lut, out, int(lut is None), sums, STREAM)
     return out
 
 

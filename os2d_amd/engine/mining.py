@@ -19,8 +19,8 @@ from collections import OrderedDict
 
 import torch
 
-from .. import _lib
 from .. import _train_lib
+from .._native import STREAM
 from ..modeling.box_ops import MAX_BOX_OPS, as_box_ops, ops_tables
 from ..structures.bounding_box import BoxList
 from ..structures.feature_map import FeatureMapSize
@@ -127,12 +127,9 @@ def mine_select(per_anchor, cls_scores_pyramid, corners_pyramid, img_size_pyrami
                torch.empty(A, 3, K, VALUE_FLOATS, dtype=torch.float32, device=dev))
     count, index, values = out
     g = box_grid_generator
-    with torch.cuda.device(dev):
-        _train_lib.check(tl.os2d_train_mine_select(
-            A, B, L, c_hw, c_img, c_rows, int(g.box_stride.w), int(g.box_size.w), c_counts, c_kinds, c_args, arrays["cls_loss"],
-            arrays["loc_loss"], arrays["flags"], arrays["cls_preds"], arrays["corners"], int(crop_size.w), int(crop_size.h),
-            ctypes.c_float(nms_iou_threshold), K, _lib.ptr(count), _lib.ptr(index), _lib.ptr(values), _lib.ptr(ws), ws.numel(),
-            _lib.current_stream(dev)), "os2d_train_mine_select")
+    _train_lib.call("os2d_train_mine_select", A, B, L, c_hw, c_img, c_rows, int(g.box_stride.w), int(g.box_size.w), c_counts, c_kinds,
+                    c_args, arrays["cls_loss"], arrays["loc_loss"], arrays["flags"], arrays["cls_preds"], arrays["corners"],
+                    int(crop_size.w), int(crop_size.h), nms_iou_threshold, K, count, index, values, ws, ws.numel(), STREAM)
     return count, index, values
 
 

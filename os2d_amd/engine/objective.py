@@ -10,14 +10,13 @@ RLL uses every negative: the reference sets ``neg_to_pos_ratio = inf`` for it an
 which saturates to the largest int64 on a device (and to the smallest on the CPU, where no negative would be used); the
 device's behaviour is the one the reference's comment intends and the one implemented here.
 """
-import ctypes
 from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 
-from .. import _lib
 from .. import _train_lib
+from .._native import STREAM
 
 CLASS_LOSSES = {"contrastiveloss": 0, "rll": 1}
 F_POS, F_NEG, F_POSREG = 1, 2, 4        # bits of the per-element flags (include/os2d_train.h)
@@ -39,14 +38,10 @@ class _ObjectiveFunction(torch.autograd.Function):
         flags = torch.empty(A, B, HW, dtype=torch.uint8, device=dev)
         coef = torch.empty(A, B, HW, **f32)
         ws = torch.empty(int(tl.os2d_train_objective_workspace_floats(A, B, HW)), **f32)
-        p = _lib.ptr
-        with torch.cuda.device(dev):
-            _train_lib.check(tl.os2d_train_objective_forward(
-                crit._kind, 1 if patch else 0, p(loc_preds), p(loc_targets), p(cls_preds), p(cls_targets), p(cls_targets_remapped),
-                p(cls_preds_for_neg), A, B, HW, ctypes.c_float(crit.margin), ctypes.c_float(crit.margin_pos),
-                ctypes.c_float(crit.class_loss_neg_weight), ctypes.c_float(crit.localization_weight),
-                ctypes.c_float(float(crit.neg_to_pos_ratio)), ctypes.c_double(float(crit.rll_neg_weight_ratio)), p(losses), p(cls_loss),
-                p(loc_loss), p(flags), p(coef), p(ws), ws.numel(), _lib.current_stream(dev)), "os2d_train_objective_forward")
+        _train_lib.call("os2d_train_objective_forward", crit._kind, 1 if patch else 0, loc_preds, loc_targets, cls_preds, cls_targets,
+                        cls_targets_remapped, cls_preds_for_neg, A, B, HW, crit.margin, crit.margin_pos, crit.class_loss_neg_weight,
+                        crit.localization_weight, float(crit.neg_to_pos_ratio), float(crit.rll_neg_weight_ratio), losses, cls_loss,
+                        loc_loss, flags, coef, ws, ws.numel(), STREAM)
         ctx.crit, ctx.shape = crit, (A, B, HW)
         ctx.has_neg = cls_preds_for_neg is not None
         ctx.saved = (loc_preds, loc_targets, flags, coef, ws)
@@ -56,7 +51,6 @@ class _ObjectiveFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlosses, *_):
-        tl = _train_lib.load()
         crit, (A, B, HW) = ctx.crit, ctx.shape
         loc_preds, loc_targets, flags, coef, ws = ctx.saved
         dev = flags.device
@@ -67,13 +61,9 @@ class _ObjectiveFunction(torch.autograd.Function):
         has_neg = ctx.has_neg
         dneg = torch.empty(A, B, HW, **f32) if has_neg else None     # with cls_preds_for_neg the negatives' term goes there
         g = dlosses.contiguous()                                    # element 0 = d loss; the other scalars are for logging
-        p = _lib.ptr
-        with torch.cuda.device(dev):
-            if need_loc or need_cls or has_neg:
-                _train_lib.check(tl.os2d_train_objective_backward(
-                    p(g), p(loc_preds), p(loc_targets), p(flags), p(coef), p(ws), A, B, HW, ctypes.c_float(crit.class_loss_neg_weight),
-                    ctypes.c_float(crit.localization_weight), p(dloc), p(dcls), p(dneg), _lib.current_stream(dev)),
-                    "os2d_train_objective_backward")
+        if need_loc or need_cls or has_neg:
+            _train_lib.call("os2d_train_objective_backward", g, loc_preds, loc_targets, flags, coef, ws, A, B, HW,
+                            crit.class_loss_neg_weight, crit.localization_weight, dloc, dcls, dneg, STREAM)
         return None, None, dloc, None, dcls, None, None, (dneg if need_neg else None)
 
 

@@ -10,15 +10,14 @@ keys (``momentum_buffer``; ``step`` as a 0-dim device float tensor, ``exp_avg``,
 ``clip_grad_norm_`` + ``if not isnan(norm): step()`` decided on the device: it returns the norm as a device scalar and never
 waits for the device.
 """
-import ctypes
 import logging
 from statistics import median
 
 import torch
 from torch import optim
 
-from .. import _lib
 from .. import _train_lib
+from .._native import STREAM
 
 MAX_TENSORS = _train_lib.OPTIM_MAX_TENSORS      # tensors per launch (the table travels in the kernel arguments)
 CHUNK = _train_lib.OPTIM_CHUNK                  # elements per work-group
@@ -219,23 +218,20 @@ class _DeviceStep(object):
                 for p in group["params"]:
                     return torch.zeros((), dtype=torch.float32, device=p.device)
         dev = plan.entries[0][0].device
-        tl = _train_lib.load()
         adam = self._method == _train_lib.OPTIM_ADAM
         partials = torch.empty(max(plan.total_chunks, 1), dtype=torch.float64, device=dev)
         record = torch.empty(4, dtype=torch.float32, device=dev)
         factors = torch.empty(2 * len(plan.entries), dtype=torch.float32, device=dev) if adam else None
-        pp, rp = ctypes.c_void_p(partials.data_ptr()), ctypes.c_void_p(record.data_ptr())
-        with torch.cuda.device(dev):
-            stream = _lib.current_stream(dev)
-            for arr, n, _, _ in plan.tables:
-                _train_lib.check(tl.os2d_train_optim_sumsq(arr, n, pp, plan.total_chunks, stream), "os2d_train_optim_sumsq")
-            _train_lib.check(tl.os2d_train_optim_finalize(pp, plan.total_chunks, max_norm, rp, stream), "os2d_train_optim_finalize")
-            for arr, n, offset, (h0, h1, h2) in plan.tables:
-                fp = None
-                if adam:
-                    fp = ctypes.c_void_p(factors.data_ptr() + 8 * offset)
-                    _train_lib.check(tl.os2d_train_optim_prepare(arr, n, rp, h0, h1, fp, stream), "os2d_train_optim_prepare")
-                _train_lib.check(tl.os2d_train_optim_update(self._method, arr, n, rp, fp, h0, h1, h2, stream), "os2d_train_optim_update")
+        call = _train_lib.call
+        for arr, n, _, _ in plan.tables:
+            call("os2d_train_optim_sumsq", arr, n, partials, plan.total_chunks, STREAM)
+        call("os2d_train_optim_finalize", partials, plan.total_chunks, max_norm, record, STREAM)
+        for arr, n, offset, (h0, h1, h2) in plan.tables:
+            fp = None
+            if adam:
+                fp = factors[2 * offset:]          # this table's (two floats per tensor) factors
+                call("os2d_train_optim_prepare", arr, n, record, h0, h1, fp, STREAM)
+            call("os2d_train_optim_update", self._method, arr, n, record, fp, h0, h1, h2, STREAM)
         self._last = (record, factors)        # read by the stage tests: {norm, coef, skip, 0} and the per-tensor Adam factors
         return record[0]
 

@@ -27,16 +27,16 @@ are in range, which host-side ground truth is checked for; it then counts as a f
 behind every class with the key ``num_labels`` (``sorted_labels`` holds ``num_labels`` for those rows, and
 ``class_offsets[num_labels]`` is the number of detections in range): the per-class numbers are those without it.
 """
-import ctypes
-
 import torch
 
 from .. import _eval_lib
+from .._native import STREAM
 from ..structures.bounding_box import BoxList  # noqa: F401  (the type of the arguments)
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+def _n(t):
+    """The kernels take NULL for an array without elements (no detections, no ground truth)."""
+    return t if t is not None and t.numel() else None
 
 
 def _to_device(host, device):
@@ -137,61 +137,51 @@ class VocEvaluator(object):
         if host_gt and (max(int(l.max()) for l in host_gt) >= L or min(int(l.min()) for l in host_gt) < 0):
             raise ValueError("VocEvaluator: a ground-truth label lies outside [0, num_labels = {})".format(L))
         p["L"] = L
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         # [class_offsets (L+1) | n_pos (L+1) | gt_count (L)]: one buffer, one device-to-host copy when the curves are asked for
         meta = torch.empty(3 * L + 2, dtype=torch.int32, device=dev)
         p["meta"] = meta
         p["class_offsets"], p["n_pos"], p["gt_count"] = meta[:L + 1], meta[L + 1:2 * L + 2], meta[2 * L + 2:]
-        _eval_lib.check(lib.os2d_eval_count_gt(_ptr(p["gt_labels"]), _ptr(p["gt_difficult"]), G, L, _ptr(p["n_pos"]), _ptr(p["gt_count"]),
-                                               stream), "os2d_eval_count_gt")
+        _eval_lib.call("os2d_eval_count_gt", _n(p["gt_labels"]), _n(p["gt_difficult"]), G, L, _n(p["n_pos"]), _n(p["gt_count"]), STREAM)
         p["perm_joint"] = torch.empty(D, dtype=torch.int32, device=dev)
         p["perm_class"] = torch.empty(D, dtype=torch.int32, device=dev)
         p["sorted_labels"] = torch.empty(D, dtype=torch.int32, device=dev)
         ws = torch.empty(lib.os2d_eval_sort_workspace_bytes(D), dtype=torch.uint8, device=dev)
-        _eval_lib.check(lib.os2d_eval_sort(_ptr(p["det_scores"]), _ptr(p["det_labels"]), D, L, max(L - 1, 0).bit_length(),
-                                           _ptr(p["perm_joint"]), _ptr(p["perm_class"]), _ptr(p["sorted_labels"]), _ptr(p["class_offsets"]),
-                                           _ptr(ws), ws.numel(), stream), "os2d_eval_sort")
+        _eval_lib.call("os2d_eval_sort", _n(p["det_scores"]), _n(p["det_labels"]), D, L, max(L - 1, 0).bit_length(), _n(p["perm_joint"]),
+                       _n(p["perm_class"]), _n(p["sorted_labels"]), _n(p["class_offsets"]), _n(ws), ws.numel(), STREAM)
         p["scan_ws"] = torch.empty(lib.os2d_eval_scan_workspace_bytes(D), dtype=torch.uint8, device=dev)
         self._packed = p
         return p
 
     # ------------------------------------------------------------------------------------------------ stages
     def _match(self, p, iou_thresh):
-        lib = _eval_lib.load()
         dev, D, G = p["device"], p["D"], p["G"]
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         match = torch.empty(D, dtype=torch.int8, device=dev)
         gt_index = torch.empty(D, dtype=torch.int32, device=dev)
         winner = torch.empty(G, dtype=torch.int64, device=dev)
-        _eval_lib.check(lib.os2d_eval_match(_ptr(p["det_boxes"]), _ptr(p["det_scores"]), _ptr(p["det_labels"]), _ptr(p["det_offsets"]), D,
-                                            p["N"], _ptr(p["gt_boxes"]), _ptr(p["gt_labels"]), _ptr(p["gt_difficult"]), _ptr(p["gt_offsets"]),
-                                            G, float(iou_thresh), _ptr(gt_index), _ptr(winner), _ptr(match), stream), "os2d_eval_match")
+        _eval_lib.call("os2d_eval_match", _n(p["det_boxes"]), _n(p["det_scores"]), _n(p["det_labels"]), _n(p["det_offsets"]), D, p["N"],
+                       _n(p["gt_boxes"]), _n(p["gt_labels"]), _n(p["gt_difficult"]), _n(p["gt_offsets"]), G, float(iou_thresh),
+                       _n(gt_index), _n(winner), _n(match), STREAM)
         return match
 
     def _curves(self, p, match, joint, rec_last):
         """tp/fp, prec and rec of the per-class (joint=False) or the joint-classes ordering."""
-        lib = _eval_lib.load()
         dev, D, L = p["device"], p["D"], p["L"]
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         tpfp = torch.empty(D, dtype=torch.int64, device=dev)
         prec = torch.empty(D, dtype=torch.float64, device=dev)
         rec = torch.empty(D, dtype=torch.float64, device=dev)
         perm = p["perm_joint"] if joint else p["perm_class"]
         seg = None if joint else p["sorted_labels"]
         n_pos = p["n_pos"][L:] if joint else p["n_pos"]
-        _eval_lib.check(lib.os2d_eval_prec_rec(_ptr(match), _ptr(perm), _ptr(seg), _ptr(n_pos), 1 if joint else L, D, _ptr(tpfp), _ptr(prec),
-                                               _ptr(rec), _ptr(rec_last[L:] if joint else rec_last), _ptr(p["scan_ws"]), p["scan_ws"].numel(),
-                                               stream), "os2d_eval_prec_rec")
+        _eval_lib.call("os2d_eval_prec_rec", _n(match), _n(perm), _n(seg), _n(n_pos), 1 if joint else L, D, _n(tpfp), _n(prec), _n(rec),
+                       _n(rec_last[L:] if joint else rec_last), _n(p["scan_ws"]), p["scan_ws"].numel(), STREAM)
         return tpfp, prec, rec
 
     def _ap(self, p, prec, rec, joint, use_07_metric, acc):
-        lib = _eval_lib.load()
         dev, D, L = p["device"], p["D"], p["L"]
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         mpre = torch.empty(D, dtype=torch.float64, device=dev)
         seg = None if joint else p["sorted_labels"]
-        _eval_lib.check(lib.os2d_eval_ap(_ptr(prec), _ptr(rec), _ptr(seg), 1 if joint else L, D, int(bool(use_07_metric)), _ptr(mpre),
-                                         _ptr(acc[L:] if joint else acc), _ptr(p["scan_ws"]), p["scan_ws"].numel(), stream), "os2d_eval_ap")
+        _eval_lib.call("os2d_eval_ap", _n(prec), _n(rec), _n(seg), 1 if joint else L, D, int(bool(use_07_metric)), _n(mpre),
+                       _n(acc[L:] if joint else acc), _n(p["scan_ws"]), p["scan_ws"].numel(), STREAM)
         return mpre
 
     def compute(self, iou_thresh=0.5, use_07_metric=False, with_curves=True):
@@ -199,10 +189,8 @@ class VocEvaluator(object):
         ``n_pos`` are fp64 tensors of length num_labels, ``map``, ``map_weighted``, ``recall``, ``ap_joint_classes`` 0-dim
         fp64 tensors, ``prec`` / ``rec`` lists of per-class views into the class-sorted arrays (None where the reference has
         None; left out with ``with_curves=False``)."""
-        lib = _eval_lib.load()
         p = self._pack()
         dev, L = p["device"], p["L"]
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         match = self._match(p, iou_thresh)
         rec_last = torch.zeros(L + 1, dtype=torch.float64, device=dev)
         acc = torch.zeros(L + 1, 11, dtype=torch.float64, device=dev)
@@ -212,8 +200,8 @@ class VocEvaluator(object):
         mpre_j = self._ap(p, prec_j, rec_j, True, use_07_metric, acc)
         out = torch.empty(3 * L + 4, dtype=torch.float64, device=dev)
         ap, recall_pc, n_pos, scalars = out[:L], out[L:2 * L], out[2 * L:3 * L], out[3 * L:]
-        _eval_lib.check(lib.os2d_eval_finalise(_ptr(acc), _ptr(rec_last), _ptr(p["n_pos"]), L, int(bool(use_07_metric)), _ptr(ap),
-                                               _ptr(recall_pc), _ptr(n_pos), _ptr(scalars), stream), "os2d_eval_finalise")
+        _eval_lib.call("os2d_eval_finalise", _n(acc), _n(rec_last), _n(p["n_pos"]), L, int(bool(use_07_metric)), _n(ap), _n(recall_pc),
+                       _n(n_pos), _n(scalars), STREAM)
         self.last = dict(match=match, tpfp=tpfp, prec=prec, rec=rec, mpre=mpre, tpfp_joint=tpfp_j, prec_joint=prec_j, rec_joint=rec_j,
                          mpre_joint=mpre_j, perm_class=p["perm_class"], perm_joint=p["perm_joint"], class_offsets=p["class_offsets"],
                          n_pos_joint=p["n_pos"][L])
@@ -289,14 +277,12 @@ def calc_detection_voc_ap(prec, rec, use_07_metric=False):
     D = sum(lengths)
     acc = torch.zeros(n, 11, dtype=torch.float64, device=dev)
     if D:
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         p = torch.cat([prec[l].to(torch.float64) for l in have]).contiguous()
         r = torch.cat([rec[l].to(torch.float64) for l in have]).contiguous()
         seg = _to_device(torch.repeat_interleave(torch.tensor(have, dtype=torch.int32), torch.tensor(lengths)), dev)
         mpre = torch.empty(D, dtype=torch.float64, device=dev)
         ws = torch.empty(lib.os2d_eval_scan_workspace_bytes(D), dtype=torch.uint8, device=dev)
-        _eval_lib.check(lib.os2d_eval_ap(_ptr(p), _ptr(r), _ptr(seg), n, D, int(bool(use_07_metric)), _ptr(mpre), _ptr(acc), _ptr(ws),
-                                         ws.numel(), stream), "os2d_eval_ap")
+        _eval_lib.call("os2d_eval_ap", _n(p), _n(r), _n(seg), n, D, int(bool(use_07_metric)), _n(mpre), _n(acc), _n(ws), ws.numel(), STREAM)
     if use_07_metric:
         total = torch.zeros(n, dtype=torch.float64, device=dev)
         for t in range(11):

@@ -27,6 +27,7 @@ import torch
 
 from .. import _lib
 from .. import _train_lib
+from .._native import STREAM
 from ..structures.feature_map import FeatureMapSize
 from ..structures.bounding_box import BoxList, FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM          # noqa: F401 (the flips: re-exported)
 from .box_ops import (OP_SCALE, OP_HFLIP, OP_VFLIP, OP_SHIFT, MAX_BOX_OPS, MAX_DEFAULT_BOX_OPS,          # noqa: F401 (re-exported)
@@ -70,16 +71,12 @@ class BoxGridGenerator(object):
         if device.type != "cuda":
             raise RuntimeError("get_box_to_cut_anchor runs on the HIP device only (no CPU fallback), got {}".format(device))
         ops, out_size = traced_box_ops(default_box_transform, img_size)
-        tl = _train_lib.load()
         HW = fm_size.h * fm_size.w
         crops = torch.empty(HW, 4, dtype=torch.float32, device=device)
         anchors = torch.empty(HW, 4, dtype=torch.float32, device=device)
         _, kinds, args = ops_tables([ops])
-        with torch.cuda.device(device):
-            _train_lib.check(tl.os2d_train_crop_boxes(fm_size.h, fm_size.w, int(self.box_stride.w), int(self.box_size.w), int(img_size.w),
-                                                      int(img_size.h), int(crop_size.w), int(crop_size.h), len(ops), kinds, args,
-                                                      _lib.ptr(crops), _lib.ptr(anchors), _lib.current_stream(device)),
-                             "os2d_train_crop_boxes")
+        _train_lib.call("os2d_train_crop_boxes", fm_size.h, fm_size.w, int(self.box_stride.w), int(self.box_size.w), int(img_size.w),
+                        int(img_size.h), int(crop_size.w), int(crop_size.h), len(ops), kinds, args, crops, anchors, STREAM)
         return BoxList(crops, out_size), BoxList(anchors, out_size), torch.arange(HW, device=device)
 
 
@@ -188,17 +185,13 @@ class Os2dBoxCoder(object):
     def decode_level(self, loc_scores, img_size):
         """loc_scores [NB,4,HW] device tensor -> boxes [NB,HW,4] xyxy clipped to the level image
         (reference box_coder.py:319-330 + bounding_box.py:261-265) with os2d_decode_boxes."""
-        lib = _lib.load()
         _require_device(loc_scores)
         loc_scores = loc_scores.contiguous()
         fm = self.get_feature_map_size(img_size)
         NB, four, HW = loc_scores.shape
         assert four == 4 and HW == fm.w * fm.h, "loc_scores {} do not match the feature map {}".format(tuple(loc_scores.shape), fm)
         boxes = torch.empty(NB, HW, 4, dtype=torch.float32, device=loc_scores.device)
-        with torch.cuda.device(loc_scores.device):       # launches act on the CURRENT device
-            _lib.check(lib.os2d_decode_boxes(_lib.ptr(loc_scores), NB, fm.h, fm.w, self._stride, self._rec_field,
-                                             ctypes.c_float(img_size.w), ctypes.c_float(img_size.h), _lib.ptr(boxes),
-                                             _lib.current_stream(loc_scores.device)), "os2d_decode_boxes")
+        _lib.call("os2d_decode_boxes", loc_scores, NB, fm.h, fm.w, self._stride, self._rec_field, img_size.w, img_size.h, boxes, STREAM)
         return boxes
 
     def build_boxes_from_loc_scores(self, loc_scores, default_boxes):
@@ -212,7 +205,6 @@ class Os2dBoxCoder(object):
     @staticmethod
     def nms_sorted(boxes_sorted, counts, iou_threshold):
         """boxes_sorted [NC,N,4] (each list by decreasing score, counts[c] valid) -> keep mask [NC,N] bool."""
-        lib = _lib.load()
         if not boxes_sorted.is_cuda:
             raise RuntimeError("NMS runs on the HIP device only (no CPU fallback)")
         boxes_sorted = boxes_sorted.contiguous().float()
@@ -222,12 +214,9 @@ class Os2dBoxCoder(object):
         keep = torch.empty(NC, N, dtype=torch.uint8, device=dev)
         num_keep = torch.empty(NC, dtype=torch.int32, device=dev)
         nbytes = ctypes.c_size_t()
-        _lib.check(lib.os2d_nms_workspace_bytes(NC, N, ctypes.byref(nbytes)), "os2d_nms_workspace_bytes")
+        _lib.call("os2d_nms_workspace_bytes", NC, N, ctypes.byref(nbytes))
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.os2d_nms(_lib.ptr(boxes_sorted), _lib.ptr(counts), NC, N, ctypes.c_float(iou_threshold),
-                                    _lib.ptr(keep), _lib.ptr(num_keep), _lib.ptr(ws), ws.numel(),
-                                    _lib.current_stream(dev)), "os2d_nms")
+        _lib.call("os2d_nms", boxes_sorted, counts, NC, N, iou_threshold, keep, num_keep, ws, ws.numel(), STREAM)
         return keep.bool()
 
     def _nms_lists(self, boxes, scores, valid, iou_threshold, nms_max_batch=10000):
@@ -413,12 +402,8 @@ class Os2dBoxCoder(object):
         out_scores = torch.empty(B, HW, dtype=torch.float32, device=dev)
         out_index = torch.empty(B, HW, dtype=torch.int32, device=dev)
         out_count = torch.empty(B, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):     # hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device
-            _lib.check(lib.os2d_detect_level_ops(_lib.ptr(loc), _lib.ptr(cls), B, fm.h, fm.w, self._stride, self._rec_field,
-                                                 ctypes.c_float(img_size.w), ctypes.c_float(img_size.h), len(ops), kinds_c, args_c,
-                                                 ctypes.c_float(score_thr), ctypes.c_float(iou_thr),
-                                                 _lib.ptr(out_boxes), _lib.ptr(out_scores), _lib.ptr(out_index),
-                                                 _lib.ptr(out_count), _lib.current_stream(dev)), "os2d_detect_level_ops")
+        _lib.call("os2d_detect_level_ops", loc, cls, B, fm.h, fm.w, self._stride, self._rec_field, img_size.w, img_size.h, len(ops),
+                  kinds_c, args_c, score_thr, iou_thr, out_boxes, out_scores, out_index, out_count, STREAM)
         # rows in the label order of the reference, survivors of a row by score
         order = [rows_of[l][0] for l in labels]
         perm = torch.tensor(order, dtype=torch.long, device=dev) if order != list(range(B)) else None
@@ -501,7 +486,7 @@ class Os2dBoxCoder(object):
         d_counts, d_kinds, d_args = ops_tables([t_[1] for t_ in traced], MAX_DEFAULT_BOX_OPS)
         passes = int(self.fused_pyramid_passes)
         nbytes = ctypes.c_size_t()
-        _lib.check(lib.os2d_detect_pyramid_workspace_bytes(G, N, passes, ctypes.byref(nbytes)), "os2d_detect_pyramid_workspace_bytes")
+        _lib.call("os2d_detect_pyramid_workspace_bytes", G, N, passes, ctypes.byref(nbytes))
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
         out_boxes = torch.empty(G, N, 4, dtype=torch.float32, device=dev)
         out_scores = torch.empty(G, N, dtype=torch.float32, device=dev)
@@ -519,16 +504,11 @@ class Os2dBoxCoder(object):
         c_hw = (ctypes.c_int * (2 * L))(*[v for fm in fms for v in (fm.h, fm.w)])
         c_img = (ctypes.c_float * (2 * L))(*[float(v) for s_ in size_pyr for v in (s_.w, s_.h)])
         identity = labels == ids                         # one row per label, already in the reference's label order
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev):                     # the table's upload and its event
             slot_rows = None if identity else self._slot_rows(tuple(ids), tuple(labels), rows_of, V, dev)
-            _lib.check(lib.os2d_detect_pyramid_ops(c_loc, c_cls, c_cor, B, L, c_hw, self._stride, self._rec_field, c_img,
-                                                   c_counts, c_kinds, c_args, d_counts, d_kinds, d_args,
-                                                   ctypes.c_float(score_thr), ctypes.c_float(iou_thr),
-                                                   int(self.nms_max_batch), passes, G, V, _lib.ptr(slot_rows),
-                                                   _lib.ptr(out_boxes), _lib.ptr(out_scores), _lib.ptr(out_index),
-                                                   _lib.ptr(out_default), _lib.ptr(out_corners), _lib.ptr(out_count),
-                                                   _lib.ptr(unfinished), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
-                       "os2d_detect_pyramid_ops")
+        _lib.call("os2d_detect_pyramid_ops", c_loc, c_cls, c_cor, B, L, c_hw, self._stride, self._rec_field, c_img, c_counts, c_kinds,
+                  c_args, d_counts, d_kinds, d_args, score_thr, iou_thr, int(self.nms_max_batch), passes, G, V, slot_rows, out_boxes,
+                  out_scores, out_index, out_default, out_corners, out_count, unfinished, ws, ws.numel(), STREAM)
         mask = torch.arange(N, device=dev).unsqueeze(0) < out_count.unsqueeze(1)
         row, pos = mask.nonzero(as_tuple=True)                   # the one host synchronisation: sizes the result
         if int(unfinished.item()) != 0:
@@ -559,7 +539,6 @@ class Os2dBoxCoder(object):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("target assignment runs on the HIP device only (no CPU fallback), got {}".format(device))
-        tl = _train_lib.load()
         A, HW = len(batch_boxes), fm.h * fm.w
         gt_boxes, gt_labels, gt_difficult, offsets, n = self._pack_boxes(batch_boxes, device)
         cls_targets = torch.empty(A, num_labels, HW, dtype=torch.int64, device=device)
@@ -570,19 +549,16 @@ class Os2dBoxCoder(object):
             outs = (None, torch.empty(A, num_labels, HW, dtype=torch.float32, device=device),
                     torch.empty(A, num_labels, HW, dtype=torch.float32, device=device))
             high, low = self.remap_classification_targets_iou_pos, self.remap_classification_targets_iou_neg
-        head = (mode, _lib.ptr(gt_boxes) if n else None, _lib.ptr(gt_labels) if n else None, _lib.ptr(gt_difficult) if n else None,
-                _lib.ptr(offsets), n, _lib.ptr(loc_scores), A, num_labels, fm.h, fm.w, self._stride, self._rec_field,
-                ctypes.c_float(high), ctypes.c_float(low))
-        tail = (_lib.ptr(outs[0]), _lib.ptr(cls_targets), _lib.ptr(outs[1]), _lib.ptr(outs[2]), _lib.current_stream(device))
-        with torch.cuda.device(device):
-            if ops is None:
-                _train_lib.check(tl.os2d_train_assign_targets(*(head + tail)), "os2d_train_assign_targets")
-            else:
-                if len(ops) > MAX_BOX_OPS:
-                    raise ValueError("a box-op chain of {} entries: at most {} are supported".format(len(ops), MAX_BOX_OPS))
-                _, kinds, args = ops_tables([ops])
-                _train_lib.check(tl.os2d_train_assign_targets_ops(*(head + (len(ops), kinds, args) + tail)),
-                                 "os2d_train_assign_targets_ops")
+        head = (mode, gt_boxes if n else None, gt_labels if n else None, gt_difficult if n else None, offsets, n, loc_scores, A, num_labels,
+                fm.h, fm.w, self._stride, self._rec_field, high, low)
+        tail = (outs[0], cls_targets, outs[1], outs[2], STREAM)
+        if ops is None:
+            _train_lib.call("os2d_train_assign_targets", *(head + tail))
+        else:
+            if len(ops) > MAX_BOX_OPS:
+                raise ValueError("a box-op chain of {} entries: at most {} are supported".format(len(ops), MAX_BOX_OPS))
+            _, kinds, args = ops_tables([ops])
+            _train_lib.call("os2d_train_assign_targets_ops", *(head + (len(ops), kinds, args) + tail))
         return cls_targets, outs
 
     def encode_batch(self, batch_boxes, img_size, num_labels, device):

@@ -30,6 +30,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, _train_lib
+from .._native import STREAM
 from ..structures.feature_map import FeatureMapSize
 from .box_coder import BoxGridGenerator
 from . import head_train
@@ -222,8 +223,7 @@ class TransformationNet(nn.Module):
             b = _require_device_f32(self.linear.bias.detach(), "conv bias")
             pw = torch.empty(lib.os2d_packed_conv_floats(3), dtype=torch.float32, device=dev)
             pb = torch.zeros(lib.os2d_packed_bias_floats(3), dtype=torch.float32, device=dev)
-            _lib.check(lib.os2d_pack_conv(3, self.output_dim, _lib.ptr(w), _lib.ptr(b), None, None, None, None, ctypes.c_float(0.0),
-                                          _lib.ptr(pw), _lib.ptr(pb), _lib.current_stream(dev)), "os2d_pack_conv")
+            _lib.call("os2d_pack_conv", 3, self.output_dim, w, b, None, None, None, None, 0.0, pw, pb, STREAM)
             result = (pw, pb)
             self._packed_cache["linear.f32"] = _StreamOrdered(key, result, dev)
         return result
@@ -308,12 +308,11 @@ class TransformationNet(nn.Module):
             for conv, bn in ((self.conv[0], self.conv[1]), (self.conv[3], self.conv[4])):
                 held += [_require_device_f32(t.detach(), "TransformNet parameter")
                          for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-                args += [_lib.ptr(t) for t in held[-6:]] + [ctypes.c_double(float(bn.eps))]      # the Python float, as ``_folded``
+                args += held[-6:] + [float(bn.eps)]      # the Python float, as ``_folded``
             held.append(_require_device_f32(self.linear.weight.detach(), "TransformNet parameter"))
             exps = torch.empty(lib.os2d_train_range_plan_ints(), dtype=torch.int32, device=dev)
             bounds = torch.empty(lib.os2d_train_range_plan_doubles(), dtype=torch.int64, device=dev)
-            _train_lib.check(lib.os2d_train_range_plan(*args, _lib.ptr(held[-1]), _lib.ptr(exps), _lib.ptr(bounds), _lib.current_stream(dev)),
-                             "os2d_train_range_plan")
+            _train_lib.call("os2d_train_range_plan", *args, held[-1], exps, bounds, STREAM)
             result = (exps, bounds)
             self._packed_cache["range_plan"] = _StreamOrdered(key, result, dev)
         return result
@@ -358,7 +357,6 @@ class TransformationNet(nn.Module):
         lib = _lib.load()
         self.check_ready()
         with torch.cuda.device(dev):
-            stream = _lib.current_stream(dev)
             cur = torch.cuda.current_stream(dev)
             out = []
             P = self.output_dim
@@ -381,16 +379,13 @@ class TransformationNet(nn.Module):
                     exps = [plan[k][layer - 1] for k in ("weight_exp", "in_exp", "out_exp")]
                     exps = [e.to(dev).contiguous() if e is not None else None for e in exps]
                     pw = torch.empty(lib.os2d_packed_conv_bytes(layer, PRECISIONS[precision]), dtype=torch.uint8, device=dev)
-                    _lib.check(lib.os2d_pack_conv_f16x3(layer, P, _lib.ptr(w), _lib.ptr(b), *[_lib.ptr(t) for t in bnp],
-                                                        ctypes.c_float(eps), *[_lib.ptr(e) for e in exps],
-                                                        _lib.ptr(pw), _lib.ptr(pb), stream), "os2d_pack_conv_f16x3")
+                    _lib.call("os2d_pack_conv_f16x3", layer, P, w, b, *bnp, eps, *exps, pw, pb, STREAM)
                     for e in exps:
                         if e is not None:
                             e.record_stream(cur)
                 else:
                     pw = torch.empty(lib.os2d_packed_conv_floats(layer), dtype=torch.float32, device=dev)
-                    _lib.check(lib.os2d_pack_conv(layer, P, _lib.ptr(w), _lib.ptr(b), *[_lib.ptr(t) for t in bnp],
-                                                  ctypes.c_float(eps), _lib.ptr(pw), _lib.ptr(pb), stream), "os2d_pack_conv")
+                    _lib.call("os2d_pack_conv", layer, P, w, b, *bnp, eps, pw, pb, STREAM)
                 out += [pw, pb]
             result = tuple(out)
             self._packed_cache[precision] = _StreamOrdered(key, result, dev)
@@ -470,26 +465,24 @@ class TransformationNet(nn.Module):
         w1, b1, w2, b2, w3, b3 = self.packed(precision)
         out = torch.empty(N, P, H, W, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            stream = _lib.current_stream(dev)
             if precision in FP32_MODES:      # (the frequency-domain modes differ from their families only inside the fused head)
                 plane = lib.os2d_plane_floats(H, W)
                 r = torch.empty(N * 226 * plane, dtype=torch.float32, device=dev)
                 h1 = torch.empty(N * 128 * plane, dtype=torch.float32, device=dev)
                 h2 = torch.empty(N * 64 * plane, dtype=torch.float32, device=dev)
-                _lib.check(lib.os2d_corr_normalize(_lib.ptr(corr_maps), _lib.ptr(r), N, H, W, stream), "os2d_corr_normalize")
-                _lib.check(lib.os2d_transform_conv(1, _lib.ptr(r), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(h1), N, P, H, W, stream), "conv1")
-                _lib.check(lib.os2d_transform_conv(2, _lib.ptr(h1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(h2), N, P, H, W, stream), "conv2")
-                _lib.check(lib.os2d_transform_conv(3, _lib.ptr(h2), _lib.ptr(w3), _lib.ptr(b3), _lib.ptr(out), N, P, H, W, stream), "conv3")
+                _lib.call("os2d_corr_normalize", corr_maps, r, N, H, W, STREAM)
+                _lib.call("os2d_transform_conv", 1, r, w1, b1, h1, N, P, H, W, STREAM)
+                _lib.call("os2d_transform_conv", 2, h1, w2, b2, h2, N, P, H, W, STREAM)
+                _lib.call("os2d_transform_conv", 3, h2, w3, b3, out, N, P, H, W, STREAM)
             else:
                 terms1 = 2 if precision == "f16x2" else 3
                 r = torch.empty(N * lib.os2d_shb_bytes(225, H, W), dtype=torch.uint8, device=dev)
                 h1 = torch.empty(N * lib.os2d_shb_bytes(128, H, W), dtype=torch.uint8, device=dev)
                 h2 = torch.empty(N * lib.os2d_shb_bytes(64, H, W), dtype=torch.uint8, device=dev)
                 status = torch.zeros(1, dtype=torch.int32, device=dev)
-                _lib.check(lib.os2d_corr_normalize_f16x3(_lib.ptr(corr_maps), _lib.ptr(r), N, H, W, stream), "os2d_corr_normalize_f16x3")
+                _lib.call("os2d_corr_normalize_f16x3", corr_maps, r, N, H, W, STREAM)
                 for layer, src, wp, bp, dst, terms in ((1, r, w1, b1, h1, terms1), (2, h1, w2, b2, h2, 3), (3, h2, w3, b3, out, 3)):
-                    _lib.check(lib.os2d_transform_conv_f16x3(layer, _lib.ptr(src), _lib.ptr(wp), _lib.ptr(bp), _lib.ptr(dst), N, P,
-                                                             H, W, terms, _lib.ptr(status), stream), "os2d_transform_conv_f16x3")
+                    _lib.call("os2d_transform_conv_f16x3", layer, src, wp, bp, dst, N, P, H, W, terms, status, STREAM)
                 self.last_status = status      # device int32: OS2D_STATUS_F16_RANGE if an activation left the fp16 range
         return out
 
@@ -528,14 +521,10 @@ class Os2dAlignment(nn.Module):
         N, P, H, W = params.shape
         assert P == self.num_transform_params, \
             "Tranformation parameter vector has to be of dimension {0}, have {1} instead".format(self.num_transform_params, P)
-        lib = _lib.load()
         dev = params.device
         theta = torch.empty(N * H * W, 2, 3, dtype=torch.float32, device=dev) if want_theta else None
         grids = torch.empty(N, H, W, TEMPLATE, TEMPLATE, 2, dtype=torch.float32, device=dev) if want_grids else None
-        with torch.cuda.device(dev):
-            _lib.check(lib.os2d_alignment_grids(_lib.ptr(params), N, H, W, P, 1 if self.use_inverse_geom_model else 0,
-                                                _lib.ptr(theta), _lib.ptr(grids), _lib.current_stream(dev)),
-                       "os2d_alignment_grids")
+        _lib.call("os2d_alignment_grids", params, N, H, W, P, 1 if self.use_inverse_geom_model else 0, theta, grids, STREAM)
         return theta, grids
 
     def forward(self, corr_maps, precision="f32"):
@@ -632,16 +621,14 @@ def _prepare_class_maps(class_feature_maps, normalise=True):
     q15 = torch.empty(B, C, TEMPLATE, TEMPLATE, dtype=torch.float32, device=dev)
     qp = torch.empty(B, C, QROWS, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        stream = _lib.current_stream(dev)
         # ONE launch for all classes (the reference loops them, head.py:261-268): pointer + size tables on the device
         for b0 in range(0, B, 65535):
             chunk = maps[b0:b0 + 65535]
             ptrs = torch.tensor([m.data_ptr() for m in chunk], dtype=torch.int64).to(dev, non_blocking=False)
             sizes = torch.tensor([[m.size(1), m.size(2)] for m in chunk], dtype=torch.int32).to(dev, non_blocking=False)
             ws = torch.empty(lib.os2d_class_prepare_workspace_floats(len(chunk), C), dtype=torch.float32, device=dev)
-            _lib.check(lib.os2d_class_prepare_batch(_lib.ptr(ptrs), _lib.ptr(sizes), len(chunk), C, 1 if normalise else 0,
-                                                    _lib.ptr(q15[b0:b0 + len(chunk)]), _lib.ptr(qp[b0:b0 + len(chunk)]),
-                                                    _lib.ptr(ws), stream), "os2d_class_prepare_batch")
+            _lib.call("os2d_class_prepare_batch", ptrs, sizes, len(chunk), C, 1 if normalise else 0, q15[b0:b0 + len(chunk)],
+                      qp[b0:b0 + len(chunk)], ws, STREAM)
             cur = torch.cuda.current_stream(dev)
             ptrs.record_stream(cur), sizes.record_stream(cur), ws.record_stream(cur)
             for m in chunk:
@@ -722,9 +709,7 @@ class Os2dHead(nn.Module):
             lib = _lib.load()
             B, C = self._qp.size(0), self._qp.size(1)
             qs = torch.empty(lib.os2d_class_split_bytes(B, C), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.os2d_class_split(_lib.ptr(self._qp), _lib.ptr(qs), B, C, _lib.current_stream(dev)),
-                           "os2d_class_split")
+            _lib.call("os2d_class_split", self._qp, qs, B, C, STREAM)
             self._qs = _StreamOrdered(None, qs, dev)
         return self._qs.get(dev)
 
@@ -803,7 +788,6 @@ class Os2dHead(nn.Module):
             "Feature dimensionality of input={0} and class={1} feature maps has to equal".format(C, class_feature_dim)
         if self._qp.device != feature_maps.device:
             raise RuntimeError("class features are on {} but feature_maps on {}".format(self._qp.device, feature_maps.device))
-        lib = _lib.load()
         dev = feature_maps.device
         regressor = self.aligner.parameter_regressor
         P = regressor.output_dim
@@ -841,20 +825,15 @@ class Os2dHead(nn.Module):
                     raise RuntimeError("out tensors must be contiguous float32 [A,B,{},H,W] on {}".format(k, dev))
         full = ctypes.c_size_t()
         one = ctypes.c_size_t()
-        _lib.check(lib.os2d_head_workspace_bytes_ex(A, B, C, H, W, P, PRECISIONS[precision], ctypes.byref(full)), "os2d_head_workspace_bytes_ex")
-        _lib.check(lib.os2d_head_workspace_bytes_ex(A, 1, C, H, W, P, PRECISIONS[precision], ctypes.byref(one)), "os2d_head_workspace_bytes_ex")
+        _lib.call("os2d_head_workspace_bytes_ex", A, B, C, H, W, P, PRECISIONS[precision], ctypes.byref(full))
+        _lib.call("os2d_head_workspace_bytes_ex", A, 1, C, H, W, P, PRECISIONS[precision], ctypes.byref(one))
         with torch.cuda.device(dev):     # hipFuncSetAttribute / launches act on the CURRENT device
             ws = get_workspace(dev, min(full.value, workspace_cap_bytes()), one.value)      # (a cap replaced on THIS module is obeyed)
             status = self._status_word() if precision not in FP32_MODES else None
-            _lib.check(lib.os2d_head_forward_ex2(
-                _lib.ptr(feature_maps), _lib.ptr(self._qp), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2),
-                _lib.ptr(w3), _lib.ptr(b3), A, B, C, H, W, P, 1 if self.aligner.use_inverse_geom_model else 0,
-                self._stride, self._rec_field, _lib.ptr(loc), _lib.ptr(cls), _lib.ptr(corners),
-                _lib.ptr(ws), ws.numel(), _lib.current_stream(dev), PRECISIONS[precision],
-                _lib.ptr(self._split_class_operand()) if precision not in FP32_MODES else None, stage_events, None,
-                _lib.host_ptr(status), *([_lib.ptr(t) for t in spectra[:3]] if spectra is not None else [None, None, None]),
-                _lib.ptr(spectra2)),
-                "os2d_head_forward_ex2")
+            _lib.call("os2d_head_forward_ex2", feature_maps, self._qp, w1, b1, w2, b2, w3, b3, A, B, C, H, W, P,
+                      1 if self.aligner.use_inverse_geom_model else 0, self._stride, self._rec_field, loc, cls, corners, ws, ws.numel(),
+                      STREAM, PRECISIONS[precision], self._split_class_operand() if precision not in FP32_MODES else None, stage_events,
+                      None, _lib.host_ptr(status), *(spectra[:3] if spectra is not None else (None, None, None)), spectra2)
         strict = self.strict_range if strict_range is None else strict_range
         if strict and precision not in FP32_MODES:
             torch.cuda.current_stream(dev).synchronize()

@@ -25,13 +25,13 @@ of the convolution in front of it gets an exactly zero gradient.  ``head.last_li
 As in the reference (head.py:396-402, 423): ``cls_det`` carries the same values as ``cls`` but its gradient reaches the
 correlation only, not the transformation; ``corners`` carries none.
 """
-import ctypes
 import os
 
 import torch
 
 from .. import _lib
 from .. import _train_lib
+from .._native import STREAM
 
 TEMPLATE = 15
 MAX_W_DIRECT7 = 209
@@ -75,61 +75,55 @@ def resolve_deterministic(value=None):
     return bool(torch.are_deterministic_algorithms_enabled())
 
 
-def _ptr(t):
-    return _lib.ptr(t)
-
-
 def _wgrad_splits(NB, PL):
     """Split-K slices of a weight gradient: one per ~4096 positions of the NB * PLANE reduction, at most 64."""
     return max(1, min(64, (NB * PL + 4095) // 4096))
 
 
-def _corr_front_f32(lib, head, fm, corr, shape, s):
+def _corr_front_f32(head, fm, corr, shape):
     """The fp32 correlation front: fills ``corr``; returns (rnorm [NB,226,PLANE], sumsq), which the caller keeps to its end."""
     A, B, C, H, W, P, PL = shape
     sumsq = torch.empty(A * H * W, dtype=torch.float32, device=fm.device)
     rnorm = torch.empty(A * B * 226 * PL, dtype=torch.float32, device=fm.device)
-    _lib.check(lib.os2d_fm_sumsq(_ptr(fm), _ptr(sumsq), A, C, H, W, s), "os2d_fm_sumsq")
-    _lib.check(lib.os2d_corr(_ptr(fm), _ptr(head._qp), _ptr(sumsq), _ptr(corr), _ptr(rnorm), A, B, C, H, W, s), "os2d_corr")
+    _lib.call("os2d_fm_sumsq", fm, sumsq, A, C, H, W, STREAM)
+    _lib.call("os2d_corr", fm, head._qp, sumsq, corr, rnorm, A, B, C, H, W, STREAM)
     return rnorm, sumsq
 
 
-def _corr_front_f16x3(lib, head, fm, corr, shape, s):
+def _corr_front_f16x3(lib, head, fm, corr, shape):
     """The split-fp16 correlation front: fills ``corr``; returns (the blocked rnorm, the workspace: the caller frees it)."""
     A, B, C, H, W, P, PL = shape
     qs = head._split_class_operand()
     ws = torch.empty(int(lib.os2d_corr_f16x3_workspace_bytes(A, C, H, W)), dtype=torch.uint8, device=fm.device)
     rshb = torch.empty(A * B * int(lib.os2d_shb_bytes(225, H, W)), dtype=torch.uint8, device=fm.device)
-    _lib.check(lib.os2d_corr_f16x3(_ptr(fm), _ptr(qs), _ptr(corr), _ptr(rshb), A, B, C, H, W, _ptr(ws), ws.numel(), s), "os2d_corr_f16x3")
+    _lib.call("os2d_corr_f16x3", fm, qs, corr, rshb, A, B, C, H, W, ws, ws.numel(), STREAM)
     return rshb, ws
 
 
-def _planes_from_shb(buf, exp, channels, out_channels, shape, s):
+def _planes_from_shb(buf, exp, channels, out_channels, shape):
     """A split-half blocked activation buffer as the fp32 planes [NB,out_channels,PLANE] the backward reads (exact)."""
     A, B, C, H, W, P, PL = shape
     out = torch.empty(A * B * out_channels * PL, dtype=torch.float32, device=buf.device)
-    _train_lib.check(_train_lib.load().os2d_train_planes_from_shb(_ptr(buf), _ptr(exp), A * B, channels, out_channels, H, W, _ptr(out), s),
-                     "os2d_train_planes_from_shb")
+    _train_lib.call("os2d_train_planes_from_shb", buf, exp, A * B, channels, out_channels, H, W, out, STREAM)
     return out
 
 
-def _stages_f32(lib, head, fm, corr, prm, shape, s):
+def _stages_f32(head, fm, corr, prm, shape):
     """The strict-fp32 stages up to the transformation parameters: fills ``corr`` and ``prm``, returns the activations
     (rnorm [NB,226,PLANE], h1 [NB,128,PLANE], h2 [NB,64,PLANE]) as flat fp32 tensors."""
     A, B, C, H, W, P, PL = shape
     NB = A * B
     f32 = dict(dtype=torch.float32, device=fm.device)
     w1, b1, w2, b2, w3, b3 = head.aligner.parameter_regressor.packed("f32")
-    rnorm, sumsq = _corr_front_f32(lib, head, fm, corr, shape, s)
+    rnorm, sumsq = _corr_front_f32(head, fm, corr, shape)
     h1 = torch.empty(NB * 128 * PL, **f32)
     h2 = torch.empty(NB * 64 * PL, **f32)
     for layer, src, wp, bp, dst in ((1, rnorm, w1, b1, h1), (2, h1, w2, b2, h2), (3, h2, w3, b3, prm)):
-        _lib.check(lib.os2d_transform_conv(layer, _ptr(src), _ptr(wp), _ptr(bp), _ptr(dst), NB, P, H, W, s),
-                   "os2d_transform_conv")
+        _lib.call("os2d_transform_conv", layer, src, wp, bp, dst, NB, P, H, W, STREAM)
     return rnorm, h1, h2
 
 
-def _stages_f16x3(lib, head, fm, corr, prm, shape, s):
+def _stages_f16x3(lib, head, fm, corr, prm, shape):
     """The same on the direct split-fp16 route: the stage entry points the head call of ``precision="f16x3"`` is made of (they
     zero the borders the next layer's taps read themselves: os2d_corr_f16x3 those of its output before the correlation writes
     it, the convolutions in their epilogue).  Each split-half blocked buffer becomes fp32 planes (os2d_train_planes_from_shb:
@@ -148,21 +142,20 @@ def _stages_f16x3(lib, head, fm, corr, prm, shape, s):
         return torch.empty(NB * int(lib.os2d_shb_bytes(channels, H, W)), dtype=torch.uint8, device=dev)
 
     def conv(layer, src, wp, bp, dst):
-        _lib.check(lib.os2d_transform_conv_f16x3(layer, _ptr(src), _ptr(wp), _ptr(bp), _ptr(dst), NB, P, H, W, 3, status, s),
-                   "os2d_transform_conv_f16x3")
+        _lib.call("os2d_transform_conv_f16x3", layer, src, wp, bp, dst, NB, P, H, W, 3, status, STREAM)
 
-    rshb, ws = _corr_front_f16x3(lib, head, fm, corr, shape, s)
+    rshb, ws = _corr_front_f16x3(lib, head, fm, corr, shape)
     del ws
     h1shb = shb(128)
     conv(1, rshb, w1, b1, h1shb)
-    rnorm = _planes_from_shb(rshb, exps[0], 225, 226, shape, s)
+    rnorm = _planes_from_shb(rshb, exps[0], 225, 226, shape)
     del rshb
     h2shb = shb(64)
     conv(2, h1shb, w2, b2, h2shb)
-    h1 = _planes_from_shb(h1shb, exps[1], 128, 128, shape, s)
+    h1 = _planes_from_shb(h1shb, exps[1], 128, 128, shape)
     del h1shb
     conv(3, h2shb, w3, b3, prm)
-    h2 = _planes_from_shb(h2shb, exps[2], 64, 64, shape, s)
+    h2 = _planes_from_shb(h2shb, exps[2], 64, 64, shape)
     del h2shb
     return rnorm, h1, h2
 
@@ -177,7 +170,7 @@ def _update_running_stats(bn, mean, var, n):
     bn.num_batches_tracked.add_(1)
 
 
-def _stages_live(lib, head, fm, corr, prm, shape, s, live, forward_precision):
+def _stages_live(lib, head, fm, corr, prm, shape, live, forward_precision):
     """The stages up to the transformation parameters when a BatchNorm of the TransformNet takes batch statistics (DESIGN.md
     section 16).  Both layers with a BatchNorm run os2d_train_conv_forward (the raw convolution z; arith = the forward
     precision) and os2d_train_bn_relu_forward; a live layer gets its mean and 1 / sqrt(var + eps) from os2d_train_bn_stats and
@@ -192,39 +185,36 @@ def _stages_live(lib, head, fm, corr, prm, shape, s, live, forward_precision):
     regressor = head.aligner.parameter_regressor
     arith = TRAIN_FORWARD_PRECISIONS.index(forward_precision)
     if arith:
-        rshb, ws = _corr_front_f16x3(lib, head, fm, corr, shape, s)
+        rshb, ws = _corr_front_f16x3(lib, head, fm, corr, shape)
         # the exponent of the normalised correlation is a constant of the library: it does not depend on the BatchNorms
         exp0 = torch.full((225,), int(lib.os2d_rnorm_exp()), dtype=torch.int32, device=dev)
-        rnorm = _planes_from_shb(rshb, exp0, 225, 226, shape, s)
+        rnorm = _planes_from_shb(rshb, exp0, 225, 226, shape)
         del ws, rshb
     else:
-        rnorm, sumsq = _corr_front_f32(lib, head, fm, corr, shape, s)
+        rnorm, sumsq = _corr_front_f32(head, fm, corr, shape)
     src, acts, kept = rnorm, [], []
     layers = ((1, regressor.conv[0], regressor.conv[1], 128), (2, regressor.conv[3], regressor.conv[4], 64))
     for (layer, conv, bn, cout), is_live in zip(layers, live):
         z = torch.empty(NB * cout * PL, **f32)
         cws = torch.empty(int(tl.os2d_train_conv_forward_workspace_floats(arith, layer, P, NB)), **f32)
-        _train_lib.check(tl.os2d_train_conv_forward(arith, layer, P, _ptr(conv.weight.detach().contiguous()),
-                                                    _ptr(conv.bias.detach().contiguous()), _ptr(src), NB, H, W, _ptr(z), _ptr(cws),
-                                                    cws.numel(), s), "os2d_train_conv_forward")
+        _train_lib.call("os2d_train_conv_forward", arith, layer, P, conv.weight.detach().contiguous(), conv.bias.detach().contiguous(), src,
+                        NB, H, W, z, cws, cws.numel(), STREAM)
         if is_live:
             mean, var, invstd = (torch.empty(cout, **f32) for _ in range(3))
             bws = torch.empty(int(tl.os2d_train_bn_workspace_bytes(layer, NB)), dtype=torch.uint8, device=dev)
-            _train_lib.check(tl.os2d_train_bn_stats(layer, _ptr(z), NB, H, W, ctypes.c_float(float(bn.eps)), _ptr(mean), _ptr(var),
-                                                    _ptr(invstd), _ptr(bws), bws.numel(), s), "os2d_train_bn_stats")
+            _train_lib.call("os2d_train_bn_stats", layer, z, NB, H, W, float(bn.eps), mean, var, invstd, bws, bws.numel(), STREAM)
             _update_running_stats(bn, mean, var, float(NB * HW))
         else:
             mean = bn.running_mean.detach().contiguous()
             invstd = 1.0 / torch.sqrt(bn.running_var.detach() + float(bn.eps))
         h = torch.empty(NB * cout * PL, **f32)
-        _train_lib.check(tl.os2d_train_bn_relu_forward(layer, _ptr(z), _ptr(bn.weight.detach().contiguous()),
-                                                       _ptr(bn.bias.detach().contiguous()), _ptr(mean), _ptr(invstd), NB, H, W, _ptr(h), s),
-                         "os2d_train_bn_relu_forward")
+        _train_lib.call("os2d_train_bn_relu_forward", layer, z, bn.weight.detach().contiguous(), bn.bias.detach().contiguous(), mean,
+                        invstd, NB, H, W, h, STREAM)
         kept.append((z, mean, invstd) if is_live else None)
         acts.append(h)
         src = h
     w3, b3 = regressor.packed_linear_f32()
-    _lib.check(lib.os2d_transform_conv(3, _ptr(acts[1]), _ptr(w3), _ptr(b3), _ptr(prm), NB, P, H, W, s), "os2d_transform_conv")
+    _lib.call("os2d_transform_conv", 3, acts[1], w3, b3, prm, NB, P, H, W, STREAM)
     return rnorm, acts[0], acts[1], kept
 
 
@@ -248,17 +238,14 @@ class _HeadFunction(torch.autograd.Function):
         cls = torch.empty(A, B, 1, H, W, **f32)
         corners = torch.empty(A, B, 8, H, W, **f32)
         with torch.cuda.device(dev):
-            s = _lib.current_stream(dev)
             live, kept = head.last_live_batchnorm, [None, None]
             if any(live):
-                rnorm, h1, h2, kept = _stages_live(lib, head, fm, corr, prm, (A, B, C, H, W, P, PL), s, live,
-                                                   head.last_train_forward_precision)
+                rnorm, h1, h2, kept = _stages_live(lib, head, fm, corr, prm, (A, B, C, H, W, P, PL), live, head.last_train_forward_precision)
             elif head.last_train_forward_precision == "f16x3":
-                rnorm, h1, h2 = _stages_f16x3(lib, head, fm, corr, prm, (A, B, C, H, W, P, PL), s)
+                rnorm, h1, h2 = _stages_f16x3(lib, head, fm, corr, prm, (A, B, C, H, W, P, PL))
             else:
-                rnorm, h1, h2 = _stages_f32(lib, head, fm, corr, prm, (A, B, C, H, W, P, PL), s)
-            _lib.check(lib.os2d_sample_decode(_ptr(corr), _ptr(prm), NB, H, W, P, inverse, head._stride, head._rec_field,
-                                              _ptr(loc), _ptr(cls), _ptr(corners), s), "os2d_sample_decode")
+                rnorm, h1, h2 = _stages_f32(head, fm, corr, prm, (A, B, C, H, W, P, PL))
+            _lib.call("os2d_sample_decode", corr, prm, NB, H, W, P, inverse, head._stride, head._rec_field, loc, cls, corners, STREAM)
         q15raw = None
         if any(ctx.needs_input_grad[3:3 + n_class]):
             from .head import _prepare_class_maps
@@ -297,32 +284,28 @@ class _HeadFunction(torch.autograd.Function):
         grads = [None] * 10
         dfm, draws = None, [None] * n_class
         with torch.cuda.device(dev):
-            s = _lib.current_stream(dev)
             dcorr = torch.zeros(NB, 225, HW, **f32)
             dparams = torch.empty(NB, P, HW, **f32)
-            decode_args = (_ptr(sv["corr"]), _ptr(sv["params"]), _ptr(dcls), _ptr(dcls_det), _ptr(dloc), NB, H, W, P, inverse,
-                           head._stride, head._rec_field, _ptr(dcorr), _ptr(dparams))
+            decode_args = (sv["corr"], sv["params"], dcls, dcls_det, dloc, NB, H, W, P, inverse, head._stride, head._rec_field, dcorr, dparams)
             if ctx.deterministic:
                 ws = torch.empty(int(tl.os2d_train_decode_backward_det_workspace_bytes(NB, H, W)), dtype=torch.uint8, device=dev)
-                _train_lib.check(tl.os2d_train_decode_backward_det(*decode_args, _ptr(ws), ws.numel(), s), "os2d_train_decode_backward_det")
+                _train_lib.call("os2d_train_decode_backward_det", *decode_args, ws, ws.numel(), STREAM)
                 del ws
             else:
-                _train_lib.check(tl.os2d_train_decode_backward(*decode_args, s), "os2d_train_decode_backward")
+                _train_lib.call("os2d_train_decode_backward", *decode_args, STREAM)
             splits = _wgrad_splits(NB, PL)
 
             def wgrad(layer, x, dy, like):
                 n = int(tl.os2d_train_conv_weight_slice_floats_ex(arith, layer, P))
                 ws = torch.empty(n * splits, **f32)
                 dw = torch.empty_like(like)
-                _train_lib.check(tl.os2d_train_conv_backward_weight_ex(arith, layer, P, _ptr(x), _ptr(dy), NB, H, W, _ptr(dw), _ptr(ws),
-                                                                       ws.numel(), s), "os2d_train_conv_backward_weight_ex")
+                _train_lib.call("os2d_train_conv_backward_weight_ex", arith, layer, P, x, dy, NB, H, W, dw, ws, ws.numel(), STREAM)
                 return dw
 
             def dgrad(layer, w, dy, cin):
                 ws = torch.empty(int(tl.os2d_train_conv_data_workspace_floats_ex(arith, layer, P, NB)), **f32)
                 dx = torch.empty(NB * cin * PL, **f32)
-                _train_lib.check(tl.os2d_train_conv_backward_data_ex(arith, layer, P, _ptr(w), _ptr(dy), NB, H, W, _ptr(dx), _ptr(ws),
-                                                                     ws.numel(), s), "os2d_train_conv_backward_data_ex")
+                _train_lib.call("os2d_train_conv_backward_data_ex", arith, layer, P, w, dy, NB, H, W, dx, ws, ws.numel(), STREAM)
                 return dx
 
             def bn_relu(layer, dh, h, bn, gamma, beta, cout, ig, ib, iw):
@@ -333,24 +316,20 @@ class _HeadFunction(torch.autograd.Function):
                     # batch statistics: the backward goes through them; the convolution's bias cancels in z - mean
                     z, mean, invstd = sv["live"][layer - 1]
                     ws = torch.empty(int(tl.os2d_train_bn_workspace_bytes(layer, NB)), dtype=torch.uint8, device=dev)
-                    _train_lib.check(tl.os2d_train_bn_relu_backward_batch(layer, _ptr(dh), _ptr(z), _ptr(h), _ptr(gamma), _ptr(mean),
-                                                                          _ptr(invstd), NB, H, W, _ptr(dy), _ptr(dg), _ptr(dbe), _ptr(ws),
-                                                                          ws.numel(), s), "os2d_train_bn_relu_backward_batch")
+                    _train_lib.call("os2d_train_bn_relu_backward_batch", layer, dh, z, h, gamma, mean, invstd, NB, H, W, dy, dg, dbe, ws,
+                                    ws.numel(), STREAM)
                     grads[ig], grads[ib], grads[iw] = dg, dbe, (torch.zeros(cout, **f32) if need_p[iw] else None)
                     return dy
                 db = torch.empty(cout, **f32) if need_p[iw] else None
-                _train_lib.check(tl.os2d_train_bn_relu_backward(layer, _ptr(dh), _ptr(h), _ptr(gamma), _ptr(beta),
-                                                                _ptr(bn.running_var.detach().contiguous()), ctypes.c_float(float(bn.eps)),
-                                                                NB, H, W, _ptr(dy), _ptr(dg), _ptr(dbe), _ptr(db), s),
-                                 "os2d_train_bn_relu_backward")
+                _train_lib.call("os2d_train_bn_relu_backward", layer, dh, h, gamma, beta, bn.running_var.detach().contiguous(),
+                                float(bn.eps), NB, H, W, dy, dg, dbe, db, STREAM)
                 grads[ig], grads[ib], grads[iw] = dg, dbe, db
                 return dy
 
             # layer 3 (linear): parameters -> plane gradient, bias gradient
             dy3 = torch.empty(NB * P * PL, **f32)
             db3 = torch.empty(P, **f32) if need_p[9] else None
-            _train_lib.check(tl.os2d_train_params_backward(_ptr(dparams), NB, P, H, W, _ptr(dy3), _ptr(db3), s),
-                             "os2d_train_params_backward")
+            _train_lib.call("os2d_train_params_backward", dparams, NB, P, H, W, dy3, db3, STREAM)
             grads[9] = db3
             if need_p[8]:
                 grads[8] = wgrad(3, sv["h2"], dy3, w3)
@@ -366,22 +345,19 @@ class _HeadFunction(torch.autograd.Function):
                     grads[0] = wgrad(1, sv["rnorm"], dy1, w1)
                 if need_fm or need_cls:
                     dxn = dgrad(1, w1, dy1, 225)
-                    _train_lib.check(tl.os2d_train_norm225_backward(_ptr(sv["corr"]), _ptr(dxn), NB, H, W, _ptr(dcorr), s),
-                                     "os2d_train_norm225_backward")
+                    _train_lib.call("os2d_train_norm225_backward", sv["corr"], dxn, NB, H, W, dcorr, STREAM)
             if need_fm or need_cls:
                 ws = torch.empty(int(tl.os2d_train_corr_workspace_floats_ex(arith, A, B, C, H, W)), **f32)
                 dfm = torch.empty(A, C, H, W, **f32) if need_fm else None
                 dq = torch.empty(B, C, 225, **f32) if need_cls else None
-                _train_lib.check(tl.os2d_train_corr_backward_ex(arith, _ptr(fm), _ptr(head._qp), _ptr(dcorr), A, B, C, H, W, _ptr(dfm),
-                                                                _ptr(dq), _ptr(ws), ws.numel(), s), "os2d_train_corr_backward_ex")
+                _train_lib.call("os2d_train_corr_backward_ex", arith, fm, head._qp, dcorr, A, B, C, H, W, dfm, dq, ws, ws.numel(), STREAM)
                 if need_cls:
                     raws = sv["raws"]
                     draws = [torch.empty(r.shape, **f32) for r in raws]
                     ptrs = torch.tensor([d.data_ptr() for d in draws], dtype=torch.int64).to(dev)
                     sizes = torch.tensor([[r.shape[-2], r.shape[-1]] for r in raws], dtype=torch.int32).to(dev)
                     cws = torch.empty(B * C * 225, **f32)
-                    _train_lib.check(tl.os2d_train_class_backward(_ptr(sv["q15raw"]), _ptr(dq), B, C, _ptr(ptrs), _ptr(sizes), _ptr(cws),
-                                                                  cws.numel(), s), "os2d_train_class_backward")
+                    _train_lib.call("os2d_train_class_backward", sv["q15raw"], dq, B, C, ptrs, sizes, cws, cws.numel(), STREAM)
                     draws = [d if need[3 + i] else None for i, d in enumerate(draws)]
         grads = [g if need_p[i] else None for i, g in enumerate(grads)]
         return (None, None, dfm) + tuple(draws) + tuple(grads)

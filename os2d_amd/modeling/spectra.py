@@ -10,6 +10,7 @@ import os
 import torch
 
 from .. import _lib
+from .._native import STREAM
 
 
 @functools.lru_cache(maxsize=None)
@@ -42,8 +43,7 @@ def build_dft_matrices(P, Q, device):
     lib = _lib.load()
     tp64, tq64 = twiddles64(P, device), twiddles64(Q, device)
     mats = torch.empty(lib.os2d_dft_matrices_bytes(P, Q), dtype=torch.uint8, device=device)
-    _lib.check(lib.os2d_dft_matrices_build(_lib.ptr(tp64), _lib.ptr(tq64), P, Q, _lib.ptr(mats), _lib.current_stream(device)),
-               "os2d_dft_matrices_build")
+    _lib.call("os2d_dft_matrices_build", tp64, tq64, P, Q, mats, STREAM)
     cur = torch.cuda.current_stream(device)
     tp64.record_stream(cur), tq64.record_stream(cur)
     return mats
@@ -57,15 +57,13 @@ def build_weight_spectra(wfold, C, Cout, P, Q, nbins, split, device):
     wfold = wfold.to(device).contiguous()
     tp64, tq64 = twiddles64(P, device), twiddles64(Q, device)
     scratch = torch.empty(1024, dtype=torch.uint8, device=device)
-    args = (_lib.ptr(wfold), _lib.ptr(tp64), _lib.ptr(tq64), C, Cout, P, Q, nbins)
+    args = (wfold, tp64, tq64, C, Cout, P, Q, nbins)
     if split:
         wspec = torch.empty(lib.os2d_spectral_weight16_bytes(C, nbins), dtype=torch.uint8, device=device)
-        _lib.check(lib.os2d_spectral_weights_build_dft(*args, _lib.ptr(wspec), _lib.ptr(scratch), _lib.current_stream(device)),
-                   "os2d_spectral_weights_build_dft")
+        _lib.call("os2d_spectral_weights_build_dft", *args, wspec, scratch, STREAM)
     else:
         wspec = torch.empty(lib.os2d_spectral_weight_bytes(C, Cout, nbins) // 4, dtype=torch.float32, device=device)
-        _lib.check(lib.os2d_spectral_weights_build(*args, 0, _lib.ptr(wspec), _lib.ptr(scratch), _lib.current_stream(device)),
-                   "os2d_spectral_weights_build")
+        _lib.call("os2d_spectral_weights_build", *args, 0, wspec, scratch, STREAM)
     cur = torch.cuda.current_stream(device)
     for t in (wfold, tp64, tq64, scratch):
         t.record_stream(cur)
