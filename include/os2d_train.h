@@ -305,9 +305,9 @@ int os2d_train_mine_select(int A, int B, int L, const int* level_hw, const int* 
 typedef struct {
   float* param;        /* [numel] */
   float* grad;         /* [numel]; the update writes grad * coef back */
-  float* state1;       /* SGD: momentum_buffer (not read when momentum == 0); Adam: exp_avg */
+  float* state1;       /* SGD: momentum_buffer (not read when momentum == 0); Adam: exp_avg; the other methods: the table below */
   float* state2;       /* Adam: exp_avg_sq */
-  float* step;         /* Adam: the tensor's step count, one float on the device */
+  float* step;         /* every method but SGD: the tensor's step count, one float on the device */
   long long numel;     /* 0 is allowed: no chunk, no access */
   float lr;
   float weight_decay;
@@ -344,6 +344,52 @@ int os2d_train_optim_prepare(const os2d_train_optim_tensor* tensors, int n, cons
  * keep their bits.                                                                                                             */
 int os2d_train_optim_update(int method, const os2d_train_optim_tensor* tensors, int n, const float* record, const float* factors,
                             double momentum_or_beta1, double beta2, double eps, void* stream);
+
+/* ---- The reference's other six methods (torch.optim.Adagrad, Adadelta, Adamax, ASGD, RMSprop, Rprop as its create_optimizer
+ * builds them: single-tensor arithmetic, no maximize; RMSprop without momentum and not centered).  A step is
+ *     sumsq (per table)  ->  finalize  ->  prepare_ex (per table)  ->  update_ex (per table)
+ * with the same tables, record, chunk numbering and checks as above.  `hyper` is a HOST array of nhyper doubles, read before the
+ * call returns (it travels in the kernel arguments); a method outside 2 .. 7, an nhyper other than the method's, a null hyper, a
+ * value outside its range or a null state pointer the method needs: -1 before anything is launched.
+ *   method     hyper                                          state1        state2                    factors written by prepare_ex
+ *   ADAGRAD    lr_decay, eps                                  sum           -                         clr
+ *   ADADELTA   rho, eps                                       square_avg    acc_delta                 -
+ *   ADAMAX     beta1, beta2, eps                              exp_avg       exp_inf                   lr / (1 - beta1^step)
+ *   ASGD       lambd, alpha, t0                               ax            {eta, mu}: TWO floats     1 - lambd eta, eta, mu
+ *   RMSPROP    alpha, eps                                     square_avg    -                         -
+ *   RPROP      etaminus, etaplus, step_size_min, _max         prev          step_size                 -
+ * The change is additive: OS2D_TRAIN_ABI_VERSION stays 2.                                                                      */
+#define OS2D_TRAIN_OPTIM_ADAGRAD 2
+#define OS2D_TRAIN_OPTIM_ADADELTA 3
+#define OS2D_TRAIN_OPTIM_ADAMAX 4
+#define OS2D_TRAIN_OPTIM_ASGD 5
+#define OS2D_TRAIN_OPTIM_RMSPROP 6
+#define OS2D_TRAIN_OPTIM_RPROP 7
+#define OS2D_TRAIN_OPTIM_MAX_HYPER 8      /* no method takes more hyperparameters */
+#define OS2D_TRAIN_OPTIM_FACTORS 4        /* floats per tensor that prepare_ex writes */
+
+/* ---- between finalize and update_ex, one thread per tensor of the table: unless record says skip, *step += 1 and
+ * factors[4 i ..] = the method's factors above, computed in double from (double)lr and the new step and rounded once (unused
+ * entries are 0).  ASGD: the factors are the eta and mu that state2 holds - those the previous step left, lr and 1 before the
+ * first - and state2 then receives eta = lr / (1 + lambd lr step)^alpha, mu = 1 / max(1, step - t0) for the next step.  Every
+ * record needs `step` (ASGD: and state2), also one without elements.  factors: 4 n floats.                                     */
+int os2d_train_optim_prepare_ex(int method, const os2d_train_optim_tensor* tensors, int n, const float* record, const double* hyper,
+                                int nhyper, float* factors, void* stream);
+
+/* ---- per element g = grad * record[1], written back to grad; then, unless record says skip, in fp32, one rounding per operation,
+ * correctly rounded division and square root, d = g + weight_decay * p (d = g when weight_decay == 0; Rprop: always d = g), with
+ * f0 .. f2 the tensor's factors and every hyperparameter (and 1 - rho, 1 - beta1, 1 - alpha) rounded once from double:
+ *   ADAGRAD    sum = sum + d * d;  p = p - f0 * (d / (sqrt(sum) + eps))
+ *   ADADELTA   sq = rho * sq + ((1 - rho) * d) * d;  delta = sqrt(acc + eps) / sqrt(sq + eps) * d;
+ *              acc = rho * acc + ((1 - rho) * delta) * delta;  p = p - lr * delta
+ *   ADAMAX     m = m + (d - m) * (1 - beta1);  u = max(beta2 * u, |d| + eps), NaN if either is;  p = p - f0 * (m / u)
+ *   ASGD       p = p * f0;  p = p - f1 * d;  ax = ax + (p - ax) * f2 when f2 != 1, else ax = p        (state2 is not touched)
+ *   RMSPROP    sq = alpha * sq + ((1 - alpha) * d) * d;  p = p - lr * (d / (sqrt(sq) + eps))
+ *   RPROP      s = d * prev;  step_size = clamp(step_size * (etaplus if s > 0, etaminus if s < 0, 1 if s == 0, NaN else), min, max),
+ *              a NaN stays;  d = 0 where s < 0;  p = p - sign(d) * step_size (sign(0) = 0, sign(NaN) = NaN);  prev = d
+ * On a skipped step parameters and state keep their bits.                                                                       */
+int os2d_train_optim_update_ex(int method, const os2d_train_optim_tensor* tensors, int n, const float* record, const float* factors,
+                               const double* hyper, int nhyper, void* stream);
 
 /* ---- the range plan of the split-fp16 ("f16x3") packing on the device - what a parameter change makes stale every step: the
  * exponents os2d_pack_conv_f16x3 (include/os2d_hip.h) takes, from the raw fp32 parameters (w1 [128,225,7,7], w2 [64,128,5,5],

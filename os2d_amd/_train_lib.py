@@ -24,6 +24,8 @@ class OptimTensor(ctypes.Structure):
 
 OPTIM_MAX_TENSORS, OPTIM_CHUNK = 60, 4096      # OS2D_TRAIN_OPTIM_MAX_TENSORS, OS2D_TRAIN_OPTIM_CHUNK
 OPTIM_SGD, OPTIM_ADAM = 0, 1
+OPTIM_ADAGRAD, OPTIM_ADADELTA, OPTIM_ADAMAX, OPTIM_ASGD, OPTIM_RMSPROP, OPTIM_RPROP = 2, 3, 4, 5, 6, 7
+OPTIM_MAX_HYPER, OPTIM_FACTORS = 8, 4          # OS2D_TRAIN_OPTIM_MAX_HYPER, OS2D_TRAIN_OPTIM_FACTORS
 
 SIGNATURES = {
     "os2d_train_abi_version": (_i, []),
@@ -70,6 +72,8 @@ SIGNATURES = {
     "os2d_train_optim_finalize": (_i, [_p, _sz, _f, _p, _p]),
     "os2d_train_optim_prepare": (_i, [_p, _i, _p, _d, _d, _p, _p]),
     "os2d_train_optim_update": (_i, [_i, _p, _i, _p, _p, _d, _d, _d, _p]),
+    "os2d_train_optim_prepare_ex": (_i, [_i, _p, _i, _p, _p, _i, _p, _p]),
+    "os2d_train_optim_update_ex": (_i, [_i, _p, _i, _p, _p, _p, _i, _p]),
     "os2d_train_range_plan_ints": (_sz, []),
     "os2d_train_range_plan_doubles": (_sz, []),
     "os2d_train_range_plan": (_i, [_i] + [_p] * 6 + [_d] + [_p] * 6 + [_d] + [_p] * 4),

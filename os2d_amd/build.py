@@ -60,7 +60,7 @@ TRAIN_CSRC = os.path.join(HERE, "csrc_train")
 # mining.hip needs no flag: every function of it that rounds (csrc/detect_common.h, mining_crop.h) switches contraction off itself
 # shb_planes.hip: the split-half blocked activations of an f16x3 training forward as the fp32 planes the backward reads
 # bn_live.hip: batch-statistics BatchNorm of the TransformNet (statistics, normalise + ReLU, backward through the statistics)
-# optim.hip: gradient norm, clip, NaN guard and the SGD / Adam step as multi-tensor kernels; needs no flag either: every function
+# optim.hip: gradient norm, clip, NaN guard and the step of all eight methods as multi-tensor kernels; needs no flag either: every function
 #            of it that rounds switches contraction off itself
 # range_plan.hip: BatchNorm fold, bounds and exponents of the f16x3 packing in float64 - what a parameter change makes stale every
 #                 step (here and not in libos2d_hip.so, whose kernel set is pinned); contraction off in its own functions as well

@@ -21,6 +21,10 @@
 // Step counts are device state (Adam).  prepare, one thread per tensor, runs between finalize and update: it advances the
 // tensor's count unless the step is skipped and writes the two factors the update reads, so no work-group of the update reads a
 // count that another one of the same launch writes.
+//
+// The other six methods (Adagrad, Adadelta, Adamax, ASGD, RMSprop, Rprop: prepare_ex / update_ex) share all of this: the same
+// chunk loop with another element function, and a prepare that writes OS2D_TRAIN_OPTIM_FACTORS floats per tensor.  ASGD's eta and
+// mu are functions of the count alone: prepare_ex hands the update the pair the previous step left and writes the next one.
 #include <math.h>
 #include <stdint.h>
 
@@ -181,16 +185,16 @@ __device__ __forceinline__ float scaled(float g, float coef) {
   return g * coef;
 }
 
-// ADAM: false = SGD.  STATE: SGD only, false = no momentum buffer (mu == 0).  VEC: 16-byte accesses.
-template <bool ADAM, bool VEC>
-__device__ __forceinline__ void update_chunk(const Tensor& t, long long base, long long left, float coef, bool skip, float f0, float f1,
-                                             const Hyper& h) {
+// What one element does is an OP: op(g, p, a, b) updates the parameter and its (at most two) state values from the clipped
+// gradient.  OP::STATE2: the method keeps a second per-element state tensor; op.has1: state1 is read and written (SGD without
+// momentum has none).  VEC: 16-byte accesses.
+template <bool VEC, class OP>
+__device__ __forceinline__ void update_chunk(const Tensor& t, long long base, long long left, float coef, bool skip, const OP& op) {
   float* __restrict__ gp = t.grad + base;
   float* __restrict__ pp = t.param + base;
   float* __restrict__ s1 = t.state1 ? t.state1 + base : nullptr;
-  float* __restrict__ s2 = ADAM ? t.state2 + base : nullptr;
-  const float lr = t.lr, wd = t.weight_decay;
-  const bool has1 = s1 != nullptr;
+  float* __restrict__ s2 = OP::STATE2 ? t.state2 + base : nullptr;
+  const bool has1 = op.has1;
   constexpr int W = VEC ? 4 : 1;
 #pragma unroll
   for (int k = 0; k < PER_THREAD / W; ++k) {
@@ -205,33 +209,46 @@ __device__ __forceinline__ void update_chunk(const Tensor& t, long long base, lo
       f32x4 p = *reinterpret_cast<const f32x4*>(pp + e);
       f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f}, b = a;
       if (has1) a = *reinterpret_cast<const f32x4*>(s1 + e);
-      if (ADAM) b = *reinterpret_cast<const f32x4*>(s2 + e);
+      if (OP::STATE2) b = *reinterpret_cast<const f32x4*>(s2 + e);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float pj = p[j], aj = a[j], bj = b[j];
-        if (ADAM) adam_element(g[j], pj, aj, bj, wd, f0, f1, h);
-        else sgd_element(g[j], pj, aj, lr, wd, has1 ? h.mu : 0.0f);
+        op(g[j], pj, aj, bj);
         p[j] = pj, a[j] = aj, b[j] = bj;
       }
       *reinterpret_cast<f32x4*>(pp + e) = p;
       if (has1) *reinterpret_cast<f32x4*>(s1 + e) = a;
-      if (ADAM) *reinterpret_cast<f32x4*>(s2 + e) = b;
+      if (OP::STATE2) *reinterpret_cast<f32x4*>(s2 + e) = b;
     } else {
       for (int j = 0; j < W; ++j) {
         if (e + j >= left) break;
         const float g = scaled(gp[e + j], coef);
         gp[e + j] = g;
         if (skip) continue;
-        float p = pp[e + j], a = has1 ? s1[e + j] : 0.0f, b = ADAM ? s2[e + j] : 0.0f;
-        if (ADAM) adam_element(g, p, a, b, wd, f0, f1, h);
-        else sgd_element(g, p, a, lr, wd, has1 ? h.mu : 0.0f);
+        float p = pp[e + j], a = has1 ? s1[e + j] : 0.0f, b = OP::STATE2 ? s2[e + j] : 0.0f;
+        op(g, p, a, b);
         pp[e + j] = p;
         if (has1) s1[e + j] = a;
-        if (ADAM) s2[e + j] = b;
+        if (OP::STATE2) s2[e + j] = b;
       }
     }
   }
 }
+
+struct SgdOp {
+  static constexpr bool STATE2 = false;
+  float lr, wd, mu;
+  bool has1;
+  __device__ __forceinline__ void operator()(float g, float& p, float& a, float&) const { sgd_element(g, p, a, lr, wd, has1 ? mu : 0.0f); }
+};
+
+struct AdamOp {
+  static constexpr bool STATE2 = true;
+  static constexpr bool has1 = true;
+  float wd, f0, f1;
+  const Hyper& h;
+  __device__ __forceinline__ void operator()(float g, float& p, float& m, float& v) const { adam_element(g, p, m, v, wd, f0, f1, h); }
+};
 
 // grid: x = the table's chunks.  factors: the table's [n][2] floats of prepare (Adam), else not read
 template <bool ADAM>
@@ -244,10 +261,121 @@ __global__ __launch_bounds__(THREADS) void optim_update_kernel(const Table tab, 
   const long long left = t.numel - base;
   const float coef = record[1];
   const bool skip = record[2] != 0.0f;
-  float f0 = 0.0f, f1 = 1.0f;
-  if (ADAM && !skip) f0 = factors[2 * i], f1 = factors[2 * i + 1];
-  if (t.aligned) update_chunk<ADAM, true>(t, base, left, coef, skip, f0, f1, h);
-  else update_chunk<ADAM, false>(t, base, left, coef, skip, f0, f1, h);
+  if (ADAM) {
+    float f0 = 0.0f, f1 = 1.0f;
+    if (!skip) f0 = factors[2 * i], f1 = factors[2 * i + 1];
+    const AdamOp op = {t.weight_decay, f0, f1, h};
+    if (t.aligned) update_chunk<true>(t, base, left, coef, skip, op);
+    else update_chunk<false>(t, base, left, coef, skip, op);
+  } else {
+    const SgdOp op = {t.lr, t.weight_decay, h.mu, t.state1 != nullptr};
+    if (t.aligned) update_chunk<true>(t, base, left, coef, skip, op);
+    else update_chunk<false>(t, base, left, coef, skip, op);
+  }
+}
+
+// ---- the other six methods of torch.optim that the reference offers (include/os2d_train.h: os2d_train_optim_*_ex)
+
+constexpr int FACTORS = OS2D_TRAIN_OPTIM_FACTORS;      // floats per tensor that prepare_ex writes
+
+// one thread per tensor of the table: unless the step is skipped, advance the count and write what depends on it.  h0 .. h2: the
+// method's hyperparameters that prepare needs, in double (Adagrad: lr_decay; Adamax: beta1; ASGD: lambd, alpha, t0)
+__global__ __launch_bounds__(64) void optim_prepare_ex_kernel(const Table tab, int n, int method, const float* __restrict__ record, double h0,
+                                                              double h1, double h2, float* __restrict__ factors) {
+#pragma clang fp contract(off)
+  const int i = threadIdx.x;
+  if (i >= n || record[2] != 0.0f) return;
+  const Tensor& t = tab.t[i];
+  const float stepf = *t.step + 1.0f;
+  *t.step = stepf;
+  const double step = (double)stepf, lr = (double)t.lr;
+  float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f;
+  if (method == OS2D_TRAIN_OPTIM_ADAGRAD) {
+    f0 = (float)(lr / (1.0 + (step - 1.0) * h0));
+  } else if (method == OS2D_TRAIN_OPTIM_ADAMAX) {
+    f0 = (float)(lr / (1.0 - pow_whole(h0, (unsigned)stepf)));
+  } else if (method == OS2D_TRAIN_OPTIM_ASGD) {
+    // this step runs with the eta and mu the previous one left (state2 = {eta, mu}); the next step's follow from the new count
+    float* __restrict__ eta_mu = t.state2;
+    const float eta = eta_mu[0], mu = eta_mu[1];
+    f0 = (float)(1.0 - h0 * (double)eta), f1 = eta, f2 = mu;
+    const double rest = step - h2;
+    eta_mu[0] = (float)(lr / pow(1.0 + h0 * lr * step, h1));
+    eta_mu[1] = (float)(1.0 / (rest > 1.0 ? rest : 1.0));
+  }
+  float* __restrict__ f = factors + FACTORS * i;
+  f[0] = f0, f[1] = f1, f[2] = f2, f[3] = 0.0f;
+}
+
+struct HyperEx {     // the method's hyperparameters the update needs, each rounded once from double
+  float v0, v1, v2, v3;
+};
+
+// One element of method M.  a, b: the method's state1 / state2 value; f0 .. f2: the tensor's factors of prepare_ex.
+//   Adagrad   a sum;  f0 clr;  v0 eps                          Adadelta  a square_avg, b acc_delta;  v0 rho, v1 1 - rho, v2 eps
+//   Adamax    a exp_avg, b exp_inf;  f0 lr / bc1;  v0 1 - beta1, v1 beta2, v2 eps
+//   ASGD      a ax;  f0 1 - lambd eta, f1 eta, f2 mu           RMSprop   a square_avg;  v0 alpha, v1 1 - alpha, v2 eps
+//   Rprop     a prev, b step_size;  v0 etaminus, v1 etaplus, v2 / v3 the smallest / largest step size
+template <int M>
+struct MethodOp {
+  static constexpr bool STATE2 = M == OS2D_TRAIN_OPTIM_ADADELTA || M == OS2D_TRAIN_OPTIM_ADAMAX || M == OS2D_TRAIN_OPTIM_RPROP;
+  static constexpr bool has1 = true;
+  float lr, wd, f0, f1, f2;
+  const HyperEx& h;
+  __device__ __forceinline__ void operator()(float g, float& p, float& a, float& b) const {
+#pragma clang fp contract(off)
+    float d = g;
+    if (M != OS2D_TRAIN_OPTIM_RPROP && wd != 0.0f) d = g + wd * p;
+    if (M == OS2D_TRAIN_OPTIM_ADAGRAD) {
+      a = a + d * d;
+      p = p - f0 * (d / (sqrtf(a) + h.v0));
+    } else if (M == OS2D_TRAIN_OPTIM_ADADELTA) {
+      a = h.v0 * a + (h.v1 * d) * d;
+      const float delta = sqrtf(b + h.v2) / sqrtf(a + h.v2) * d;
+      b = h.v0 * b + (h.v1 * delta) * delta;
+      p = p - lr * delta;
+    } else if (M == OS2D_TRAIN_OPTIM_ADAMAX) {
+      a = a + (d - a) * h.v0;
+      const float x = h.v1 * b, y = fabsf(d) + h.v2;
+      b = (y > x || y != y) ? y : x;                     // the larger one; a NaN on either side stays, as torch.maximum keeps it
+      p = p - f0 * (a / b);
+    } else if (M == OS2D_TRAIN_OPTIM_ASGD) {
+      p = p * f0;
+      p = p - f1 * d;
+      a = f2 != 1.0f ? a + (p - a) * f2 : p;
+    } else if (M == OS2D_TRAIN_OPTIM_RMSPROP) {
+      a = h.v0 * a + (h.v1 * d) * d;
+      p = p - lr * (d / (sqrtf(a) + h.v2));
+    } else {
+      const float s = d * a;
+      const float eta = s > 0.0f ? h.v1 : (s < 0.0f ? h.v0 : (s == 0.0f ? 1.0f : s));      // a NaN product stays NaN
+      float size = b * eta;
+      size = size < h.v2 ? h.v2 : (size > h.v3 ? h.v3 : size);                            // and so does a NaN size
+      b = size;
+      if (s < 0.0f) d = 0.0f;
+      const float sign = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : (d == 0.0f ? 0.0f : d));
+      p = p - sign * size;
+      a = d;
+    }
+  }
+};
+
+// grid: x = the table's chunks.  factors: the table's [n][FACTORS] floats of prepare_ex
+template <int M>
+__global__ __launch_bounds__(THREADS) void optim_update_ex_kernel(const Table tab, int n, int chunk_base, const float* __restrict__ record,
+                                                                  const float* __restrict__ factors, const HyperEx h) {
+  const int c = chunk_base + blockIdx.x;
+  const int i = find_tensor(tab, n, c);
+  const Tensor& t = tab.t[i];
+  const long long base = (long long)(c - t.first_chunk) * CHUNK;
+  const long long left = t.numel - base;
+  const float coef = record[1];
+  const bool skip = record[2] != 0.0f;
+  float f0 = 0.0f, f1 = 0.0f, f2 = 1.0f;
+  if (!skip) f0 = factors[FACTORS * i], f1 = factors[FACTORS * i + 1], f2 = factors[FACTORS * i + 2];
+  const MethodOp<M> op = {t.lr, t.weight_decay, f0, f1, f2, h};
+  if (t.aligned) update_chunk<true>(t, base, left, coef, skip, op);
+  else update_chunk<false>(t, base, left, coef, skip, op);
 }
 
 size_t chunks_of(long long numel) { return numel <= 0 ? 0 : (size_t)((numel + CHUNK - 1) / CHUNK); }
@@ -359,4 +487,103 @@ extern "C" int os2d_train_optim_update(int method, const os2d_train_optim_tensor
   else
     hipLaunchKernelGGL(optim_update_kernel<false>, dim3((unsigned)chunks), dim3(THREADS), 0, os2d_stream(stream), tab, n, first, record, factors, h);
   return os2d_launched("optim_update_kernel");
+}
+
+namespace {
+
+// what a method takes and needs: the length of its hyperparameter array and, for the update / for prepare, which of state1 (1),
+// state2 (2), step (4) a tensor must carry
+struct MethodTraits {
+  const char* name;
+  int nhyper, update_need, prepare_need;
+};
+
+const MethodTraits* traits_of(int method) {
+  static const MethodTraits table[] = {
+      {"Adagrad", 2, 1, 4},      // lr_decay, eps
+      {"Adadelta", 2, 3, 4},     // rho, eps
+      {"Adamax", 3, 3, 4},       // beta1, beta2, eps
+      {"ASGD", 3, 1, 4 | 2},     // lambd, alpha, t0; state2 = {eta, mu}, read and written by prepare only
+      {"RMSprop", 2, 1, 4},      // alpha, eps
+      {"Rprop", 4, 3, 4},        // etaminus, etaplus, the smallest and the largest step size
+  };
+  if (method < OS2D_TRAIN_OPTIM_ADAGRAD || method > OS2D_TRAIN_OPTIM_RPROP) return nullptr;
+  return &table[method - OS2D_TRAIN_OPTIM_ADAGRAD];
+}
+
+// -> 0, or the refusal's code: the method, the array's length and the values' ranges (torch's constructors check the same)
+int check_hyper(const char* who, int method, const double* h, int nhyper) {
+  const MethodTraits* m = traits_of(method);
+  if (!m) return OS2D_REFUSE(-1, "%s: method=%d (2 Adagrad, 3 Adadelta, 4 Adamax, 5 ASGD, 6 RMSprop, 7 Rprop)", who, method);
+  if (nhyper != m->nhyper) return OS2D_REFUSE(-1, "%s: %s takes %d hyperparameters, got nhyper=%d", who, m->name, m->nhyper, nhyper);
+  if (!h) return OS2D_REFUSE(-1, "%s: null pointer (hyper)", who);
+  bool ok = true;
+  switch (method) {
+    case OS2D_TRAIN_OPTIM_ADAGRAD: ok = h[0] >= 0.0 && h[1] >= 0.0; break;
+    case OS2D_TRAIN_OPTIM_ADADELTA: ok = h[0] >= 0.0 && h[0] <= 1.0 && h[1] >= 0.0; break;
+    case OS2D_TRAIN_OPTIM_ADAMAX: ok = h[0] >= 0.0 && h[0] < 1.0 && h[1] >= 0.0 && h[1] < 1.0 && h[2] >= 0.0; break;
+    case OS2D_TRAIN_OPTIM_ASGD: ok = h[0] == h[0] && h[1] == h[1] && h[2] == h[2]; break;
+    case OS2D_TRAIN_OPTIM_RMSPROP: ok = h[0] >= 0.0 && h[1] >= 0.0; break;
+    default: ok = h[0] > 0.0 && h[0] < 1.0 && h[1] > 1.0 && h[2] <= h[3]; break;
+  }
+  if (!ok) return OS2D_REFUSE(-1, "%s: a hyperparameter of %s is outside its range", who, m->name);
+  return 0;
+}
+
+template <int M>
+void launch_update_ex(size_t chunks, const Table& tab, int n, int first, const float* record, const float* factors, const HyperEx& h, void* stream) {
+  hipLaunchKernelGGL(optim_update_ex_kernel<M>, dim3((unsigned)chunks), dim3(THREADS), 0, os2d_stream(stream), tab, n, first, record, factors, h);
+}
+
+}  // namespace
+
+extern "C" int os2d_train_optim_prepare_ex(int method, const os2d_train_optim_tensor* tensors, int n, const float* record, const double* hyper,
+                                           int nhyper, float* factors, void* stream) {
+  const char* who = "os2d_train_optim_prepare_ex";
+  if (const int rc = check_hyper(who, method, hyper, nhyper)) return rc;
+  const MethodTraits* m = traits_of(method);
+  size_t chunks = 0;
+  if (const int rc = check_table(who, tensors, n, m->prepare_need, &chunks)) return rc;
+  if (!record || !factors) return OS2D_REFUSE(-1, "%s: null pointer", who);
+  for (int i = 0; i < n; ++i) {     // a record without elements is counted too: it had a gradient
+    if (!tensors[i].step) return OS2D_REFUSE(-1, "%s: null pointer (step of tensor %d)", who, i);
+    if ((m->prepare_need & 2) && !tensors[i].state2) return OS2D_REFUSE(-1, "%s: null pointer (state2 of tensor %d)", who, i);
+  }
+  if (n == 0) return 0;
+  double h0 = 0.0, h1 = 0.0, h2 = 0.0;
+  if (method == OS2D_TRAIN_OPTIM_ADAGRAD || method == OS2D_TRAIN_OPTIM_ADAMAX) h0 = hyper[0];
+  if (method == OS2D_TRAIN_OPTIM_ASGD) h0 = hyper[0], h1 = hyper[1], h2 = hyper[2];
+  hipLaunchKernelGGL(optim_prepare_ex_kernel, dim3(1), dim3(64), 0, os2d_stream(stream), table_of(tensors, n), n, method, record, h0, h1, h2,
+                     factors);
+  return os2d_launched("optim_prepare_ex_kernel");
+}
+
+extern "C" int os2d_train_optim_update_ex(int method, const os2d_train_optim_tensor* tensors, int n, const float* record, const float* factors,
+                                          const double* hyper, int nhyper, void* stream) {
+  const char* who = "os2d_train_optim_update_ex";
+  if (const int rc = check_hyper(who, method, hyper, nhyper)) return rc;
+  size_t chunks = 0;
+  if (const int rc = check_table(who, tensors, n, traits_of(method)->update_need, &chunks)) return rc;
+  if (!record || !factors) return OS2D_REFUSE(-1, "%s: null pointer", who);
+  if (chunks == 0) return 0;
+  HyperEx h = {};
+  switch (method) {
+    case OS2D_TRAIN_OPTIM_ADAGRAD: h.v0 = (float)hyper[1]; break;
+    case OS2D_TRAIN_OPTIM_ADADELTA:
+    case OS2D_TRAIN_OPTIM_RMSPROP: h.v0 = (float)hyper[0], h.v1 = (float)(1.0 - hyper[0]), h.v2 = (float)hyper[1]; break;
+    case OS2D_TRAIN_OPTIM_ADAMAX: h.v0 = (float)(1.0 - hyper[0]), h.v1 = (float)hyper[1], h.v2 = (float)hyper[2]; break;
+    case OS2D_TRAIN_OPTIM_ASGD: break;
+    default: h.v0 = (float)hyper[0], h.v1 = (float)hyper[1], h.v2 = (float)hyper[2], h.v3 = (float)hyper[3]; break;
+  }
+  const Table tab = table_of(tensors, n);
+  const int first = tensors[0].first_chunk;
+  switch (method) {
+    case OS2D_TRAIN_OPTIM_ADAGRAD: launch_update_ex<OS2D_TRAIN_OPTIM_ADAGRAD>(chunks, tab, n, first, record, factors, h, stream); break;
+    case OS2D_TRAIN_OPTIM_ADADELTA: launch_update_ex<OS2D_TRAIN_OPTIM_ADADELTA>(chunks, tab, n, first, record, factors, h, stream); break;
+    case OS2D_TRAIN_OPTIM_ADAMAX: launch_update_ex<OS2D_TRAIN_OPTIM_ADAMAX>(chunks, tab, n, first, record, factors, h, stream); break;
+    case OS2D_TRAIN_OPTIM_ASGD: launch_update_ex<OS2D_TRAIN_OPTIM_ASGD>(chunks, tab, n, first, record, factors, h, stream); break;
+    case OS2D_TRAIN_OPTIM_RMSPROP: launch_update_ex<OS2D_TRAIN_OPTIM_RMSPROP>(chunks, tab, n, first, record, factors, h, stream); break;
+    default: launch_update_ex<OS2D_TRAIN_OPTIM_RPROP>(chunks, tab, n, first, record, factors, h, stream); break;
+  }
+  return os2d_launched("optim_update_ex_kernel");
 }

@@ -1,15 +1,17 @@
-"""Optimisers and learning-rate annealing (reference os2d/engine/optimization.py), with the per-step work of SGD and Adam -
+"""Optimisers and learning-rate annealing (reference os2d/engine/optimization.py), with the per-step work of every method -
 gradient norm, clipping, the NaN guard and the update - on the multi-tensor HIP kernels of libos2d_train.so
 (os2d_train_optim_*, include/os2d_train.h).
 
 ``create_optimizer`` builds the reference's optimiser from its settings: "sgd" and "adam" give ``DeviceSGD`` / ``DeviceAdam``,
-the other six methods the stock ``torch.optim`` classes.  The device classes subclass ``torch.optim.SGD`` / ``Adam`` for their
-constructor, ``defaults``, ``param_groups`` and ``state_dict()`` layout only: state lives in ``self.state[p]`` under torch's own
-keys (``momentum_buffer``; ``step`` as a 0-dim device float tensor, ``exp_avg``, ``exp_avg_sq`` - the layout of
-``Adam(capturable=True)``), so checkpoints and torch's LR schedulers work unchanged.  ``clip_and_step(max_grad_norm)`` is
-``clip_grad_norm_`` + ``if not isnan(norm): step()`` decided on the device: it returns the norm as a device scalar and never
-waits for the device.
+the other six methods the stock ``torch.optim`` classes or, with ``on_device=True``, ``DeviceAdagrad``, ``DeviceAdadelta``,
+``DeviceAdamax``, ``DeviceASGD``, ``DeviceRMSprop``, ``DeviceRprop`` (os2d_train_optim_prepare_ex / update_ex).  The device
+classes subclass the ``torch.optim`` class of their method for its constructor, ``defaults``, ``param_groups`` and
+``state_dict()`` layout only: state lives in ``self.state[p]`` under torch's own keys (``momentum_buffer``; ``step`` as a 0-dim
+device float tensor, ``exp_avg``, ``exp_avg_sq`` - the layout of ``Adam(capturable=True)``; ``sum``, ``square_avg``, ... for the
+other methods), so checkpoints and torch's LR schedulers work unchanged.  ``clip_and_step(max_grad_norm)`` is ``clip_grad_norm_``
++ ``if not isnan(norm): step()`` decided on the device: it returns the norm as a device scalar and never waits for the device.
 """
+import ctypes
 import logging
 from statistics import median
 
@@ -79,7 +81,7 @@ class _Plan(object):
 
 
 class _DeviceStep(object):
-    """The step of DeviceSGD / DeviceAdam: everything but the method's state and hyperparameters."""
+    """The step of every device optimiser: everything but the method's state and hyperparameters."""
     _method = None
 
     # ---- what a subclass provides
@@ -87,7 +89,8 @@ class _DeviceStep(object):
         raise NotImplementedError
 
     def _hyper(self, group):
-        """(momentum or beta1, beta2, eps) of a group: tensors of one launch share them."""
+        """The hyperparameters of a group that tensors of one launch share: (momentum or beta1, beta2, eps) for SGD / Adam, the
+        method's `hyper` array of os2d_train_optim_*_ex for the others."""
         raise NotImplementedError
 
     def _state_of(self, p, group):
@@ -157,7 +160,7 @@ class _DeviceStep(object):
             lr = group["lr"]
             if isinstance(lr, torch.Tensor):
                 raise ValueError("{}: a tensor learning rate would need a host wait; use a float".format(type(self).__name__))
-            out.append((group, lr, group["weight_decay"], self._hyper(group)))
+            out.append((group, lr, group.get("weight_decay", 0.0), self._hyper(group)))      # (Rprop has no weight decay)
         return out
 
     def _build_plan(self, groups):
@@ -218,21 +221,29 @@ class _DeviceStep(object):
                 for p in group["params"]:
                     return torch.zeros((), dtype=torch.float32, device=p.device)
         dev = plan.entries[0][0].device
-        adam = self._method == _train_lib.OPTIM_ADAM
+        method = self._method
+        adam = method == _train_lib.OPTIM_ADAM
+        ex = method not in (_train_lib.OPTIM_SGD, _train_lib.OPTIM_ADAM)         # the *_ex entry points
+        per = _train_lib.OPTIM_FACTORS if ex else (2 if adam else 0)            # floats of prepare per tensor
         partials = torch.empty(max(plan.total_chunks, 1), dtype=torch.float64, device=dev)
         record = torch.empty(4, dtype=torch.float32, device=dev)
-        factors = torch.empty(2 * len(plan.entries), dtype=torch.float32, device=dev) if adam else None
+        factors = torch.empty(per * len(plan.entries), dtype=torch.float32, device=dev) if per else None
         call = _train_lib.call
         for arr, n, _, _ in plan.tables:
             call("os2d_train_optim_sumsq", arr, n, partials, plan.total_chunks, STREAM)
         call("os2d_train_optim_finalize", partials, plan.total_chunks, max_norm, record, STREAM)
-        for arr, n, offset, (h0, h1, h2) in plan.tables:
-            fp = None
+        for arr, n, offset, hyper in plan.tables:
+            fp = factors[per * offset:] if per else None         # this table's factors
+            if ex:
+                h = (ctypes.c_double * len(hyper))(*hyper)       # a host array: it travels in the kernel arguments
+                call("os2d_train_optim_prepare_ex", method, arr, n, record, h, len(hyper), fp, STREAM)
+                call("os2d_train_optim_update_ex", method, arr, n, record, fp, h, len(hyper), STREAM)
+                continue
+            h0, h1, h2 = hyper
             if adam:
-                fp = factors[2 * offset:]          # this table's (two floats per tensor) factors
                 call("os2d_train_optim_prepare", arr, n, record, h0, h1, fp, STREAM)
-            call("os2d_train_optim_update", self._method, arr, n, record, fp, h0, h1, h2, STREAM)
-        self._last = (record, factors)        # read by the stage tests: {norm, coef, skip, 0} and the per-tensor Adam factors
+            call("os2d_train_optim_update", method, arr, n, record, fp, h0, h1, h2, STREAM)
+        self._last = (record, factors)        # read by the stage tests: {norm, coef, skip, 0} and the per-tensor factors of prepare
         return record[0]
 
 
@@ -304,6 +315,162 @@ class DeviceAdam(_DeviceStep, optim.Adam):
         st["exp_avg_sq"] = self._like(p, st["exp_avg_sq"])
 
 
+class _MethodStep(_DeviceStep):
+    """The step of the reference's other six methods (os2d_train_optim_prepare_ex / update_ex).  A subclass names torch's keys of
+    its one or two per-element state tensors (``_keys``: state1, state2); ``step`` is a 0-dim float32 tensor on the parameter's
+    device for all of them, advanced on the device and only on a step that is not skipped."""
+    _keys = ()
+    _refused = ("maximize", "differentiable")          # group options that must be false
+
+    def _check_group(self, group):
+        for name in self._refused:
+            if group.get(name):
+                raise ValueError("{} does not support {}={!r}".format(type(self).__name__, name, group[name]))
+
+    def _new_state(self, p, group, key):
+        return torch.zeros_like(p, memory_format=torch.contiguous_format)
+
+    def _state_of(self, p, group):
+        st = self.state[p]
+        if "step" not in st:
+            st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
+            for key in self._keys:
+                st[key] = self._new_state(p, group, key)
+        return st[self._keys[0]], (st[self._keys[1]] if len(self._keys) > 1 else None), st["step"]
+
+    def _adopt_group(self, group):
+        if "capturable" in group:             # a checkpoint of the stock optimiser carries False: `step` would stay on the host
+            group["capturable"] = True
+
+    @staticmethod
+    def _scalar(p, value):
+        """a count, eta or mu of a checkpoint (a tensor of any device, or a number of old torch versions) as a fresh 0-dim
+        float32 tensor on the parameter's device"""
+        if not isinstance(value, torch.Tensor):
+            value = torch.tensor(float(value))
+        return value.detach().to(device=p.device, dtype=torch.float32).reshape(()).clone()
+
+    def _adopt_param_state(self, p, st):
+        st["step"] = self._scalar(p, st["step"])
+        for key in self._keys:
+            st[key] = self._like(p, st[key])
+
+
+class DeviceAdagrad(_MethodStep, optim.Adagrad):
+    """``torch.optim.Adagrad`` (``lr_decay``, L2 weight decay, ``initial_accumulator_value``) as multi-tensor HIP kernels.
+    State: ``step``, ``sum``.  The stock class creates both in its constructor, the count on the host; it is moved to the
+    parameter's device here."""
+    _method = _train_lib.OPTIM_ADAGRAD
+    _keys = ("sum",)
+    _refused = ("maximize", "differentiable", "fused")
+
+    def __init__(self, params, lr=1e-2, lr_decay=0.0, weight_decay=0.0, initial_accumulator_value=0.0, eps=1e-10):
+        optim.Adagrad.__init__(self, params, lr=lr, lr_decay=lr_decay, weight_decay=weight_decay,
+                               initial_accumulator_value=initial_accumulator_value, eps=eps)
+        self._adopt_state()
+
+    def _hyper(self, group):
+        return (float(group["lr_decay"]), float(group["eps"]))
+
+    def _new_state(self, p, group, key):
+        return torch.full_like(p, group["initial_accumulator_value"], memory_format=torch.contiguous_format)
+
+
+class DeviceAdadelta(_MethodStep, optim.Adadelta):
+    """``torch.optim.Adadelta`` (L2 weight decay) as multi-tensor HIP kernels.  State: ``step``, ``square_avg``, ``acc_delta``."""
+    _method = _train_lib.OPTIM_ADADELTA
+    _keys = ("square_avg", "acc_delta")
+
+    def __init__(self, params, lr=1.0, rho=0.9, eps=1e-6, weight_decay=0.0):
+        optim.Adadelta.__init__(self, params, lr=lr, rho=rho, eps=eps, weight_decay=weight_decay, capturable=True)
+        self._plan = None
+
+    def _hyper(self, group):
+        return (float(group["rho"]), float(group["eps"]))
+
+
+class DeviceAdamax(_MethodStep, optim.Adamax):
+    """``torch.optim.Adamax`` (L2 weight decay) as multi-tensor HIP kernels, with the arithmetic of the stock class's
+    ``capturable=False`` route (the bias correction in double).  State: ``step``, ``exp_avg``, ``exp_inf``."""
+    _method = _train_lib.OPTIM_ADAMAX
+    _keys = ("exp_avg", "exp_inf")
+
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        optim.Adamax.__init__(self, params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=True)
+        self._plan = None
+
+    def _hyper(self, group):
+        b1, b2 = group["betas"]
+        return (float(b1), float(b2), float(group["eps"]))
+
+
+class DeviceASGD(_MethodStep, optim.ASGD):
+    """``torch.optim.ASGD`` (L2 weight decay) as multi-tensor HIP kernels.  State: ``step``, ``eta``, ``mu``, ``ax``.
+
+    ``eta`` and ``mu`` are torch's 0-dim tensors, and here the two elements of ONE two-float device tensor per parameter, which
+    the tensor record's ``state2`` points to: the prepare kernel hands the update the pair the previous step left and writes
+    the next one, both functions of the step count alone.  ``state_dict()`` shows them as torch does; state that arrives from
+    outside is copied into a fresh pair."""
+    _method = _train_lib.OPTIM_ASGD
+    _keys = ("ax",)
+
+    def __init__(self, params, lr=1e-2, lambd=1e-4, alpha=0.75, t0=1e6, weight_decay=0.0):
+        optim.ASGD.__init__(self, params, lr=lr, lambd=lambd, alpha=alpha, t0=t0, weight_decay=weight_decay, capturable=True)
+        self._plan = None
+
+    def _hyper(self, group):
+        return (float(group["lambd"]), float(group["alpha"]), float(group["t0"]))
+
+    def _state_of(self, p, group):
+        st = self.state[p]
+        if "step" not in st:
+            st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
+            start = torch.ones(2, dtype=torch.float32, device=p.device)      # eta = lr, mu = 1 before the first step
+            start[0] = group["lr"]
+            st["eta"], st["mu"] = start[0], start[1]
+            st["ax"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return st["ax"], st["eta"], st["step"]
+
+    def _adopt_param_state(self, p, st):
+        super(DeviceASGD, self)._adopt_param_state(p, st)
+        pair = torch.stack([self._scalar(p, st["eta"]), self._scalar(p, st["mu"])])
+        st["eta"], st["mu"] = pair[0], pair[1]
+
+
+class DeviceRMSprop(_MethodStep, optim.RMSprop):
+    """``torch.optim.RMSprop`` (L2 weight decay; no momentum, not centered) as multi-tensor HIP kernels.  State: ``step``,
+    ``square_avg``."""
+    _method = _train_lib.OPTIM_RMSPROP
+    _keys = ("square_avg",)
+    _refused = ("maximize", "differentiable", "momentum", "centered")
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0):
+        optim.RMSprop.__init__(self, params, lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay, capturable=True)
+        self._plan = None
+
+    def _hyper(self, group):
+        return (float(group["alpha"]), float(group["eps"]))
+
+
+class DeviceRprop(_MethodStep, optim.Rprop):
+    """``torch.optim.Rprop`` as multi-tensor HIP kernels.  State: ``step``, ``prev``, ``step_size`` (filled with the group's
+    learning rate at creation).  No weight decay, as in torch."""
+    _method = _train_lib.OPTIM_RPROP
+    _keys = ("prev", "step_size")
+
+    def __init__(self, params, lr=1e-2, etas=(0.5, 1.2), step_sizes=(1e-6, 50)):
+        optim.Rprop.__init__(self, params, lr=lr, etas=etas, step_sizes=step_sizes, capturable=True)
+        self._plan = None
+
+    def _hyper(self, group):
+        return tuple(float(v) for v in tuple(group["etas"]) + tuple(group["step_sizes"]))
+
+    def _new_state(self, p, group, key):
+        if key == "prev":
+            return torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return torch.full_like(p, group["lr"], memory_format=torch.contiguous_format)
+
+
 def _setting(cfg, keywords, name):
     if name in keywords:
         return keywords[name]
@@ -315,32 +482,35 @@ def _setting(cfg, keywords, name):
 def create_optimizer(parameters, cfg=None, optimizer_state=None, **keywords):
     """reference optimization.py:9-35.  The settings ``optim_method``, ``lr``, ``weight_decay``, ``sgd_momentum`` come from
     ``cfg`` (any object with these attributes, e.g. the reference's cfg.train.optim) or from keywords, which win.  "sgd" and
-    "adam" give the device optimisers; ``optimizer_state`` is a ``state_dict()`` of either kind of optimiser."""
-    unknown = set(keywords) - {"optim_method", "lr", "weight_decay", "sgd_momentum"}
+    "adam" give the device optimisers; the other six methods give the stock ``torch.optim`` classes, or with ``on_device=True`` (a
+    keyword or an attribute of ``cfg``; default False) ``DeviceAdagrad`` .. ``DeviceRprop``.  ``optimizer_state`` is a
+    ``state_dict()`` of either kind of optimiser."""
+    unknown = set(keywords) - {"optim_method", "lr", "weight_decay", "sgd_momentum", "on_device"}
     if unknown:
         raise TypeError("create_optimizer: unknown settings {}".format(sorted(unknown)))
     lr = _setting(cfg, keywords, "lr")
     method = _setting(cfg, keywords, "optim_method")
     optim_method = method.casefold()
+    on_device = bool(keywords["on_device"] if "on_device" in keywords else getattr(cfg, "on_device", False))
 
     def wd():
         return _setting(cfg, keywords, "weight_decay")
     if optim_method == "sgd":
         optimizer = DeviceSGD(parameters, lr=lr, weight_decay=wd(), momentum=_setting(cfg, keywords, "sgd_momentum"))
     elif optim_method == "adagrad":
-        optimizer = optim.Adagrad(parameters, lr=lr, weight_decay=wd())
+        optimizer = (DeviceAdagrad if on_device else optim.Adagrad)(parameters, lr=lr, weight_decay=wd())
     elif optim_method == "adadelta":
-        optimizer = optim.Adadelta(parameters, lr=lr, weight_decay=wd())
+        optimizer = (DeviceAdadelta if on_device else optim.Adadelta)(parameters, lr=lr, weight_decay=wd())
     elif optim_method == "adam":
         optimizer = DeviceAdam(parameters, lr=lr, weight_decay=wd())
     elif optim_method == "adamax":
-        optimizer = optim.Adamax(parameters, lr=lr, weight_decay=wd())
+        optimizer = (DeviceAdamax if on_device else optim.Adamax)(parameters, lr=lr, weight_decay=wd())
     elif optim_method == "asgd":
-        optimizer = optim.ASGD(parameters, lr=lr, t0=5000, weight_decay=wd())
+        optimizer = (DeviceASGD if on_device else optim.ASGD)(parameters, lr=lr, t0=5000, weight_decay=wd())
     elif optim_method == "rmsprop":
-        optimizer = optim.RMSprop(parameters, lr=lr, weight_decay=wd())
+        optimizer = (DeviceRMSprop if on_device else optim.RMSprop)(parameters, lr=lr, weight_decay=wd())
     elif optim_method == "rprop":
-        optimizer = optim.Rprop(parameters, lr=lr)
+        optimizer = (DeviceRprop if on_device else optim.Rprop)(parameters, lr=lr)
     else:
         raise RuntimeError("Invalid optim method: " + method)
     if optimizer_state is not None:

@@ -32,7 +32,8 @@ def train_one_batch(net, criterion, optimizer, box_coder, images, class_images, 
     ``cls_preds_for_neg`` = the transform-detached scores (unless ``train_transform_on_negs``), backward, gradient-norm
     clipping, and an optimiser step unless the norm is NaN.  ``loc_targets`` / ``class_targets`` are the encoded targets of
     the batch; None = encoded here with ``box_coder.encode_batch``.  Returns the criterion's losses with "grad_norm" added
-    (device scalars).  An optimiser with ``clip_and_step`` (os2d_amd/engine/optimization.py: DeviceSGD, DeviceAdam) clips,
+    (device scalars).  An optimiser with ``clip_and_step`` (os2d_amd/engine/optimization.py: DeviceSGD, DeviceAdam, and with
+    ``create_optimizer(..., on_device=True)`` the device classes of the reference's other six methods) clips,
     checks and steps on the device over ITS parameters, and nothing here waits for the device; with any other optimiser the
     NaN check of the norm is a host wait, as in the reference."""
     optimizer.zero_grad()

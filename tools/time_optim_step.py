@@ -1,17 +1,20 @@
 """Times the last line of a training step on the parameter set of the model (ResNet50-C4 + TransformNet, synthetic weights,
 random gradients), both routes in one process:
 
-    device   DeviceSGD / DeviceAdam.clip_and_step (os2d_amd/engine/optimization.py, os2d_train_optim_* kernels)
-    parent   clip_grad_norm_ + float(norm) + torch.optim.SGD / Adam.step, what train_one_batch did before
+    device   clip_and_step of the device optimiser (os2d_amd/engine/optimization.py, os2d_train_optim_* kernels):
+             create_optimizer(..., on_device=True)
+    parent   clip_grad_norm_ + float(norm) + the stock torch.optim class's step, what train_one_batch does with a stock optimiser
 
 Per route and method: host time until the step is enqueued (the parent's includes its host wait: float(norm)), device time
 between two events around the step (it spans the gaps in which the device waits for the host), and from torch.profiler, where
 it works, the number of kernel launches and the sum of the kernels' durations (the device route's launch count also from its
 launch plan).  The device kernels' bytes - SGD 28 B / element (norm pass 4; update: read p, g, buf 12, write p, g, buf 12),
-Adam 36 - over the kernels' durations, as a fraction of HBM_COPY, the copy rate of tools/hbm_peak.hip.
+Adam 36; Adagrad, RMSprop, ASGD 28 (one state tensor), Adadelta, Adamax, Rprop 36 (two) - over the kernels' durations, as a
+fraction of HBM_COPY, the copy rate of tools/hbm_peak.hip.
 Medians of 20 after warm-up.
 
-    python tools/time_optim_step.py            # one JSON line
+    python tools/time_optim_step.py                        # one JSON line: sgd and adam
+    python tools/time_optim_step.py adagrad rprop          # the named methods; "all": the eight of the reference
 """
 import json
 import os
@@ -32,7 +35,9 @@ from os2d_amd.utils import synthetic  # noqa: E402
 HBM_COPY = 4.8e12        # bytes / s read + written, tools/hbm_peak.hip
 MAX_NORM = 100.0
 SETTINGS = dict(lr=1e-3, weight_decay=1e-4)
-BYTES = {"sgd": 28, "adam": 36}
+BYTES = {"sgd": 28, "adam": 36, "adagrad": 28, "adadelta": 36, "adamax": 36, "asgd": 28, "rmsprop": 28, "rprop": 36}
+STOCK = {"sgd": torch.optim.SGD, "adam": torch.optim.Adam, "adagrad": torch.optim.Adagrad, "adadelta": torch.optim.Adadelta,
+         "adamax": torch.optim.Adamax, "asgd": torch.optim.ASGD, "rmsprop": torch.optim.RMSprop, "rprop": torch.optim.Rprop}
 REPS, WARMUP = 20, 5
 
 
@@ -44,10 +49,12 @@ def parameter_set(device):
 
 def make(route, method, shapes_from):
     ps = [p.clone().requires_grad_() for p in shapes_from]
+    opt = O.create_optimizer(ps, optim_method=method, sgd_momentum=0.9, on_device=route == "device", **SETTINGS)
     if route == "device":
-        opt = O.DeviceSGD(ps, momentum=0.9, **SETTINGS) if method == "sgd" else O.DeviceAdam(ps, **SETTINGS)
         return ps, opt, lambda: opt.clip_and_step(MAX_NORM)
-    opt = torch.optim.SGD(ps, momentum=0.9, **SETTINGS) if method == "sgd" else torch.optim.Adam(ps, **SETTINGS)
+    if method in ("sgd", "adam"):          # create_optimizer has no stock route for these two
+        opt = torch.optim.SGD(ps, momentum=0.9, **SETTINGS) if method == "sgd" else torch.optim.Adam(ps, **SETTINGS)
+    assert type(opt) is STOCK[method]
 
     def step():
         norm = torch.nn.utils.clip_grad_norm_(ps, MAX_NORM, norm_type=2)
@@ -96,20 +103,20 @@ def measure(route, method, params, grads):
     out = dict(host_us=float(np.median(host)), device_us=float(np.median(dev)))
     if route == "device":
         tables = len(opt._plan.tables)
-        out["launches"] = 2 * tables + 1 + (tables if method == "adam" else 0)
+        out["launches"] = 2 * tables + 1 + (0 if method == "sgd" else tables)      # sumsq, update (+ prepare) per table; finalize
     refill()
     out["launches_profiled"], out["kernels_us"] = launches(step)
     return out
 
 
-def main():
+def main(methods):
     device = torch.device("cuda:0")
     params = parameter_set(device)
     gen = torch.Generator(device=device).manual_seed(3)
     grads = [torch.randn(p.shape, device=device, generator=gen) * 1e-2 for p in params]
     elements = sum(p.numel() for p in params)
     result = dict(tensors=len(params), elements=elements, hbm_copy_bytes_per_s=HBM_COPY)
-    for method in ("sgd", "adam"):
+    for method in methods:
         for route in ("device", "parent"):
             r = measure(route, method, params, grads)
             if route == "device":
@@ -121,4 +128,10 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    names = [a.lower() for a in sys.argv[1:]] or ["sgd", "adam"]
+    if names == ["all"]:
+        names = list(BYTES)
+    unknown = [a for a in names if a not in BYTES]
+    if unknown:
+        sys.exit("unknown methods {} (known: {}, or all)".format(unknown, " ".join(BYTES)))
+    main(names)
