@@ -2,7 +2,8 @@
 (os2d/engine/train.py:142-370) on the drawn inputs of tests/mining_cases.py, with get_box_to_cut_anchor, the transformed encode
 and remap outputs and the per-anchor losses recorded on the way.
 
-    python tests/golden/make_mining_golden.py
+    python tests/golden/make_mining_golden.py             every fixture
+    python tests/golden/make_mining_golden.py geometry    mining_geometry.npz only
 
 How the reference is driven: its train module's ``make_iterator_extract_scores_from_images_batched`` is replaced by a generator
 that yields the drawn scores and corners; a stub dataloader supplies ``box_coder``, ``get_image_annotation_for_imageid``,
@@ -14,7 +15,12 @@ Conditions asserted on the reference alone (the seed is redrawn until they hold)
 threshold; per role the scores of the records and of the best candidate surviving after them differ pairwise by more than 1e-4
 relative; some role returns K records, some fewer than K but more than 0, and the image without a box returns none for pos and
 pos_loc; every candidate list has at most 10,000 entries (where the reference's chunked NMS is global greedy NMS); every branch
-of the crop placement is hit (case "pyr")."""
+of the crop placement is hit (case "pyr").
+
+mining_geometry.npz: the reference's get_box_to_cut_anchor on every geometry of tests/mining_stage_cases.py (strides that are no
+power of two, odd crops, images that are no multiple of the stride, crops larger than the image on one axis, a 3,600 px level),
+without a transform and, for a handful, through a TransformList of resize / flip / crop closures.  Asserted on the reference alone:
+the loop model (tests/mining_stage_model.py) and the torch model equal it bit for bit, and every branch is hit on each axis."""
 import importlib.util
 import os
 import sys
@@ -49,12 +55,14 @@ spec.loader.exec_module(mog)        # installs the torchvision stand-in and the 
 import os2d.engine.train as ref_train  # noqa: E402
 from os2d.modeling.box_coder import Os2dBoxCoder, BoxGridGenerator  # noqa: E402
 from os2d.engine.objective import Os2dObjective  # noqa: E402
-from os2d.structures.bounding_box import BoxList, FLIP_LEFT_RIGHT  # noqa: E402
+from os2d.structures.bounding_box import BoxList, FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM  # noqa: E402
 from os2d.structures.feature_map import FeatureMapSize  # noqa: E402
 from os2d.structures.transforms import TransformList  # noqa: E402
 
 import mining_cases as MC  # noqa: E402
 import mining_model as MM  # noqa: E402
+import mining_stage_cases as SC  # noqa: E402
+import mining_stage_model as SM  # noqa: E402
 from objective_util import BAND  # noqa: E402
 
 
@@ -214,6 +222,45 @@ def record(name, seed):
     return out
 
 
+def steps_transform(steps):
+    """The steps of a geometry (applied first to last) as the reference's TransformList (which runs its closures last to first)."""
+    def closure(s):
+        if s[0] == "resize":
+            return lambda b: b.resize(FeatureMapSize(w=s[1], h=s[2]))
+        if s[0] == "hflip":
+            return lambda b: b.transpose(FLIP_LEFT_RIGHT)
+        if s[0] == "vflip":
+            return lambda b: b.transpose(FLIP_TOP_BOTTOM)
+        return lambda b: b.crop(s[1:])
+    t = TransformList()
+    for s in reversed(steps):
+        t.append(closure(s))
+    return t
+
+
+def record_geometry():
+    out = {}
+    hit_x, hit_y = set(), set()
+    for g in SC.GEOMETRIES:
+        gen = BoxGridGenerator(box_size=FeatureMapSize(w=g["box"], h=g["box"]), box_stride=FeatureMapSize(w=g["stride"], h=g["stride"]))
+        img, crop = FeatureMapSize(w=g["img"][0], h=g["img"][1]), FeatureMapSize(w=g["crop"][0], h=g["crop"][1])
+        cb, ab, index = gen.get_box_to_cut_anchor(img, crop, FeatureMapSize(w=g["W"], h=g["H"]), steps_transform(g["steps"]) if g["steps"] else None)
+        assert torch.equal(index, torch.arange(g["H"] * g["W"]))
+        ops, size = SC.chain_ops(g["steps"], g["img"])
+        assert (cb.image_size.w, cb.image_size.h) == tuple(size), g["name"]
+        crops, anchors, bx, by = SC.geometry_model(g["name"])
+        assert np.array_equal(crops, cb.bbox_xyxy.numpy()) and np.array_equal(anchors, ab.bbox_xyxy.numpy()), \
+            "the loop model's crop placement differs from the reference: " + g["name"]
+        mc, ma, _ = MM.crop_boxes(g["H"], g["W"], g["stride"], g["box"], img.w, img.h, crop.w, crop.h, ops)
+        assert torch.equal(mc, cb.bbox_xyxy) and torch.equal(ma, ab.bbox_xyxy), "the torch model differs from the reference: " + g["name"]
+        hit_x |= set(bx)
+        hit_y |= set(by)
+        out["crop_" + g["name"]], out["anchor_" + g["name"]] = cb.bbox_xyxy.numpy(), ab.bbox_xyxy.numpy()
+    assert hit_x == hit_y == set(SM.BRANCHES), (hit_x, hit_y)
+    out["names"] = np.array([g["name"] for g in SC.GEOMETRIES])
+    return out
+
+
 def save(fname, arrays):
     path = os.path.join(HERE, fname)
     np.savez_compressed(path, **arrays)
@@ -225,7 +272,8 @@ def save(fname, arrays):
 if __name__ == "__main__":
     import logging
     logging.disable(logging.CRITICAL)
-    for case, c in MC.CASES.items():
+    save("mining_geometry.npz", record_geometry())
+    for case, c in ({} if sys.argv[1:] == ["geometry"] else MC.CASES).items():
         for seed in range(c["seed"], c["seed"] + 200):
             try:
                 arrays = record(case, seed)
