@@ -1,4 +1,4 @@
-"""In-tree build of the five HIP libraries for gfx950 with hipcc (no JIT cache: the .so files travel with the tree).
+"""In-tree build of the six HIP libraries for gfx950 with hipcc (no JIT cache: the .so files travel with the tree).
 
     python -m os2d_amd.build                      # build what is stale
     python -m os2d_amd.build --force
@@ -6,6 +6,7 @@
     python -m os2d_amd.build --eval               # only libos2d_eval.so (the VOC detection metric)
     python -m os2d_amd.build --image              # only libos2d_image.so (the image pyramid from uint8 images)
     python -m os2d_amd.build --augment            # only libos2d_augment.so (padded crops and colour distortion of training images)
+    python -m os2d_amd.build --backbone           # only libos2d_backbone.so (the frozen-BatchNorm epilogues of the backbone's inference route)
     python -m os2d_amd.build --variant TAG [--packed on|off|fft] [-DFLAG ...]
                                                   # diagnostic copy under tools/diag_libs/TAG/ (run with OS2D_HIP_LIB=...)
 """
@@ -88,15 +89,22 @@ IMAGE = Library("libos2d_image.so", IMAGE_CSRC, ["resample.hip"], FLAGS + PACKED
 AUGMENT_CSRC = os.path.join(HERE, "csrc_augment")
 AUGMENT = Library("libos2d_augment.so", AUGMENT_CSRC, ["resample_padded.hip", "color.hip"], FLAGS + PACKED_OFF, {}, [AUGMENT_CSRC, IMAGE_CSRC, SHARED],
                   "os2d_augment.h", "OS2D_AUGMENT_LIB")
+# The backbone's frozen-inference route (include/os2d_backbone.h): what runs between the convolutions of a
+# ResNet with folded BatchNorms.  Its kernels run next to MIOpen's convolutions and, under the pyramid runner, next to other
+# streams' MFMA waves: no packed FP32 (the finding above).  The units include none of csrc/*.h.
+BACKBONE_CSRC = os.path.join(HERE, "csrc_backbone")
+BACKBONE = Library("libos2d_backbone.so", BACKBONE_CSRC, ["pointwise.hip"], FLAGS + PACKED_OFF, {}, [BACKBONE_CSRC, SHARED],
+                   "os2d_backbone.h", "OS2D_BACKBONE_LIB")
 LIBRARIES = [HIP, TRAIN, EVAL, IMAGE]          # forward, backward, evaluation, image pyramid
-ALL_LIBRARIES = LIBRARIES + [AUGMENT]          # what build() makes
+ALL_LIBRARIES = LIBRARIES + [AUGMENT]          # the libraries of the head, the metric and the images
+BUILT_LIBRARIES = ALL_LIBRARIES + [BACKBONE]   # what build() makes
 
 
 def lib_path(lib):
     return os.path.join(LIB_DIR, lib.name)
 
 
-LIB_PATH, TRAIN_LIB_PATH, EVAL_LIB_PATH, IMAGE_LIB_PATH, AUGMENT_LIB_PATH = [lib_path(lib) for lib in ALL_LIBRARIES]
+LIB_PATH, TRAIN_LIB_PATH, EVAL_LIB_PATH, IMAGE_LIB_PATH, AUGMENT_LIB_PATH, BACKBONE_LIB_PATH = [lib_path(lib) for lib in BUILT_LIBRARIES]
 
 
 def headers(lib=HIP):
@@ -209,14 +217,14 @@ def build_library(lib, force=False, verbose=True):
 
 def build(force=False, verbose=True):
     """Build every library that is stale (force: all of them).  Returns the forward library's path."""
-    for lib in ALL_LIBRARIES:
+    for lib in BUILT_LIBRARIES:
         build_library(lib, force=force, verbose=verbose)
     return LIB_PATH
 
 
 # The names the per-library test fixtures call: each is the record's field or the one function bound to the record.
-TRAIN_SOURCES, EVAL_SOURCES, IMAGE_SOURCES, AUGMENT_SOURCES = TRAIN.sources, EVAL.sources, IMAGE.sources, AUGMENT.sources
-build_train, build_eval, build_image, build_augment = [functools.partial(build_library, lib) for lib in (TRAIN, EVAL, IMAGE, AUGMENT)]
+TRAIN_SOURCES, EVAL_SOURCES, IMAGE_SOURCES, AUGMENT_SOURCES, BACKBONE_SOURCES = TRAIN.sources, EVAL.sources, IMAGE.sources, AUGMENT.sources, BACKBONE.sources
+build_train, build_eval, build_image, build_augment, build_backbone = [functools.partial(build_library, lib) for lib in (TRAIN, EVAL, IMAGE, AUGMENT, BACKBONE)]
 train_up_to_date = functools.partial(up_to_date, TRAIN)
 
 
@@ -243,7 +251,7 @@ if __name__ == "__main__":
         packed = argv[argv.index("--packed") + 1] if "--packed" in argv else None
         print(build_variant(tag, packed, [a for a in argv if a.startswith("-D")], verbose=True))
     else:
-        only = [lib for lib, switch in ((TRAIN, "--train"), (EVAL, "--eval"), (IMAGE, "--image"), (AUGMENT, "--augment")) if switch in argv]
+        only = [lib for lib, switch in ((TRAIN, "--train"), (EVAL, "--eval"), (IMAGE, "--image"), (AUGMENT, "--augment"), (BACKBONE, "--backbone")) if switch in argv]
         if only:
             print(build_library(only[0], force="--force" in argv))
         else:

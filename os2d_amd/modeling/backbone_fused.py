@@ -1,0 +1,145 @@
+"""The frozen-BatchNorm inference route of ``ResNetFeatureExtractor``: MIOpen keeps the convolutions,
+everything between them runs as HIP kernels of libos2d_backbone.so (include/os2d_backbone.h).
+
+A BatchNorm in eval mode is one multiply-add per element.  ``fold_batchnorm`` turns its four tensors into a multiplier and an
+offset per channel, in float64, rounded once to fp32:
+
+    s = gamma / sqrt(running_var + eps)        t = beta - running_mean * s
+
+so a bottleneck is three convolutions and three kernels (bn + relu in place, twice; bn + residual [+ the downsample branch's bn]
++ relu) where the module path runs seven pointwise kernels, and the stem is one convolution and one kernel (bn + relu + maxpool)
+where the module path runs three full-tensor passes.
+
+The folds of all layers live in ONE device buffer that belongs to a ``FusedBackbone``, which an extractor keeps as a plain
+attribute: it adds no parameter, buffer or submodule, so ``state_dict()``, ``parameters()`` and ``named_modules()`` of the
+extractor are what they were.  The buffer is rebuilt when any of the four tensors of any norm layer was written to
+(``_version``) or replaced (``data_ptr``), or when the call's device changes.
+
+There is no fallback in here: a missing library raises ``Os2dLibraryError``.  WHICH calls take this route is part of its
+definition (``eligible``): inference calls on a contiguous fp32 device tensor with every BatchNorm in eval mode."""
+import torch
+import torch.nn as nn
+
+from .. import _backbone_lib
+from .._native import STREAM
+
+ROUTES = ("torch", "fused")
+ROUTE_ENV = "OS2D_BACKBONE_ROUTE"
+
+
+def fold_batchnorm(weight, bias, running_mean, running_var, eps):
+    """(s, t) of one or several concatenated BatchNorms as float32 tensors: float64 arithmetic, one rounding."""
+    s = weight.double() / torch.sqrt(running_var.double() + eps)
+    t = bias.double() - running_mean.double() * s
+    return s.float(), t.float()
+
+
+def norm_layers(extractor):
+    """The norm layers of an extractor in the order the runner meets them: the stem's, then per block bn1, bn2, bn3 and the
+    downsample branch's."""
+    layers = [extractor.bn1]
+    for stage in extractor.resnet_blocks:
+        for block in stage:
+            layers += [block.bn1, block.bn2, block.bn3]
+            if block.downsample is not None:
+                layers.append(block.downsample[1])
+    return layers
+
+
+def has_only_batchnorm(extractor):
+    return all(isinstance(m, nn.BatchNorm2d) for m in norm_layers(extractor))
+
+
+def frozen(extractor):
+    """Every norm layer is a BatchNorm2d in eval mode that normalises with running statistics (and has an affine part)."""
+    return all(isinstance(m, nn.BatchNorm2d) and not m.training and m.running_mean is not None and m.running_var is not None
+               and m.weight is not None and m.bias is not None for m in norm_layers(extractor))
+
+
+def eligible(extractor, x):
+    """Does this call take the fused route?  Grad mode off, a non-empty contiguous fp32 [N, 3, H, W] tensor on a HIP device, every
+    norm layer frozen.  Any other call (every training call among them) is the module path, unchanged."""
+    return (not torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and x.numel() > 0 and x.is_contiguous() and frozen(extractor))
+
+
+class FusedBackbone(object):
+    """Runner of the fused route over the module tree of one extractor; NOT a module (see the module docstring)."""
+
+    def __init__(self, extractor):
+        if not has_only_batchnorm(extractor):
+            raise ValueError("the fused backbone route folds BatchNorm2d layers: this extractor has other norm layers (GroupNorm)")
+        self.extractor = extractor
+        self._key = None
+        self._folds = None          # {id(norm layer): (s view, t view)}
+        self._buffer = None         # [2, sum of channels] float32 on the device: all s, then all t
+        self.rebuilds = 0
+
+    def _cache_key(self, device):
+        key = [device]
+        for m in norm_layers(self.extractor):
+            key += [id(m), m.eps]                   # the folds are looked up by layer: a copied runner rebuilds them
+            for v in (m.weight, m.bias, m.running_mean, m.running_var):
+                key += [v._version, v.data_ptr()]
+        return tuple(key)
+
+    def folds(self, device):
+        """{id(norm layer): (s, t)} as views of the one device buffer, rebuilt when a tensor they come from changed."""
+        key = self._cache_key(device)
+        if key == self._key:
+            return self._folds
+        layers = norm_layers(self.extractor)
+        with torch.no_grad():
+            cat = [torch.cat([getattr(m, name).detach().to(device).reshape(-1) for m in layers]) for name in ("weight", "bias", "running_mean", "running_var")]
+            eps = torch.cat([torch.full((m.num_features,), m.eps, dtype=torch.float64, device=device) for m in layers])
+            s, t = fold_batchnorm(cat[0], cat[1], cat[2], cat[3], eps)
+            self._buffer = torch.stack([s, t]).contiguous()
+        self._folds, at = {}, 0
+        for m in layers:
+            self._folds[id(m)] = (self._buffer[0, at:at + m.num_features], self._buffer[1, at:at + m.num_features])
+            at += m.num_features
+        if device.type == "cuda":
+            torch.cuda.current_stream(device).synchronize()       # the buffer serves calls on every stream from here on
+        self._key = key
+        self.rebuilds += 1
+        return self._folds
+
+    @staticmethod
+    def _bn_relu(x, fold):
+        n, c, h, w = x.shape
+        _backbone_lib.call("os2d_backbone_bn_relu", x, fold[0], fold[1], x, n, c, h * w, STREAM)
+        return x
+
+    @staticmethod
+    def _bn_add_relu(x, fold, r, fold_r):
+        n, c, h, w = x.shape
+        if r.shape != x.shape:
+            raise ValueError("residual of shape {} for a block output of shape {}".format(tuple(r.shape), tuple(x.shape)))
+        sr, tr = fold_r if fold_r is not None else (None, None)
+        _backbone_lib.call("os2d_backbone_bn_add_relu", x, fold[0], fold[1], r, sr, tr, x, n, c, h * w, STREAM)
+        return x
+
+    @staticmethod
+    def _bn_relu_maxpool(x, fold):
+        n, c, h, w = x.shape
+        y = torch.empty((n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=x.dtype, device=x.device)
+        _backbone_lib.call("os2d_backbone_bn_relu_maxpool", x, fold[0], fold[1], y, n, c, h, w, STREAM)
+        return y
+
+    def forward(self, x):
+        """x: contiguous fp32 [N, 3, H, W] on a HIP device, grad mode off (``eligible``).  Returns the C4 feature map."""
+        ex = self.extractor
+        folds = self.folds(x.device)
+        x = self._bn_relu_maxpool(ex.conv1(x).contiguous(), folds[id(ex.bn1)])
+        for stage in ex.resnet_blocks:
+            for block in stage:
+                out = self._bn_relu(block.conv1(x).contiguous(), folds[id(block.bn1)])
+                out = self._bn_relu(block.conv2(out).contiguous(), folds[id(block.bn2)])
+                out = block.conv3(out).contiguous()
+                if block.downsample is None:
+                    x = self._bn_add_relu(out, folds[id(block.bn3)], x, None)
+                else:
+                    x = self._bn_add_relu(out, folds[id(block.bn3)], block.downsample[0](x).contiguous(), folds[id(block.downsample[1])])
+        return x
+
+    __call__ = forward

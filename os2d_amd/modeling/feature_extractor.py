@@ -1,16 +1,20 @@
-"""ResNet-C4 feature extractor kept in PyTorch-ROCm (MIOpen), as BASELINE.json's north_star prescribes: the backbone
-is an input producer for the hot path, not part of it.
+"""ResNet-C4 feature extractor.  Its module path is PyTorch-ROCm (MIOpen convolutions, ATen BatchNorm / ReLU / pooling); it is
+the default (``inference_route = "torch"``) and the only path of every training call.  With ``inference_route = "fused"`` an
+inference call with frozen BatchNorms keeps MIOpen for the convolutions and runs everything between them - the folded BatchNorms,
+ReLUs, residual adds and the stem's pooling - as HIP kernels of libos2d_backbone.so (backbone_fused.py).
 
 Mirrors reference os2d/modeling/feature_extractor.py:13-129 (``build_feature_extractor``, ``ResNetFeatureExtractor``,
 ``resnet50_c4`` / ``resnet101_c4``).  torchvision is not available in this image, so the ResNet (v1.5 bottleneck:
 stride on the 3x3 convolution, as torchvision >= 0.5) is defined here with torchvision's module / parameter names
 (``conv1, bn1, layer1.0.conv1, layer1.0.downsample.0, ...``) so reference checkpoints load key-for-key.
 """
+import os
 from itertools import chain
 
 import torch.nn as nn
 
 from ..structures.feature_map import FeatureMapSize
+from . import backbone_fused
 
 GROUPNORM_NUMGROUPS = 32
 
@@ -46,7 +50,11 @@ class Bottleneck(nn.Module):
 
 class ResNetFeatureExtractor(nn.Module):
     """conv1-bn1-relu-maxpool-layer1..layer{level-1}; level 4 = C4: stride 16, 1024 channels
-    (reference feature_extractor.py:23-65)."""
+    (reference feature_extractor.py:23-65).
+
+    ``inference_route``: "torch" (the default; the environment variable OS2D_BACKBONE_ROUTE sets the initial value) or "fused".
+    "fused" needs BatchNorm layers (ValueError with GroupNorm) and is taken by the calls ``backbone_fused.eligible`` describes:
+    grad mode off, a contiguous fp32 HIP tensor, every BatchNorm in eval mode.  Every other call runs the modules below as they are."""
 
     def __init__(self, layers, level, feature_map_stride, feature_map_receptive_field, use_group_norm=False):
         super(ResNetFeatureExtractor, self).__init__()
@@ -67,6 +75,8 @@ class ResNetFeatureExtractor(nn.Module):
         for i, name in enumerate(names):
             setattr(self, name, self._make_layer(planes[i], layers[i], strides[i]))
         self._block_names = names
+        self._inference_route, self._fused = "torch", None      # plain attributes: no parameter, buffer or submodule
+        self.inference_route = os.environ.get(backbone_fused.ROUTE_ENV, "torch")
         for m in self.modules():   # torchvision's default initialisation
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
@@ -91,7 +101,27 @@ class ResNetFeatureExtractor(nn.Module):
             layers.append(Bottleneck(self.inplanes, planes, norm_layer=norm_layer))
         return nn.Sequential(*layers)
 
+    @property
+    def inference_route(self):
+        return self._inference_route
+
+    @inference_route.setter
+    def inference_route(self, route):
+        if route not in backbone_fused.ROUTES:
+            raise ValueError("inference_route is one of {}, not {!r}".format(backbone_fused.ROUTES, route))
+        if route == "fused" and not backbone_fused.has_only_batchnorm(self):
+            raise ValueError("inference_route 'fused' folds BatchNorm2d layers: this extractor normalises with GroupNorm")
+        self._inference_route = route
+
+    def fused_backbone(self):
+        """The runner of the fused route with its fold cache (made on first use)."""
+        if self._fused is None:
+            self._fused = backbone_fused.FusedBackbone(self)
+        return self._fused
+
     def forward(self, x):
+        if self._inference_route == "fused" and backbone_fused.eligible(self, x):
+            return self.fused_backbone().forward(x)
         x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         for layer in self.resnet_blocks:
             x = layer(x)
