@@ -1,4 +1,4 @@
-"""In-tree build of the six HIP libraries for gfx950 with hipcc (no JIT cache: the .so files travel with the tree).
+"""In-tree build of the seven HIP libraries for gfx950 with hipcc (no JIT cache: the .so files travel with the tree).
 
     python -m os2d_amd.build                      # build what is stale
     python -m os2d_amd.build --force
@@ -7,6 +7,7 @@
     python -m os2d_amd.build --image              # only libos2d_image.so (the image pyramid from uint8 images)
     python -m os2d_amd.build --augment            # only libos2d_augment.so (padded crops and colour distortion of training images)
     python -m os2d_amd.build --backbone           # only libos2d_backbone.so (the frozen-BatchNorm epilogues of the backbone's inference route)
+    python -m os2d_amd.build --backbone-conv      # only libos2d_backbone_conv.so (the backbone's 1x1 convolutions as fp32 MFMA GEMMs with folded-BatchNorm epilogues)
     python -m os2d_amd.build --variant TAG [--packed on|off|fft] [-DFLAG ...]
                                                   # diagnostic copy under tools/diag_libs/TAG/ (run with OS2D_HIP_LIB=...)
 """
@@ -97,14 +98,22 @@ BACKBONE = Library("libos2d_backbone.so", BACKBONE_CSRC, ["pointwise.hip"], FLAG
                    "os2d_backbone.h", "OS2D_BACKBONE_LIB")
 LIBRARIES = [HIP, TRAIN, EVAL, IMAGE]          # forward, backward, evaluation, image pyramid
 ALL_LIBRARIES = LIBRARIES + [AUGMENT]          # the libraries of the head, the metric and the images
-BUILT_LIBRARIES = ALL_LIBRARIES + [BACKBONE]   # what build() makes
+BUILT_LIBRARIES = ALL_LIBRARIES + [BACKBONE]   # the six that tests/test_backbone_model.py pins
+# The backbone's 1x1 convolutions as fp32 GEMMs on the fp32-input MFMA with the fold, residual and ReLU as the epilogue
+# (include/os2d_backbone_conv.h).  A library of its own: the exports and the ABI version of
+# libos2d_backbone.so are what they are.  Its unit includes csrc_backbone/backbone_common.h for the fold's arithmetic and the
+# argument checks; no packed FP32, as for every kernel that runs next to other streams.
+BACKBONE_CONV_CSRC = os.path.join(HERE, "csrc_backbone_conv")
+BACKBONE_CONV = Library("libos2d_backbone_conv.so", BACKBONE_CONV_CSRC, ["conv1x1.hip"], FLAGS + PACKED_OFF, {},
+                        [BACKBONE_CONV_CSRC, BACKBONE_CSRC, SHARED], "os2d_backbone_conv.h", "OS2D_BACKBONE_CONV_LIB")
+EVERY_LIBRARY = BUILT_LIBRARIES + [BACKBONE_CONV]      # what build() makes
 
 
 def lib_path(lib):
     return os.path.join(LIB_DIR, lib.name)
 
 
-LIB_PATH, TRAIN_LIB_PATH, EVAL_LIB_PATH, IMAGE_LIB_PATH, AUGMENT_LIB_PATH, BACKBONE_LIB_PATH = [lib_path(lib) for lib in BUILT_LIBRARIES]
+LIB_PATH, TRAIN_LIB_PATH, EVAL_LIB_PATH, IMAGE_LIB_PATH, AUGMENT_LIB_PATH, BACKBONE_LIB_PATH, BACKBONE_CONV_LIB_PATH = [lib_path(lib) for lib in EVERY_LIBRARY]
 
 
 def headers(lib=HIP):
@@ -217,14 +226,15 @@ def build_library(lib, force=False, verbose=True):
 
 def build(force=False, verbose=True):
     """Build every library that is stale (force: all of them).  Returns the forward library's path."""
-    for lib in BUILT_LIBRARIES:
+    for lib in EVERY_LIBRARY:
         build_library(lib, force=force, verbose=verbose)
     return LIB_PATH
 
 
 # The names the per-library test fixtures call: each is the record's field or the one function bound to the record.
 TRAIN_SOURCES, EVAL_SOURCES, IMAGE_SOURCES, AUGMENT_SOURCES, BACKBONE_SOURCES = TRAIN.sources, EVAL.sources, IMAGE.sources, AUGMENT.sources, BACKBONE.sources
-build_train, build_eval, build_image, build_augment, build_backbone = [functools.partial(build_library, lib) for lib in (TRAIN, EVAL, IMAGE, AUGMENT, BACKBONE)]
+build_train, build_eval, build_image, build_augment, build_backbone, build_backbone_conv = [functools.partial(build_library, lib) for lib in (TRAIN, EVAL, IMAGE, AUGMENT, BACKBONE,
+                                                                                                                                              BACKBONE_CONV)]
 train_up_to_date = functools.partial(up_to_date, TRAIN)
 
 
@@ -251,7 +261,8 @@ if __name__ == "__main__":
         packed = argv[argv.index("--packed") + 1] if "--packed" in argv else None
         print(build_variant(tag, packed, [a for a in argv if a.startswith("-D")], verbose=True))
     else:
-        only = [lib for lib, switch in ((TRAIN, "--train"), (EVAL, "--eval"), (IMAGE, "--image"), (AUGMENT, "--augment"), (BACKBONE, "--backbone")) if switch in argv]
+        only = [lib for lib, switch in ((TRAIN, "--train"), (EVAL, "--eval"), (IMAGE, "--image"), (AUGMENT, "--augment"), (BACKBONE, "--backbone"),
+                                         (BACKBONE_CONV, "--backbone-conv")) if switch in argv]
         if only:
             print(build_library(only[0], force="--force" in argv))
         else:

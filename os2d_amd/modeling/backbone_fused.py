@@ -15,15 +15,22 @@ attribute: it adds no parameter, buffer or submodule, so ``state_dict()``, ``par
 extractor are what they were.  The buffer is rebuilt when any of the four tensors of any norm layer was written to
 (``_version``) or replaced (``data_ptr``), or when the call's device changes.
 
+``inference_route = "fused_conv1x1"`` goes one step further: the 1x1 convolutions - conv1, conv3 and the
+downsample branch of every bottleneck, half of the backbone's arithmetic - run as fp32 GEMMs of libos2d_backbone_conv.so
+(include/os2d_backbone_conv.h) with the fold, the residual add and the ReLU as the GEMM's epilogue.  A bottleneck is then two or three
+GEMMs of ours, MIOpen's 3x3 convolution and one bn + relu kernel.  The weights go in as ``conv.weight`` lies in memory: no copy, no
+cache.  The stem and the fold cache are those of "fused".
+
 There is no fallback in here: a missing library raises ``Os2dLibraryError``.  WHICH calls take this route is part of its
 definition (``eligible``): inference calls on a contiguous fp32 device tensor with every BatchNorm in eval mode."""
 import torch
 import torch.nn as nn
 
-from .. import _backbone_lib
+from .. import _backbone_conv_lib, _backbone_lib
 from .._native import STREAM
 
-ROUTES = ("torch", "fused")
+ROUTES = ("torch", "fused", "fused_conv1x1")
+FOLDING_ROUTES = ("fused", "fused_conv1x1")          # the routes that fold BatchNorms: they need an extractor without GroupNorm
 ROUTE_ENV = "OS2D_BACKBONE_ROUTE"
 
 
@@ -48,6 +55,24 @@ def norm_layers(extractor):
 
 def has_only_batchnorm(extractor):
     return all(isinstance(m, nn.BatchNorm2d) for m in norm_layers(extractor))
+
+
+def pointwise_convs(extractor):
+    """The 1x1 convolutions of an extractor: per block conv1, conv3 and the downsample branch's."""
+    convs = []
+    for stage in extractor.resnet_blocks:
+        for block in stage:
+            convs += [block.conv1, block.conv3]
+            if block.downsample is not None:
+                convs.append(block.downsample[0])
+    return convs
+
+
+def plain_conv1x1(conv):
+    """What os2d_backbone_conv1x1 computes: a 1x1 Conv2d without bias, groups 1, dilation 1, no padding, stride 1 or 2 (the same both
+    ways), and a contiguous fp32 weight."""
+    return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.bias is None and conv.groups == 1 and conv.dilation == (1, 1)
+            and conv.padding == (0, 0) and conv.stride in ((1, 1), (2, 2)) and conv.weight.dtype == torch.float32 and conv.weight.is_contiguous())
 
 
 def frozen(extractor):
@@ -125,6 +150,35 @@ class FusedBackbone(object):
         y = torch.empty((n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=x.dtype, device=x.device)
         _backbone_lib.call("os2d_backbone_bn_relu_maxpool", x, fold[0], fold[1], y, n, c, h, w, STREAM)
         return y
+
+    @staticmethod
+    def _conv1x1(x, conv, fold, relu, r=None):
+        """relu?(fold(conv(x)) [+ r]) as ONE kernel; x and r contiguous, the output is new memory."""
+        if not plain_conv1x1(conv):
+            raise ValueError("the fused_conv1x1 route runs plain 1x1 convolutions (no bias, groups 1, dilation 1, padding 0, stride 1 or 2, "
+                             "contiguous fp32 weight), not {}".format(conv))
+        n, cin, h, w = x.shape
+        stride, cout = conv.stride[0], conv.out_channels
+        y = torch.empty((n, cout, (h - 1) // stride + 1, (w - 1) // stride + 1), dtype=x.dtype, device=x.device)
+        if r is not None and r.shape != y.shape:
+            raise ValueError("residual of shape {} for a block output of shape {}".format(tuple(r.shape), tuple(y.shape)))
+        _backbone_conv_lib.call("os2d_backbone_conv1x1", x, conv.weight.detach(), fold[0], fold[1], r, None, None, y, n, cin, cout, h, w,
+                                stride, int(relu), STREAM)
+        return y
+
+    def forward_conv1x1(self, x):
+        """The route "fused_conv1x1": as ``forward``, with every 1x1 convolution and what follows it as one GEMM of ours."""
+        ex = self.extractor
+        folds = self.folds(x.device)
+        x = self._bn_relu_maxpool(ex.conv1(x).contiguous(), folds[id(ex.bn1)])
+        for stage in ex.resnet_blocks:
+            for block in stage:
+                out = self._conv1x1(x, block.conv1, folds[id(block.bn1)], True)
+                out = self._bn_relu(block.conv2(out).contiguous(), folds[id(block.bn2)])
+                if block.downsample is not None:
+                    x = self._conv1x1(x, block.downsample[0], folds[id(block.downsample[1])], False)
+                x = self._conv1x1(out, block.conv3, folds[id(block.bn3)], True, r=x)
+        return x
 
     def forward(self, x):
         """x: contiguous fp32 [N, 3, H, W] on a HIP device, grad mode off (``eligible``).  Returns the C4 feature map."""

@@ -2,6 +2,8 @@
 the default (``inference_route = "torch"``) and the only path of every training call.  With ``inference_route = "fused"`` an
 inference call with frozen BatchNorms keeps MIOpen for the convolutions and runs everything between them - the folded BatchNorms,
 ReLUs, residual adds and the stem's pooling - as HIP kernels of libos2d_backbone.so (backbone_fused.py).
+With ``inference_route = "fused_conv1x1"`` the 1x1 convolutions of such a call run as fp32 MFMA GEMMs of libos2d_backbone_conv.so as
+well, with the fold, the residual add and the ReLU as their epilogue.
 
 Mirrors reference os2d/modeling/feature_extractor.py:13-129 (``build_feature_extractor``, ``ResNetFeatureExtractor``,
 ``resnet50_c4`` / ``resnet101_c4``).  torchvision is not available in this image, so the ResNet (v1.5 bottleneck:
@@ -52,9 +54,10 @@ class ResNetFeatureExtractor(nn.Module):
     """conv1-bn1-relu-maxpool-layer1..layer{level-1}; level 4 = C4: stride 16, 1024 channels
     (reference feature_extractor.py:23-65).
 
-    ``inference_route``: "torch" (the default; the environment variable OS2D_BACKBONE_ROUTE sets the initial value) or "fused".
-    "fused" needs BatchNorm layers (ValueError with GroupNorm) and is taken by the calls ``backbone_fused.eligible`` describes:
-    grad mode off, a contiguous fp32 HIP tensor, every BatchNorm in eval mode.  Every other call runs the modules below as they are."""
+    ``inference_route``: "torch" (the default; the environment variable OS2D_BACKBONE_ROUTE sets the initial value), "fused" or
+    "fused_conv1x1".  The last two need BatchNorm layers (ValueError with GroupNorm), "fused_conv1x1" plain 1x1 convolutions as well
+    (``backbone_fused.plain_conv1x1``); they are taken by the calls ``backbone_fused.eligible`` describes: grad mode off, a contiguous
+    fp32 HIP tensor, every BatchNorm in eval mode.  Every other call runs the modules below as they are."""
 
     def __init__(self, layers, level, feature_map_stride, feature_map_receptive_field, use_group_norm=False):
         super(ResNetFeatureExtractor, self).__init__()
@@ -109,8 +112,11 @@ class ResNetFeatureExtractor(nn.Module):
     def inference_route(self, route):
         if route not in backbone_fused.ROUTES:
             raise ValueError("inference_route is one of {}, not {!r}".format(backbone_fused.ROUTES, route))
-        if route == "fused" and not backbone_fused.has_only_batchnorm(self):
-            raise ValueError("inference_route 'fused' folds BatchNorm2d layers: this extractor normalises with GroupNorm")
+        if route in backbone_fused.FOLDING_ROUTES and not backbone_fused.has_only_batchnorm(self):
+            raise ValueError("inference_route {!r} folds BatchNorm2d layers: this extractor normalises with GroupNorm".format(route))
+        if route == "fused_conv1x1" and not all(backbone_fused.plain_conv1x1(c) for c in backbone_fused.pointwise_convs(self)):
+            raise ValueError("inference_route 'fused_conv1x1' runs plain 1x1 convolutions (no bias, groups 1, dilation 1, padding 0, "
+                             "stride 1 or 2, contiguous fp32 weight): this extractor has others")
         self._inference_route = route
 
     def fused_backbone(self):
@@ -122,6 +128,8 @@ class ResNetFeatureExtractor(nn.Module):
     def forward(self, x):
         if self._inference_route == "fused" and backbone_fused.eligible(self, x):
             return self.fused_backbone().forward(x)
+        if self._inference_route == "fused_conv1x1" and backbone_fused.eligible(self, x):
+            return self.fused_backbone().forward_conv1x1(x)
         x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         for layer in self.resnet_blocks:
             x = layer(x)

@@ -1,9 +1,11 @@
-"""Device-event timing of the backbone's two inference routes, alternated in ONE process:
+"""Device-event timing of the backbone's three inference routes (DESIGN.md sections 18 and 18.6), alternated in ONE process:
 
     python tools/time_backbone.py                         # every configuration, torch / fused / torch again (the spread)
+    python tools/time_backbone.py --route all             # torch / fused / fused_conv1x1 / fused again (the spread of "fused")
     python tools/time_backbone.py --only r50_960x1280     # one of them
     python tools/time_backbone.py --route fused --only r50_960x1280 --rounds 3      # one route (for a kernel trace)
     python tools/time_backbone.py --stem                  # the two stem variants alone at 960 x 1280
+    python tools/time_backbone.py --layers                # os2d_backbone_conv1x1 alone at every 1x1 layer of ResNet50 at 960 x 1280
 
 One JSON line per configuration on stdout (and appended to --out): the median and the minimum over --rounds rounds of the mean
 time of --iters calls.  Random weights and perturbed BatchNorms: the time does not depend on the values."""
@@ -81,11 +83,12 @@ def emit(record, out):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--route", choices=["both", "torch", "fused"], default="both")
+    ap.add_argument("--route", choices=["both", "all", "torch", "fused", "fused_conv1x1"], default="both")
     ap.add_argument("--only", action="append", help="configuration name (repeatable); default: all")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--stem", action="store_true", help="time the stem variants instead of the routes")
+    ap.add_argument("--layers", action="store_true", help="time the 1x1 GEMM of the fused_conv1x1 route layer by layer instead of the routes")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -93,6 +96,8 @@ def main():
     device = torch.device("cuda:0")
     if args.stem:
         return stem(device, args)
+    if args.layers:
+        return layers(device, args)
     for name, arch, shape in CONFIGS:
         if args.only and name not in args.only:
             continue
@@ -100,6 +105,9 @@ def main():
         x = torch.randn(*shape, device=device)
         if args.route == "both":
             arms = [("torch", run_route(ex, "torch", x)), ("fused", run_route(ex, "fused", x)), ("torch_again", run_route(ex, "torch", x))]
+        elif args.route == "all":
+            arms = [("torch", run_route(ex, "torch", x)), ("fused", run_route(ex, "fused", x)), ("fused_conv1x1", run_route(ex, "fused_conv1x1", x)),
+                    ("fused_again", run_route(ex, "fused", x))]
         else:
             arms = [(args.route, run_route(ex, args.route, x))]
         result = alternate(arms, args.rounds, args.iters)
@@ -108,6 +116,11 @@ def main():
             t = min(result["torch"]["median_ms"], result["torch_again"]["median_ms"])
             record["torch_spread"] = round(abs(result["torch"]["median_ms"] - result["torch_again"]["median_ms"]) / t, 4)
             record["fused_over_torch"] = round(result["fused"]["median_ms"] / t, 4)
+        if args.route == "all":
+            f = min(result["fused"]["median_ms"], result["fused_again"]["median_ms"])
+            record["fused_spread"] = round(abs(result["fused"]["median_ms"] - result["fused_again"]["median_ms"]) / f, 4)
+            record["fused_over_torch"] = round(f / result["torch"]["median_ms"], 4)
+            record["fused_conv1x1_over_fused"] = round(result["fused_conv1x1"]["median_ms"] / f, 4)
         emit(record, args.out)
         del ex, x
         torch.cuda.empty_cache()
@@ -125,6 +138,40 @@ def stem(device, args):
                 ("conv1_only", lambda: ex.conv1(x)),
                 ("conv1_then_pool_kernel", lambda: FusedBackbone._bn_relu_maxpool(ex.conv1(x), fold))]
         emit({"config": "stem_960x1280", "rounds": args.rounds, "iters": args.iters, "ms": alternate(arms, args.rounds, args.iters)}, args.out)
+
+
+def layers(device, args):
+    """os2d_backbone_conv1x1 with the epilogue of its place in the block, at the input each 1x1 convolution of ResNet50-C4 sees for a
+    1 x 3 x 960 x 1280 image (240 x 320 after the stem, halved by layer2 and layer3): median time of a call, the TFLOP/s that time
+    implies (2 Cin Cout pixels) and the bytes/s (x, y, the residual and w, each once)."""
+    from os2d_amd.modeling.backbone_fused import FusedBackbone
+    ex = make_extractor("resnet50", device)
+    folds = ex.fused_backbone().folds(device)
+    h, w, seen = 240, 320, set()
+    with torch.no_grad():
+        for stage in ex.resnet_blocks:
+            for block in stage:
+                ho, wo = (h - 1) // block.stride + 1, (w - 1) // block.stride + 1
+                sites = [("conv1", block.conv1, block.bn1, (h, w), True, False), ("conv3", block.conv3, block.bn3, (ho, wo), True, True)]
+                if block.downsample is not None:
+                    sites.append(("downsample", block.downsample[0], block.downsample[1], (h, w), False, False))
+                for role, conv, bn, (hi, wi), relu, residual in sites:
+                    key = (role, conv.in_channels, conv.out_channels, conv.stride[0], hi, wi)
+                    if key in seen:
+                        continue
+                    seen.add(key)
+                    x = torch.randn(1, conv.in_channels, hi, wi, device=device)
+                    so, wo_ = (hi - 1) // conv.stride[0] + 1, (wi - 1) // conv.stride[0] + 1
+                    r = torch.randn(1, conv.out_channels, so, wo_, device=device) if residual else None
+                    fn = lambda: FusedBackbone._conv1x1(x, conv, folds[id(bn)], relu, r)
+                    ms = alternate([("conv1x1", fn)], args.rounds, 20)["conv1x1"]
+                    pixels = so * wo_
+                    flop = 2.0 * conv.in_channels * conv.out_channels * pixels
+                    moved = 4.0 * (x.numel() if conv.stride[0] == 1 else conv.in_channels * pixels) + 4.0 * conv.out_channels * pixels * (2 if residual else 1) \
+                        + 4.0 * conv.weight.numel()
+                    emit({"config": "layer", "role": role, "Cin": conv.in_channels, "Cout": conv.out_channels, "stride": conv.stride[0], "H": hi, "W": wi,
+                          "ms": ms, "tflops": round(flop / ms["median_ms"] / 1e9, 1), "tbytes_per_s": round(moved / ms["median_ms"] / 1e9, 2)}, args.out)
+                h, w = ho, wo
 
 
 if __name__ == "__main__":
