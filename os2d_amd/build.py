@@ -1,4 +1,4 @@
-"""In-tree build of the seven HIP libraries for gfx950 with hipcc (no JIT cache: the .so files travel with the tree).
+"""In-tree build of the eight HIP libraries for gfx950 with hipcc (no JIT cache: the .so files travel with the tree).
 
     python -m os2d_amd.build                      # build what is stale
     python -m os2d_amd.build --force
@@ -8,6 +8,7 @@
     python -m os2d_amd.build --augment            # only libos2d_augment.so (padded crops and colour distortion of training images)
     python -m os2d_amd.build --backbone           # only libos2d_backbone.so (the frozen-BatchNorm epilogues of the backbone's inference route)
     python -m os2d_amd.build --backbone-conv      # only libos2d_backbone_conv.so (the backbone's 1x1 convolutions as fp32 MFMA GEMMs with folded-BatchNorm epilogues)
+    python -m os2d_amd.build --backbone-conv-bf16 # only libos2d_backbone_conv_bf16.so (the same 1x1 convolutions in split-bf16 arithmetic on the bf16 MFMA)
     python -m os2d_amd.build --variant TAG [--packed on|off|fft] [-DFLAG ...]
                                                   # diagnostic copy under tools/diag_libs/TAG/ (run with OS2D_HIP_LIB=...)
 """
@@ -106,7 +107,15 @@ BUILT_LIBRARIES = ALL_LIBRARIES + [BACKBONE]   # the six that tests/test_backbon
 BACKBONE_CONV_CSRC = os.path.join(HERE, "csrc_backbone_conv")
 BACKBONE_CONV = Library("libos2d_backbone_conv.so", BACKBONE_CONV_CSRC, ["conv1x1.hip"], FLAGS + PACKED_OFF, {},
                         [BACKBONE_CONV_CSRC, BACKBONE_CSRC, SHARED], "os2d_backbone_conv.h", "OS2D_BACKBONE_CONV_LIB")
-EVERY_LIBRARY = BUILT_LIBRARIES + [BACKBONE_CONV]      # what build() makes
+EVERY_LIBRARY = BUILT_LIBRARIES + [BACKBONE_CONV]      # the seven that tests/test_backbone_conv_model.py pins
+# The same 1x1 convolutions in split-bf16 arithmetic: three bf16 parts per fp32 operand, six products on the bf16 MFMA
+# (include/os2d_backbone_conv_bf16.h).  An eighth library: the exports, the ABI version and the signature of
+# libos2d_backbone_conv.so are what they are.  bf16x3_split.h of its directory is the split, for the device and for a host program; the
+# unit includes csrc_backbone/backbone_common.h as the fp32 unit does.  No packed FP32.
+BACKBONE_CONV_BF16_CSRC = os.path.join(HERE, "csrc_backbone_conv_bf16")
+BACKBONE_CONV_BF16 = Library("libos2d_backbone_conv_bf16.so", BACKBONE_CONV_BF16_CSRC, ["conv1x1_bf16x3.hip"], FLAGS + PACKED_OFF, {},
+                             [BACKBONE_CONV_BF16_CSRC, BACKBONE_CSRC, SHARED], "os2d_backbone_conv_bf16.h", "OS2D_BACKBONE_CONV_BF16_LIB")
+EVERYTHING = EVERY_LIBRARY + [BACKBONE_CONV_BF16]      # what build() makes
 
 
 def lib_path(lib):
@@ -114,6 +123,7 @@ def lib_path(lib):
 
 
 LIB_PATH, TRAIN_LIB_PATH, EVAL_LIB_PATH, IMAGE_LIB_PATH, AUGMENT_LIB_PATH, BACKBONE_LIB_PATH, BACKBONE_CONV_LIB_PATH = [lib_path(lib) for lib in EVERY_LIBRARY]
+BACKBONE_CONV_BF16_LIB_PATH = lib_path(BACKBONE_CONV_BF16)
 
 
 def headers(lib=HIP):
@@ -226,7 +236,7 @@ def build_library(lib, force=False, verbose=True):
 
 def build(force=False, verbose=True):
     """Build every library that is stale (force: all of them).  Returns the forward library's path."""
-    for lib in EVERY_LIBRARY:
+    for lib in EVERYTHING:
         build_library(lib, force=force, verbose=verbose)
     return LIB_PATH
 
@@ -235,6 +245,7 @@ def build(force=False, verbose=True):
 TRAIN_SOURCES, EVAL_SOURCES, IMAGE_SOURCES, AUGMENT_SOURCES, BACKBONE_SOURCES = TRAIN.sources, EVAL.sources, IMAGE.sources, AUGMENT.sources, BACKBONE.sources
 build_train, build_eval, build_image, build_augment, build_backbone, build_backbone_conv = [functools.partial(build_library, lib) for lib in (TRAIN, EVAL, IMAGE, AUGMENT, BACKBONE,
                                                                                                                                               BACKBONE_CONV)]
+build_backbone_conv_bf16 = functools.partial(build_library, BACKBONE_CONV_BF16)
 train_up_to_date = functools.partial(up_to_date, TRAIN)
 
 
@@ -262,7 +273,7 @@ if __name__ == "__main__":
         print(build_variant(tag, packed, [a for a in argv if a.startswith("-D")], verbose=True))
     else:
         only = [lib for lib, switch in ((TRAIN, "--train"), (EVAL, "--eval"), (IMAGE, "--image"), (AUGMENT, "--augment"), (BACKBONE, "--backbone"),
-                                         (BACKBONE_CONV, "--backbone-conv")) if switch in argv]
+                                         (BACKBONE_CONV, "--backbone-conv"), (BACKBONE_CONV_BF16, "--backbone-conv-bf16")) if switch in argv]
         if only:
             print(build_library(only[0], force="--force" in argv))
         else:

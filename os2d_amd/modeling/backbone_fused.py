@@ -21,17 +21,25 @@ downsample branch of every bottleneck, half of the backbone's arithmetic - run a
 GEMMs of ours, MIOpen's 3x3 convolution and one bn + relu kernel.  The weights go in as ``conv.weight`` lies in memory: no copy, no
 cache.  The stem and the fold cache are those of "fused".
 
+``conv1x1_precision = "bf16x3"`` is a second arithmetic for those GEMMs, read on that route alone: every fp32
+operand split exactly into three bf16 values, six products on the bf16 matrix instruction, fp32 accumulation
+(libos2d_backbone_conv_bf16.so, include/os2d_backbone_conv_bf16.h).  The weights of a frozen backbone are split ONCE, into one device
+buffer of the runner beside the folds; it is rebuilt when a weight was written to or replaced.  Activations are split inside the
+kernel: no bf16 copy of one exists in memory.  "f32" is the default and stays bit for bit what it is.
+
 There is no fallback in here: a missing library raises ``Os2dLibraryError``.  WHICH calls take this route is part of its
 definition (``eligible``): inference calls on a contiguous fp32 device tensor with every BatchNorm in eval mode."""
 import torch
 import torch.nn as nn
 
-from .. import _backbone_conv_lib, _backbone_lib
+from .. import _backbone_conv_bf16_lib, _backbone_conv_lib, _backbone_lib
 from .._native import STREAM
 
 ROUTES = ("torch", "fused", "fused_conv1x1")
 FOLDING_ROUTES = ("fused", "fused_conv1x1")          # the routes that fold BatchNorms: they need an extractor without GroupNorm
 ROUTE_ENV = "OS2D_BACKBONE_ROUTE"
+PRECISIONS = ("f32", "bf16x3")                       # the arithmetic of the 1x1 GEMMs of "fused_conv1x1"
+PRECISION_ENV = "OS2D_BACKBONE_CONV_PRECISION"
 
 
 def fold_batchnorm(weight, bias, running_mean, running_var, eps):
@@ -99,6 +107,10 @@ class FusedBackbone(object):
         self._folds = None          # {id(norm layer): (s view, t view)}
         self._buffer = None         # [2, sum of channels] float32 on the device: all s, then all t
         self.rebuilds = 0
+        self._weight_key = None
+        self._packed = None         # {id(conv): its view of the buffer}
+        self._weight_buffer = None  # int16 on the device: the split weights of every 1x1 convolution, one layer after the other
+        self.weight_packs = 0
 
     def _cache_key(self, device):
         key = [device]
@@ -129,6 +141,29 @@ class FusedBackbone(object):
         self.rebuilds += 1
         return self._folds
 
+    def packed_weights(self, device):
+        """{id(conv): wp} of the 1x1 convolutions for the bf16x3 precision, as views of the one device buffer: split again when a weight
+        was written to (``_version``) or replaced (``data_ptr``), or when the device changes."""
+        convs = pointwise_convs(self.extractor)
+        key = (device,) + tuple(v for c in convs for v in (id(c), c.weight._version, c.weight.data_ptr()))
+        if key == self._weight_key:
+            return self._packed
+        sizes = [_backbone_conv_bf16_lib.packed_elems(c.out_channels, c.in_channels) for c in convs]      # each a multiple of 8: 16-byte units
+        self._weight_buffer = torch.empty(sum(sizes), dtype=torch.int16, device=device)
+        self._packed, at = {}, 0
+        for c, n in zip(convs, sizes):
+            if not plain_conv1x1(c):
+                raise ValueError("the fused_conv1x1 route runs plain 1x1 convolutions, not {}".format(c))
+            self._packed[id(c)] = self._weight_buffer[at:at + n]
+            _backbone_conv_bf16_lib.call("os2d_backbone_conv_bf16_pack_weights", c.weight.detach(), self._packed[id(c)], c.out_channels,
+                                         c.in_channels, STREAM)
+            at += n
+        if device.type == "cuda":
+            torch.cuda.current_stream(device).synchronize()       # the buffer serves calls on every stream from here on
+        self._weight_key = key
+        self.weight_packs += 1
+        return self._packed
+
     @staticmethod
     def _bn_relu(x, fold):
         n, c, h, w = x.shape
@@ -152,8 +187,9 @@ class FusedBackbone(object):
         return y
 
     @staticmethod
-    def _conv1x1(x, conv, fold, relu, r=None):
-        """relu?(fold(conv(x)) [+ r]) as ONE kernel; x and r contiguous, the output is new memory."""
+    def _conv1x1(x, conv, fold, relu, r=None, wp=None):
+        """relu?(fold(conv(x)) [+ r]) as ONE kernel; x and r contiguous, the output is new memory.  wp: the packed weights of conv for
+        the bf16x3 arithmetic (``packed_weights``); without them the GEMM is the fp32 one."""
         if not plain_conv1x1(conv):
             raise ValueError("the fused_conv1x1 route runs plain 1x1 convolutions (no bias, groups 1, dilation 1, padding 0, stride 1 or 2, "
                              "contiguous fp32 weight), not {}".format(conv))
@@ -162,22 +198,29 @@ class FusedBackbone(object):
         y = torch.empty((n, cout, (h - 1) // stride + 1, (w - 1) // stride + 1), dtype=x.dtype, device=x.device)
         if r is not None and r.shape != y.shape:
             raise ValueError("residual of shape {} for a block output of shape {}".format(tuple(r.shape), tuple(y.shape)))
+        if wp is not None:
+            _backbone_conv_bf16_lib.call("os2d_backbone_conv1x1_bf16x3", x, wp, fold[0], fold[1], r, None, None, y, n, cin, cout, h, w,
+                                         stride, int(relu), STREAM)
+            return y
         _backbone_conv_lib.call("os2d_backbone_conv1x1", x, conv.weight.detach(), fold[0], fold[1], r, None, None, y, n, cin, cout, h, w,
                                 stride, int(relu), STREAM)
         return y
 
     def forward_conv1x1(self, x):
-        """The route "fused_conv1x1": as ``forward``, with every 1x1 convolution and what follows it as one GEMM of ours."""
+        """The route "fused_conv1x1": as ``forward``, with every 1x1 convolution and what follows it as one GEMM of ours, in the
+        arithmetic ``extractor.conv1x1_precision`` names."""
         ex = self.extractor
         folds = self.folds(x.device)
+        packed = self.packed_weights(x.device) if ex.conv1x1_precision == "bf16x3" else None
+        wp = (lambda conv: packed[id(conv)]) if packed is not None else (lambda conv: None)
         x = self._bn_relu_maxpool(ex.conv1(x).contiguous(), folds[id(ex.bn1)])
         for stage in ex.resnet_blocks:
             for block in stage:
-                out = self._conv1x1(x, block.conv1, folds[id(block.bn1)], True)
+                out = self._conv1x1(x, block.conv1, folds[id(block.bn1)], True, wp=wp(block.conv1))
                 out = self._bn_relu(block.conv2(out).contiguous(), folds[id(block.bn2)])
                 if block.downsample is not None:
-                    x = self._conv1x1(x, block.downsample[0], folds[id(block.downsample[1])], False)
-                x = self._conv1x1(out, block.conv3, folds[id(block.bn3)], True, r=x)
+                    x = self._conv1x1(x, block.downsample[0], folds[id(block.downsample[1])], False, wp=wp(block.downsample[0]))
+                x = self._conv1x1(out, block.conv3, folds[id(block.bn3)], True, r=x, wp=wp(block.conv3))
         return x
 
     def forward(self, x):

@@ -3,7 +3,8 @@ the default (``inference_route = "torch"``) and the only path of every training 
 inference call with frozen BatchNorms keeps MIOpen for the convolutions and runs everything between them - the folded BatchNorms,
 ReLUs, residual adds and the stem's pooling - as HIP kernels of libos2d_backbone.so (backbone_fused.py).
 With ``inference_route = "fused_conv1x1"`` the 1x1 convolutions of such a call run as fp32 MFMA GEMMs of libos2d_backbone_conv.so as
-well, with the fold, the residual add and the ReLU as their epilogue.
+well, with the fold, the residual add and the ReLU as their epilogue; ``conv1x1_precision = "bf16x3"`` runs
+those GEMMs in split-bf16 arithmetic on the bf16 matrix instruction (libos2d_backbone_conv_bf16.so).
 
 Mirrors reference os2d/modeling/feature_extractor.py:13-129 (``build_feature_extractor``, ``ResNetFeatureExtractor``,
 ``resnet50_c4`` / ``resnet101_c4``).  torchvision is not available in this image, so the ResNet (v1.5 bottleneck:
@@ -57,7 +58,10 @@ class ResNetFeatureExtractor(nn.Module):
     ``inference_route``: "torch" (the default; the environment variable OS2D_BACKBONE_ROUTE sets the initial value), "fused" or
     "fused_conv1x1".  The last two need BatchNorm layers (ValueError with GroupNorm), "fused_conv1x1" plain 1x1 convolutions as well
     (``backbone_fused.plain_conv1x1``); they are taken by the calls ``backbone_fused.eligible`` describes: grad mode off, a contiguous
-    fp32 HIP tensor, every BatchNorm in eval mode.  Every other call runs the modules below as they are."""
+    fp32 HIP tensor, every BatchNorm in eval mode.  Every other call runs the modules below as they are.
+
+    ``conv1x1_precision``: "f32" (the default; OS2D_BACKBONE_CONV_PRECISION sets the initial value) or "bf16x3", the arithmetic of the
+    1x1 GEMMs.  It is read on the route "fused_conv1x1" alone."""
 
     def __init__(self, layers, level, feature_map_stride, feature_map_receptive_field, use_group_norm=False):
         super(ResNetFeatureExtractor, self).__init__()
@@ -80,6 +84,8 @@ class ResNetFeatureExtractor(nn.Module):
         self._block_names = names
         self._inference_route, self._fused = "torch", None      # plain attributes: no parameter, buffer or submodule
         self.inference_route = os.environ.get(backbone_fused.ROUTE_ENV, "torch")
+        self._conv1x1_precision = "f32"
+        self.conv1x1_precision = os.environ.get(backbone_fused.PRECISION_ENV, "f32")
         for m in self.modules():   # torchvision's default initialisation
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
@@ -118,6 +124,16 @@ class ResNetFeatureExtractor(nn.Module):
             raise ValueError("inference_route 'fused_conv1x1' runs plain 1x1 convolutions (no bias, groups 1, dilation 1, padding 0, "
                              "stride 1 or 2, contiguous fp32 weight): this extractor has others")
         self._inference_route = route
+
+    @property
+    def conv1x1_precision(self):
+        return self._conv1x1_precision
+
+    @conv1x1_precision.setter
+    def conv1x1_precision(self, precision):
+        if precision not in backbone_fused.PRECISIONS:
+            raise ValueError("conv1x1_precision is one of {}, not {!r}".format(backbone_fused.PRECISIONS, precision))
+        self._conv1x1_precision = precision
 
     def fused_backbone(self):
         """The runner of the fused route with its fold cache (made on first use)."""

@@ -1,11 +1,13 @@
 """Device-event timing of the backbone's three inference routes (DESIGN.md sections 18 and 18.6), alternated in ONE process:
 
     python tools/time_backbone.py                         # every configuration, torch / fused / torch again (the spread)
-    python tools/time_backbone.py --route all             # torch / fused / fused_conv1x1 / fused again (the spread of "fused")
+    python tools/time_backbone.py --route all             # torch / fused / fused_conv1x1 / fused again (the spread of "fused") / fused_conv1x1 in bf16x3
+    python tools/time_backbone.py --route fused_conv1x1 --precision both      # the two arithmetics of the 1x1 GEMMs
     python tools/time_backbone.py --only r50_960x1280     # one of them
     python tools/time_backbone.py --route fused --only r50_960x1280 --rounds 3      # one route (for a kernel trace)
     python tools/time_backbone.py --stem                  # the two stem variants alone at 960 x 1280
     python tools/time_backbone.py --layers                # os2d_backbone_conv1x1 alone at every 1x1 layer of ResNet50 at 960 x 1280
+    python tools/time_backbone.py --layers --precision bf16x3                 # os2d_backbone_conv1x1_bf16x3 at the same layers (or: both)
 
 One JSON line per configuration on stdout (and appended to --out): the median and the minimum over --rounds rounds of the mean
 time of --iters calls.  Random weights and perturbed BatchNorms: the time does not depend on the values."""
@@ -64,9 +66,9 @@ def make_extractor(arch, device):
     return ex.to(device).eval()
 
 
-def run_route(ex, route, x):
+def run_route(ex, route, x, precision="f32"):
     def fn():
-        ex.inference_route = route
+        ex.inference_route, ex.conv1x1_precision = route, precision
         with torch.no_grad():
             return ex(x)
     return fn
@@ -84,6 +86,7 @@ def emit(record, out):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--route", choices=["both", "all", "torch", "fused", "fused_conv1x1"], default="both")
+    ap.add_argument("--precision", choices=["f32", "bf16x3", "both"], default="f32", help="the arithmetic of the 1x1 GEMMs of the fused_conv1x1 arm")
     ap.add_argument("--only", action="append", help="configuration name (repeatable); default: all")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=5)
@@ -107,7 +110,10 @@ def main():
             arms = [("torch", run_route(ex, "torch", x)), ("fused", run_route(ex, "fused", x)), ("torch_again", run_route(ex, "torch", x))]
         elif args.route == "all":
             arms = [("torch", run_route(ex, "torch", x)), ("fused", run_route(ex, "fused", x)), ("fused_conv1x1", run_route(ex, "fused_conv1x1", x)),
-                    ("fused_again", run_route(ex, "fused", x))]
+                    ("fused_again", run_route(ex, "fused", x)), ("fused_conv1x1_bf16x3", run_route(ex, "fused_conv1x1", x, "bf16x3"))]
+        elif args.route == "fused_conv1x1":
+            arms = [("fused_conv1x1" + ("" if q == "f32" else "_" + q), run_route(ex, "fused_conv1x1", x, q))
+                    for q in (("f32", "bf16x3") if args.precision == "both" else (args.precision,))]
         else:
             arms = [(args.route, run_route(ex, args.route, x))]
         result = alternate(arms, args.rounds, args.iters)
@@ -121,6 +127,7 @@ def main():
             record["fused_spread"] = round(abs(result["fused"]["median_ms"] - result["fused_again"]["median_ms"]) / f, 4)
             record["fused_over_torch"] = round(f / result["torch"]["median_ms"], 4)
             record["fused_conv1x1_over_fused"] = round(result["fused_conv1x1"]["median_ms"] / f, 4)
+            record["fused_conv1x1_bf16x3_over_fused"] = round(result["fused_conv1x1_bf16x3"]["median_ms"] / f, 4)
         emit(record, args.out)
         del ex, x
         torch.cuda.empty_cache()
@@ -143,10 +150,12 @@ def stem(device, args):
 def layers(device, args):
     """os2d_backbone_conv1x1 with the epilogue of its place in the block, at the input each 1x1 convolution of ResNet50-C4 sees for a
     1 x 3 x 960 x 1280 image (240 x 320 after the stem, halved by layer2 and layer3): median time of a call, the TFLOP/s that time
-    implies (2 Cin Cout pixels) and the bytes/s (x, y, the residual and w, each once)."""
+    implies (2 Cin Cout pixels) and the bytes/s (x, y, the residual and w, each once).  --precision bf16x3 times os2d_backbone_conv1x1_bf16x3
+    on the packed weights instead, both the two alternately."""
     from os2d_amd.modeling.backbone_fused import FusedBackbone
     ex = make_extractor("resnet50", device)
     folds = ex.fused_backbone().folds(device)
+    packed = ex.fused_backbone().packed_weights(device) if args.precision != "f32" else None
     h, w, seen = 240, 320, set()
     with torch.no_grad():
         for stage in ex.resnet_blocks:
@@ -163,14 +172,20 @@ def layers(device, args):
                     x = torch.randn(1, conv.in_channels, hi, wi, device=device)
                     so, wo_ = (hi - 1) // conv.stride[0] + 1, (wi - 1) // conv.stride[0] + 1
                     r = torch.randn(1, conv.out_channels, so, wo_, device=device) if residual else None
-                    fn = lambda: FusedBackbone._conv1x1(x, conv, folds[id(bn)], relu, r)
-                    ms = alternate([("conv1x1", fn)], args.rounds, 20)["conv1x1"]
+                    arms = []
+                    if args.precision != "bf16x3":
+                        arms.append(("conv1x1", lambda: FusedBackbone._conv1x1(x, conv, folds[id(bn)], relu, r)))
+                    if args.precision != "f32":
+                        arms.append(("conv1x1_bf16x3", lambda: FusedBackbone._conv1x1(x, conv, folds[id(bn)], relu, r, wp=packed[id(conv)])))
+                    times = alternate(arms, args.rounds, 20)
                     pixels = so * wo_
                     flop = 2.0 * conv.in_channels * conv.out_channels * pixels
                     moved = 4.0 * (x.numel() if conv.stride[0] == 1 else conv.in_channels * pixels) + 4.0 * conv.out_channels * pixels * (2 if residual else 1) \
                         + 4.0 * conv.weight.numel()
-                    emit({"config": "layer", "role": role, "Cin": conv.in_channels, "Cout": conv.out_channels, "stride": conv.stride[0], "H": hi, "W": wi,
-                          "ms": ms, "tflops": round(flop / ms["median_ms"] / 1e9, 1), "tbytes_per_s": round(moved / ms["median_ms"] / 1e9, 2)}, args.out)
+                    for name, ms in times.items():
+                        emit({"config": "layer", "entry": name, "role": role, "Cin": conv.in_channels, "Cout": conv.out_channels, "stride": conv.stride[0],
+                              "H": hi, "W": wi, "ms": ms, "tflops": round(flop / ms["median_ms"] / 1e9, 1),
+                              "tbytes_per_s": round(moved / ms["median_ms"] / 1e9, 2)}, args.out)
                 h, w = ho, wo
 
 
