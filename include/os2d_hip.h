@@ -135,7 +135,20 @@ int os2d_class_split(const float* qp, void* qs, int B, int C, void* stream);
  *                 torch.relu / norm propagate a NaN (head.py:339, 650) - no host synchronisation, later calls unaffected.  The
  *                 words are never cleared (a stale epoch matches no later call); zero-fill the first (A + 1) * 4 bytes - the range
  *                 words - of a NEW workspace once so that its initial content cannot match either.  A caller that wants the reference's exact NaN
- *                 pattern re-runs a flagged call in OS2D_PRECISION_F32, whose kernels keep NaN through their ReLUs;
+ *                 pattern re-runs a flagged call in OS2D_PRECISION_F32, whose kernels keep NaN through their ReLUs.
+ *                 What is flagged, exactly (tests/test_range_flag_stages_gpu.py):
+ *                   - an image is flagged when the float32 SUM OF SQUARES of the features of one of its locations is not finite:
+ *                     a NaN or an Inf feature, and also finite features whose squares overflow (2e19 in 32 channels), where the
+ *                     reference's norm stays finite: that image is all-NaN here;
+ *                   - a NaN or an Inf in a CLASS operand (qp / qs) makes the correlation norms of that class NaN on every image;
+ *                     the layers behind raise the word of the whole call: at least that class is all-NaN, on every image (the
+ *                     reference gives NaN loc and corners for that class only);
+ *                   - the word of the whole call is raised by the chunk of classes that meets the activation: with a workspace
+ *                     that takes the classes in chunks, the outputs of that chunk and of every LATER chunk are NaN, those of the
+ *                     chunks decoded before it are what a clean call gives (the status word is raised all the same);
+ *                   - the epoch is drawn on the host when the call is made: replaying a captured graph (hipGraph) replays the
+ *                     captured epoch, so a word raised by one replay flags every later one - replaying a captured
+ *                     split-fp16 head call is not supported;
  *   wspec, twQ, twP  the frequency-domain precisions only (NULL otherwise; w1 / b1..b3 / w2 / w3 as for F16X3, FFT32: as for F32):
  *                 OS2D_PRECISION_FFT / _FFT32: the weight spectra of the 7x7 layer for THIS map's transform size in the layout of
  *                 os2d_spectral_gemm and the two twiddle tables of os2d_fft_forward;

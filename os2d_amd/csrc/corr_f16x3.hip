@@ -252,10 +252,14 @@ __device__ __forceinline__ void corr_tile(const u32x4* fs,  // [A][CGP][2][HW]  
         for (int k = 0; k < 4; ++k) {
           const float v = acc[mi][ni][4 * q + k] * unscale;
           acc[mi][ni][4 * q + k] = v;
-          const float rl = fmaxf(v, 0.f);
+          // torch.relu, not fmaxf: a NaN accumulator - a NaN or an Inf in the CLASS operand (the image's are dropped by
+          // split_fm_kernel, which flags the image) - must reach g.  fmaxf(NaN, 0) = 0 left the row out of the norm, unflagged,
+          // and the 7x7 layer saw a zero channel where the reference's outputs are NaN.
+          const float rl = os2d_relu(v);
           g = fmaf(rl, rl, g);
         }
-        // g <= 4 (cosines); anything else is a non-finite input: flagged, the norm then becomes NaN like the reference's
+        // g <= 4 (cosines); anything else (NaN included) is a non-finite input: flagged, the norm then becomes NaN like the
+        // reference's, and the layers behind raise the call's range word
         const bool gbad = !(g < 1024.f);
         const float ga = fminf(g, 1024.f) * 1048576.f;                   // 2^20
         const unsigned gh = (unsigned)ga;
@@ -476,12 +480,17 @@ __global__ __launch_bounds__(256) void split_fm_kernel(const float* __restrict__
   // kernel of the call (sample_decode_kernel) then writes NaN into every output of that image (round 6).
   if (status.word != nullptr && g == 0 && __builtin_amdgcn_ballot_w64(!(ss <= 3.4028234e38f)) != 0ull && (threadIdx.x & 63) == 0)
     os2d_raise(Os2dRangeFlag{status.word + a, status.value});
+  // ... and the location's operand is then written as ZEROS: every output of the flagged image becomes NaN whatever is computed
+  // for it, and a NaN left in the operand would reach the correlation's norm, the 7x7 layer and through its range test the word of
+  // the WHOLE call - the other images of the batch must stay what they are.  (Without a word - the per-stage entry points - the
+  // values go through as they are.)
+  const bool drop = status.word != nullptr && !(ss <= 3.4028234e38f);
   const float inv = scale / (sqrtf(ss) + 1e-5f);
   half8 hi, lo;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int c = g * 8 + j;
-    const float v = c < C ? fm[((size_t)a * C + c) * HW + n] * inv : 0.f;
+    const float v = (c < C && !drop) ? fm[((size_t)a * C + c) * HW + n] * inv : 0.f;
     const _Float16 hv = (_Float16)v;
     hi[j] = hv;
     lo[j] = (_Float16)(v - (float)hv);

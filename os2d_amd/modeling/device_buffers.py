@@ -21,12 +21,26 @@ def workspace_total_cap_bytes():
     return int(float(os.environ.get("OS2D_WORKSPACE_TOTAL_GB", "96")) * (1 << 30))
 
 
-def get_workspace(device, wanted, minimum):
+RANGE_WORDS_ZEROED = 1024      # words (4096 bytes) zero-filled at the start of every new workspace, whatever the call
+
+
+def range_words_bytes(images):
+    """Bytes to zero-fill at the start of a NEW workspace for a head call on ``images`` feature maps: its (A + 1) range words
+    (include/os2d_hip.h, ``status``), never less than the fixed ``RANGE_WORDS_ZEROED`` words."""
+    return 4 * max(int(images) + 1, RANGE_WORDS_ZEROED)
+
+
+def get_workspace(device, wanted, minimum, images=0):
     """Grow-only scratch buffer, one per (device, stream): concurrent heads on different HIP streams (the pyramid
     runner) must not share intermediates.  The pyramid runner draws its streams from a fixed pool
     (os2d_amd/engine/pyramid.py), so the number of buffers is bounded by the number of level slots; their total is kept
     below ``workspace_total_cap_bytes`` by shrinking what a NEW or growing buffer may take (never below ``minimum``, the
-    footprint of one class)."""
+    footprint of one class).  ``images``: A of the head call the buffer is for.  A new buffer is zero-filled over that call's
+    A + 1 range words (a fixed 4096 bytes covered A <= 1023 only), and a buffer that is REUSED by a call with
+    more words than it was ever filled for gets the missing words zeroed (on the stream of the key, ahead of the call): the
+    words of a call have then been zero at least once.  What this does not do: between calls the words inside the filled extent
+    may hold an earlier call's epochs or - where a call with fewer images carved its intermediates there - its data; such a
+    stale word matches a later call's epoch with probability 2^-32 (the epochs start at a random base, head_call.hip)."""
     index = device.index if device.index is not None else torch.cuda.current_device()
     key = (device.type, index, torch.cuda.current_stream(device).cuda_stream)
     buf = _WORKSPACES.get(key)
@@ -36,8 +50,14 @@ def get_workspace(device, wanted, minimum):
     if buf is None or buf.numel() < size:
         _WORKSPACES[key] = None
         buf = torch.empty(size, dtype=torch.uint8, device=device)
-        buf[:4096].zero_()       # the range words of a head call live at the start of its workspace (include/os2d_hip.h)
+        buf.range_bytes_zeroed = min(range_words_bytes(images), size)
+        buf[:buf.range_bytes_zeroed].zero_()       # the range words of a head call live at the start of its workspace (include/os2d_hip.h)
         _WORKSPACES[key] = buf
+    else:
+        need, have = min(range_words_bytes(images), buf.numel()), getattr(buf, "range_bytes_zeroed", 0)
+        if need > have:
+            buf[have:need].zero_()
+            buf.range_bytes_zeroed = need
     return buf
 
 

@@ -828,7 +828,7 @@ class Os2dHead(nn.Module):
         _lib.call("os2d_head_workspace_bytes_ex", A, B, C, H, W, P, PRECISIONS[precision], ctypes.byref(full))
         _lib.call("os2d_head_workspace_bytes_ex", A, 1, C, H, W, P, PRECISIONS[precision], ctypes.byref(one))
         with torch.cuda.device(dev):     # hipFuncSetAttribute / launches act on the CURRENT device
-            ws = get_workspace(dev, min(full.value, workspace_cap_bytes()), one.value)      # (a cap replaced on THIS module is obeyed)
+            ws = get_workspace(dev, min(full.value, workspace_cap_bytes()), one.value, A)   # (a cap replaced on THIS module is obeyed)
             status = self._status_word() if precision not in FP32_MODES else None
             _lib.call("os2d_head_forward_ex2", feature_maps, self._qp, w1, b1, w2, b2, w3, b3, A, B, C, H, W, P,
                       1 if self.aligner.use_inverse_geom_model else 0, self._stride, self._rec_field, loc, cls, corners, ws, ws.numel(),

@@ -236,8 +236,122 @@ static int check_case(int H, int W, int C, int NB, int grid) {
   return 0;
 }
 
+// ---------------- the range flag of the inverse transform (usage: dft_mfma_check range H W NB ...)
+// Every (pair, channel) holds the spectrum of a scaled delta image, Y[u][v] = A exp(-2 pi i (u hwin / P + v wwin / Q)): the
+// inverse transform gives A at window cell (hwin, wwin) and 0 elsewhere, and with bias 0 and scale 1 the stored value IS A.
+// LOW = 65504 (1 - 2^-10) everywhere is the clean twin; the cases then change ONE spectrum of the LAST pair (its last tile):
+//   over      A = 65504 (1 + 2^-10) at the map's last cell                                       -> flag
+//   nan       one bin of that spectrum is NaN and the channel's bias is -1: every pre-activation
+//             of the channel is NaN and fmaxf(NaN, 0) = 0 stores a clean 0                       -> flag
+//   overhang  A = 65504 (1 + 2^-10) at a window cell the kernel does not store (below the map /
+//             in the halo of a tiled transform: inside == false)                                 -> no flag
+// 2^-10 is ~650 times the 1.5e-6 this file holds the inverse transform to.
+static int check_range_flag(int H, int W, int NB, int grid) {
+  DftPlan pl;
+  if (!dft_make_plan(H, W, &pl)) {
+    std::printf("no plan for %dx%d\n", H, W);
+    return 1;
+  }
+  const int P = pl.P, Q = pl.Q, V = pl.V, T = pl.T, NBT = NB * T;
+  const std::vector<double> tp = table(P), tq = table(Q);
+  std::vector<u32x4> mats(dft_matrices_units(P, Q));
+  const int nf = dft_units_fqt(P, Q), n2 = dft_units_fp2(P, Q), ne = dft_units_e2(P, Q), ng = dft_units_gq(P, Q);
+  for (int i = 0; i < nf; ++i) dft_matrix_unit(0, i, P, Q, tp.data(), tq.data(), &mats[i]);
+  for (int i = 0; i < n2; ++i) dft_matrix_unit(1, i, P, Q, tp.data(), tq.data(), &mats[nf + i]);
+  for (int i = 0; i < ne; ++i) dft_matrix_unit(2, i, P, Q, tp.data(), tq.data(), &mats[nf + n2 + i]);
+  for (int i = 0; i < ng; ++i) dft_matrix_unit(3, i, P, Q, tp.data(), tq.data(), &mats[nf + n2 + ne + i]);
+  const u32x4 *E2 = mats.data() + nf + n2, *Gq = E2 + ne;
+  DftPlan pl8;
+  const bool have8 = dft_plan_g8(pl, &pl8);
+  const int Cout = 16, MTP = 128, PLANE = plane_of(H, W), Ws = ws_of(W), BASE = base_of(W);
+  const double LOW = 65504.0 * (1.0 - 1.0 / 1024.0), HIGH = 65504.0 * (1.0 + 1.0 / 1024.0);
+  // window cell of map cell (h, w) in the last tile, and a window cell of that tile which is not stored
+  const int ty = pl.TY - 1, tx = pl.TX - 1, y0 = T > 1 ? ty * pl.TH : 0, x0 = T > 1 ? tx * pl.TW : 0;
+  const int oy = T > 1 ? pl.oy : 0, ox = T > 1 ? pl.ox : 0;
+  const int last_h = H - 1 - y0 + oy, last_w = W - 1 - x0 + ox;
+  const int out_h = T > 1 ? 0 : H, out_w = T > 1 ? 0 : W - 1;        // tiled: the halo corner; untiled: the row below the map
+  if (!(T > 1 ? (oy > 0 || ox > 0) : H < P)) {
+    std::printf("no unstored window cell for %dx%d\n", H, W);
+    return 1;
+  }
+  const int bad_pair = NBT - 1, bad_o = Cout - 3;
+  struct Case { const char* name; double amp; int hwin, wwin; bool nan; int want; };
+  const Case cases[] = {{"clean", LOW, last_h, last_w, false, 0}, {"over", HIGH, last_h, last_w, false, 1},
+                        {"nan", LOW, last_h, last_w, true, 1}, {"overhang", HIGH, out_h, out_w, false, 0}};
+  for (const Case& cs : cases)
+    for (int G = 4; G <= 8; G += 4) {
+      if (G == 8 && !have8) continue;
+      std::vector<float> Y((size_t)(pl.NBINS / 4) * NBT * Cout * 8, 0.f);
+      for (int pair = 0; pair < NBT; ++pair)
+        for (int o = 0; o < Cout; ++o) {
+          const bool it = pair == bad_pair && o == bad_o;
+          const double A = it ? cs.amp : LOW;
+          // the others sit at the first cell of their tile (window cell (oy, ox): inside for every tile)
+          const int hwin = it ? cs.hwin : oy, wwin = it ? cs.wwin : ox;
+          for (int u = 0; u < P; ++u)
+            for (int v = 0; v < V; ++v) {
+              const int a = (int)(((long long)u * hwin) % P), b = (int)(((long long)v * wwin) % Q);
+              float* y = &Y[spec_index(v * P + u, pair, NBT, pl.NBINS / 4, Cout, o)];
+              y[0] = (float)(A * (tp[2 * a] * tq[2 * b] - tp[2 * a + 1] * tq[2 * b + 1]));
+              y[1] = (float)(A * (tp[2 * a] * tq[2 * b + 1] + tp[2 * a + 1] * tq[2 * b]));
+            }
+        }
+      std::vector<float> bp(3 * MTP, 0.f);
+      for (int o = 0; o < Cout; ++o) bp[2 * MTP + o] = 1.f;
+      if (cs.nan) {
+        Y[spec_index(1 * P + 2, bad_pair, NBT, pl.NBINS / 4, Cout, bad_o)] = std::nanf("");
+        bp[bad_o] = -1.f;
+      }
+      DftPlan ip = G == 8 ? pl8 : pl;
+      std::vector<unsigned char> out((size_t)NB * ((Cout + 7) / 8) * 2 * PLANE * 16, 0x5A);
+      int flag = 0;
+      const int OG = Cout / G, iters_i = NBT * OG;
+      ip.inv_og = dft_magic((unsigned)OG);
+      emu::launch(grid, DFT_THR, ip.lds_total, [&] {
+#define INV(KS)                                                                                                                     \
+  if (ip.T > 1) dft_inverse_body<true, KS>(Y.data(), bp.data(), MTP, out.data(), E2, Gq, ip, Cout, NBT, PLANE, Ws, BASE, iters_i, &flag, 1); \
+  else dft_inverse_body<false, KS>(Y.data(), bp.data(), MTP, out.data(), E2, Gq, ip, Cout, NBT, PLANE, Ws, BASE, iters_i, &flag, 1);
+        if (G == 8) {
+          if (ip.T > 1) dft_inverse_body<true, 0, 8>(Y.data(), bp.data(), MTP, out.data(), E2, Gq, ip, Cout, NBT, PLANE, Ws, BASE, iters_i, &flag, 1);
+          else dft_inverse_body<false, 0, 8>(Y.data(), bp.data(), MTP, out.data(), E2, Gq, ip, Cout, NBT, PLANE, Ws, BASE, iters_i, &flag, 1);
+        } else
+          switch (dft_ksteps_param(ip)) {
+            case 5: INV(5) break;
+            case 6: INV(6) break;
+            case 7: INV(7) break;
+            case 8: INV(8) break;
+            default: INV(0) break;
+          }
+#undef INV
+      });
+      // the value the case is about, as stored (the map's last cell of the changed channel), and the largest other value
+      const int nb = NB - 1;
+      const size_t cell = (size_t)BASE + (size_t)(H - 1) * Ws + (W - 1);
+      const unsigned char* hi = &out[(((size_t)nb * ((Cout + 7) / 8) + (bad_o >> 3)) * 2 + 0) * (size_t)PLANE * 16];
+      const unsigned char* lo = &out[(((size_t)nb * ((Cout + 7) / 8) + (bad_o >> 3)) * 2 + 1) * (size_t)PLANE * 16];
+      const float hv = (float)*reinterpret_cast<const _Float16*>(hi + cell * 16 + (bad_o & 7) * 2);
+      const float lv = (float)*reinterpret_cast<const _Float16*>(lo + cell * 16 + (bad_o & 7) * 2);
+      std::printf("  range %dx%d %-8s (G = %d): flag %d (want %d), stored hi %g lo %g\n", H, W, cs.name, G, flag, cs.want, hv, lv);
+      if (flag != cs.want) {
+        std::printf("RANGE FLAG MISMATCH\n");
+        return 1;
+      }
+      // the clean twin and the overhang case store finite values only; the stored cell of the clean twin is LOW to 1.5e-6
+      if (cs.want == 0 && cs.hwin == last_h && !(std::fabs((double)hv + (double)lv - LOW) <= 1.5e-6 * LOW)) {
+        std::printf("RANGE TWIN VALUE MISMATCH\n");
+        return 1;
+      }
+    }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   int rc = 0;
+  if (argc >= 2 && argv[1][0] == 'r') {      // "range" as the first argument: the range flag cases, H W NB per map
+    for (int i = 2; i + 2 < argc; i += 3) rc |= check_range_flag(std::atoi(argv[i]), std::atoi(argv[i + 1]), std::atoi(argv[i + 2]), 2);
+    std::printf(rc ? "FAILED\n" : "ok\n");
+    return rc;
+  }
   if (argc >= 2 && argv[1][0] == 'c') {      // "canonical" as the first argument: plan on the six canonical transform sizes
     emu_dft_policy = 1;
     --argc;

@@ -11,7 +11,7 @@ import pytest
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
-def test_dft_mfma_kernels_on_the_host_emulator(tmp_path):
+def _build(tmp_path):
     cxx = shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"      # ext_vector_type + _Float16: clang
     if not os.path.exists(cxx) and shutil.which(cxx) is None:
         pytest.skip("no clang++")
@@ -19,6 +19,24 @@ def test_dft_mfma_kernels_on_the_host_emulator(tmp_path):
     subprocess.run([cxx, "-std=c++17", "-O1", "-pthread", "-Wno-psabi", "-I", os.path.join(REPO, "os2d_amd", "csrc"),
                     "-I", os.path.join(REPO, "tests", "host"), os.path.join(REPO, "tests", "host", "dft_mfma_check.cpp"), "-o", exe],
                    check=True, timeout=300)
+    return exe
+
+
+def test_dft_inverse_range_flag_on_the_host_emulator(tmp_path):
+    """The range flag of the inverse transform's epilogue (dft_mfma.h), where the stage tests only ever saw it stay 0: per map a
+    clean twin with EVERY channel at 65504 (1 - 2^-10) (flag 0), one inside cell of the last pair's last tile at 65504 (1 + 2^-10)
+    (flag set), a NaN pre-activation under a negative bias, which the ReLU's fmaxf turns into a clean 0 (flag set), and the
+    over-range value in a window cell the kernel does not store (flag 0) - untiled and tiled, 4 and 8 images per iteration."""
+    exe = _build(tmp_path)
+    out = subprocess.run([exe, "range", "11", "13", "2", "70", "100", "1", "30", "40", "2"], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-3000:] + out.stderr[-2000:]
+    for name in ("clean", "over", "nan", "overhang"):
+        assert out.stdout.count(" {} ".format(name)) >= 3, out.stdout[-3000:]          # every map ran the case
+    assert "(G = 8)" in out.stdout and "(G = 4)" in out.stdout
+
+
+def test_dft_mfma_kernels_on_the_host_emulator(tmp_path):
+    exe = _build(tmp_path)
     # small untiled (W % 4 != 0, partial channel group), fast path with several work-groups, a tiled map with ragged tiles, a
     # level of the pyramid with P % 8 == 4
     out = subprocess.run([exe, "11", "13", "5", "1", "20", "24", "4", "2", "70", "100", "5", "1", "30", "43", "6", "2", "9", "11", "4", "66"],

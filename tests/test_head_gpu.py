@@ -120,38 +120,19 @@ _route_heads = {}
 def _route_head(shape, device):
     """(head, feature maps) of a shape, built once for all its precisions"""
     if shape not in _route_heads:
-        from os2d_amd.utils import synthetic
         A, B, H, W = ROUTE_SHAPES[shape]
-        creator = util.make_head_creator(6, True, synthetic.make_transform_net_state(6, seed=7), device)
-        class_fms = synthetic.make_class_feature_maps(B, 32, sizes=[(15, 15), (14, 16), (16, 14)], seed=500)
+        state, class_fms, fm = util.route_head_inputs(A, B, H, W)
+        creator = util.make_head_creator(6, True, state, device)
         with torch.no_grad():
             head = creator.create_os2d_head([c.to(device) for c in class_fms])
-        _route_heads[shape] = head, synthetic.make_feature_map(32, H, W, seed=5, A=A).to(device)
+        _route_heads[shape] = head, fm.to(device)
     return _route_heads[shape]
 
 
 def _forward_ex2(head, fm, precision, workspace_bytes):
     """os2d_head_forward_ex2 through ctypes on a zero-filled workspace of exactly that size: (chunk_classes, [loc, cls, corners])"""
-    import ctypes
-    from os2d_amd import _lib
-    from os2d_amd.modeling import head as head_mod
-    lib, ptr, dev = _lib.load(), _lib.ptr, fm.device
-    A, C, H, W = fm.shape
-    B = head.class_batch_size
-    net = head.aligner.parameter_regressor
-    spectra = net.spectra(H, W, split=precision == "fftx3")[:3] if precision in head_mod.FFT_MODES else (None, None, None)
-    spectra2 = net.spectra2(H, W) if precision == "fftx3" else None
-    packed = net.packed(precision)
-    qs = head._split_class_operand() if precision not in head_mod.FP32_MODES else None
-    out = [torch.full((A, B, k, H, W), float("nan"), device=dev) for k in (4, 1, 8)]      # a cell nobody writes stays NaN: never equal
-    ws = torch.zeros(workspace_bytes, dtype=torch.uint8, device=dev)
-    chunk = ctypes.c_int(0)
-    _lib.check(lib.os2d_head_forward_ex2(
-        ptr(fm), ptr(head._qp), *[ptr(t) for t in packed], A, B, C, H, W, 6, 1, head._stride, head._rec_field, *[ptr(t) for t in out],
-        ptr(ws), ws.numel(), _lib.current_stream(dev), head_mod.PRECISIONS[precision], ptr(qs), None, ctypes.byref(chunk), None,
-        *[ptr(t) for t in spectra], ptr(spectra2)), "os2d_head_forward_ex2")
-    torch.cuda.synchronize()
-    return chunk.value, out
+    ws = torch.zeros(workspace_bytes, dtype=torch.uint8, device=fm.device)
+    return util.head_forward_ex2(head, fm, precision, ws)          # (outputs NaN-prefilled: a cell nobody writes is never equal)
 
 
 @pytest.mark.parametrize("shape,precision", [("9x14", p) for p in PRECISIONS] + [("5x212", p) for p in ("fftx3", "fft", "fft32")])

@@ -133,6 +133,51 @@ def check_or_record_fixture_pin(name, precision, ratios):
         assert r <= limit, "{} [{}] {}: error {:.4g} of the generic tolerance, pinned at {:.4g} (measured {:.4g})".format(name, precision, what, r, limit, p)
 
 
+def route_head_inputs(A, B, H, W, C=32):
+    """The network, class maps and feature maps of the head-route tests (tests/test_head_gpu.py: ROUTE_SHAPES;
+    tests/test_range_flag_stages_gpu.py): (TransformNet state for P = 6, B class maps [C, h, w], feature maps [A, C, H, W]) on the
+    CPU, fresh tensors on every call (a caller may edit them)."""
+    state = synthetic.make_transform_net_state(6, seed=7)
+    class_fms = synthetic.make_class_feature_maps(B, C, sizes=[(15, 15), (14, 16), (16, 14)], seed=500)
+    return state, class_fms, synthetic.make_feature_map(C, H, W, seed=5, A=A)
+
+
+def head_workspace_bytes(A, classes, C, H, W, precision, P=6):
+    """os2d_head_workspace_bytes_ex: the workspace that takes ``classes`` classes per chunk."""
+    import ctypes
+    from os2d_amd import _lib
+    from os2d_amd.modeling import head as head_mod
+    n = ctypes.c_size_t()
+    _lib.check(_lib.load().os2d_head_workspace_bytes_ex(A, classes, C, H, W, P, head_mod.PRECISIONS[precision], ctypes.byref(n)), "workspace bytes")
+    return n.value
+
+
+def head_forward_ex2(head, fm, precision, ws, status=None, conv2_freq=True):
+    """os2d_head_forward_ex2 through ctypes on the CALLER's workspace ``ws`` (uint8 device tensor, used as it is: the range words
+    at its start are the caller's to zero-fill and to read) and the caller's status word (int32 device tensor or None):
+    (chunk_classes, [loc, cls, corners]), synchronised.  Outputs are NaN-prefilled.  conv2_freq: hand the fftx3 route the
+    spectra of the 5x5 layer (wspec2) as well."""
+    import ctypes
+    from os2d_amd import _lib
+    from os2d_amd.modeling import head as head_mod
+    lib, ptr, dev = _lib.load(), _lib.ptr, fm.device
+    A, C, H, W = fm.shape
+    B = head.class_batch_size
+    net = head.aligner.parameter_regressor
+    spectra = net.spectra(H, W, split=precision == "fftx3")[:3] if precision in head_mod.FFT_MODES else (None, None, None)
+    spectra2 = net.spectra2(H, W) if (precision == "fftx3" and conv2_freq) else None
+    packed = net.packed(precision)
+    qs = head._split_class_operand() if precision not in head_mod.FP32_MODES else None
+    out = [torch.full((A, B, k, H, W), float("nan"), device=dev) for k in (4, 1, 8)]
+    chunk = ctypes.c_int(0)
+    _lib.check(lib.os2d_head_forward_ex2(
+        ptr(fm), ptr(head._qp), *[ptr(t) for t in packed], A, B, C, H, W, 6, 1, head._stride, head._rec_field, *[ptr(t) for t in out],
+        ptr(ws), ws.numel(), _lib.current_stream(dev), head_mod.PRECISIONS[precision], ptr(qs), None, ctypes.byref(chunk), ptr(status),
+        *[ptr(t) for t in spectra], ptr(spectra2)), "os2d_head_forward_ex2")
+    torch.cuda.synchronize()
+    return chunk.value, out
+
+
 def adversarial_transform_net_state(P, seed, lo1=-3.0, hi1=6.0, lo2=-3.0, hi2=3.0):
     """A TransformNet that computes the SAME function as ``make_transform_net_state(P, seed)`` but whose intermediate
     ranges are hostile to a fixed-range number format:
