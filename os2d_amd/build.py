@@ -102,8 +102,9 @@ ALL_LIBRARIES = LIBRARIES + [AUGMENT]          # the libraries of the head, the 
 BUILT_LIBRARIES = ALL_LIBRARIES + [BACKBONE]   # the six that tests/test_backbone_model.py pins
 # The backbone's 1x1 convolutions as fp32 GEMMs on the fp32-input MFMA with the fold, residual and ReLU as the epilogue
 # (include/os2d_backbone_conv.h).  A library of its own: the exports and the ABI version of
-# libos2d_backbone.so are what they are.  Its unit includes csrc_backbone/backbone_common.h for the fold's arithmetic and the
-# argument checks; no packed FP32, as for every kernel that runs next to other streams.
+# libos2d_backbone.so are what they are.  Its unit includes csrc_backbone/conv1x1_common.h - the epilogue, the argument contract
+# and the tile plan of a 1x1 GEMM, on top of backbone_common.h's fold - and keeps the main loop; no packed FP32, as for every kernel
+# that runs next to other streams.
 BACKBONE_CONV_CSRC = os.path.join(HERE, "csrc_backbone_conv")
 BACKBONE_CONV = Library("libos2d_backbone_conv.so", BACKBONE_CONV_CSRC, ["conv1x1.hip"], FLAGS + PACKED_OFF, {},
                         [BACKBONE_CONV_CSRC, BACKBONE_CSRC, SHARED], "os2d_backbone_conv.h", "OS2D_BACKBONE_CONV_LIB")
@@ -111,7 +112,7 @@ EVERY_LIBRARY = BUILT_LIBRARIES + [BACKBONE_CONV]      # the seven that tests/te
 # The same 1x1 convolutions in split-bf16 arithmetic: three bf16 parts per fp32 operand, six products on the bf16 MFMA
 # (include/os2d_backbone_conv_bf16.h).  An eighth library: the exports, the ABI version and the signature of
 # libos2d_backbone_conv.so are what they are.  bf16x3_split.h of its directory is the split, for the device and for a host program; the
-# unit includes csrc_backbone/backbone_common.h as the fp32 unit does.  No packed FP32.
+# epilogue, the argument contract and the tile plan are csrc_backbone/conv1x1_common.h, the text the fp32 unit includes.  No packed FP32.
 BACKBONE_CONV_BF16_CSRC = os.path.join(HERE, "csrc_backbone_conv_bf16")
 BACKBONE_CONV_BF16 = Library("libos2d_backbone_conv_bf16.so", BACKBONE_CONV_BF16_CSRC, ["conv1x1_bf16x3.hip"], FLAGS + PACKED_OFF, {},
                              [BACKBONE_CONV_BF16_CSRC, BACKBONE_CSRC, SHARED], "os2d_backbone_conv_bf16.h", "OS2D_BACKBONE_CONV_BF16_LIB")

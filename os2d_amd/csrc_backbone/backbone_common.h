@@ -21,10 +21,15 @@ __device__ __forceinline__ float bb_max_nan(float m, float v) { return (v > m ||
 
 static inline bool bb_misaligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) != 0; }
 
+// do [a, a + na) and [b, b + nb) bytes meet?
+static inline bool bb_bytes_meet(const void* a, size_t na, const void* b, size_t nb) {
+  const size_t pa = reinterpret_cast<size_t>(a), pb = reinterpret_cast<size_t>(b);
+  return pa < pb + nb && pb < pa + na;
+}
+
 // do [a, a + n) and [b, b + n) floats share a byte?
 static inline bool bb_overlap(const float* a, const float* b, long long n) {
-  const size_t pa = reinterpret_cast<size_t>(a), pb = reinterpret_cast<size_t>(b), bytes = (size_t)n * sizeof(float);
-  return pa < pb + bytes && pb < pa + bytes;
+  return bb_bytes_meet(a, (size_t)n * sizeof(float), b, (size_t)n * sizeof(float));
 }
 
 // the work-groups of a launch over `tiles` tiles: every tile has one when there are few, else the kernel strides

@@ -186,8 +186,7 @@ int os2d_backbone_bn_relu_maxpool(const float* x, const float* s, const float* t
   p.planes = N * C; p.C = C; p.H = H; p.W = W;
   p.Hp = (H - 1) / 2 + 1;
   p.Wp = (W - 1) / 2 + 1;
-  const size_t px = reinterpret_cast<size_t>(x), py = reinterpret_cast<size_t>(y);
-  if (px < py + (size_t)p.planes * p.Hp * p.Wp * sizeof(float) && py < px + (size_t)p.planes * H * W * sizeof(float))
+  if (bb_bytes_meet(x, (size_t)p.planes * H * W * sizeof(float), y, (size_t)p.planes * p.Hp * p.Wp * sizeof(float)))
     return os2d_refuse("bn_relu_maxpool: y overlaps x");
   p.gx = (p.Wp + 3) / 4;
   p.chunks = (p.Hp * p.gx + BB_THREADS - 1) / BB_THREADS;

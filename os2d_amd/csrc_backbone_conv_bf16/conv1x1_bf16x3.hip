@@ -4,9 +4,9 @@
 //
 //   pack_kernel                    w [Cout][Cin] -> wp[part][Kp / 8][Cout][8]: once per weight, the A operand as the kernel reads it.
 //   conv1x1_bf16x3_kernel<WAVES_M, VEC>
-//                                  Y[Cout][pixels] = W . X with the tiling of csrc_backbone_conv/conv1x1.hip: pixels = N * Ho * Wo, a
-//                                  work-group of 4 waves owns TM = 64 * WAVES_M output channels x TN = 64 * (4 / WAVES_M) pixels (128 x 128,
-//                                  or 64 x 256 for layers of at most 64 outputs), a wave 64 x 64 of it as 2 x 2 accumulators of 32 x 32.
+//                                  Y[Cout][pixels] = W . X in the tiling of csrc_backbone/conv1x1_common.h: a work-group of 4 waves owns
+//                                  TM = 64 * WAVES_M output channels x TN = 64 * (4 / WAVES_M) pixels (128 x 128, or 64 x 256 for layers
+//                                  of at most 64 outputs).
 //                                  Per step of TILE_K = 32 input channels:
 //                                    - the step's slice of wp, 3 * 4 * TM units of 16 bytes, is copied to LDS as it is;
 //                                    - a thread loads 2 neighbouring pixels of 8 consecutive input channels of x (a wave: 512-byte runs
@@ -20,13 +20,12 @@
 //                                  VEC: the two pixels are one 8-byte load (stride 1, H * W even, x 8-byte aligned: a pair never leaves
 //                                  its image); otherwise element by element, which also serves the stride-2 gather.
 //                                  Everything outside the tensors - k >= Cin, m >= Cout, pixel >= pixels - is 0 in BOTH operands.
-// W stays the A operand: the accumulator layout (pixel = lane & 31, channel = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)) makes every
-// store of the epilogue 32 consecutive floats of one output row.  With the roles swapped a lane would hold 4 consecutive pixels of one
-// channel, a 16-byte store, but the 32 lanes of a store would hit 32 different rows: 16-byte pieces instead of 128-byte runs.
-// The order of the products of an output is fixed (the header), whatever tile shape or load path runs.  No atomics, no inline assembly;
-// the grid is capped at OS2D_BACKBONE_CONV_BF16_MAX_GROUPS work-groups that stride over the tiles, output-channel tiles of one pixel
-// tile next to each other.
-#include "../csrc_backbone/backbone_common.h"
+// W stays the A operand, for the accumulator layout of conv1x1_common.h, whose stores are 32 consecutive floats of one output row.  With
+// the roles swapped a lane would hold 4 consecutive pixels of one channel, a 16-byte store, but the 32 lanes of a store would hit 32
+// different rows: 16-byte pieces instead of 128-byte runs.
+// The order of the products of an output is fixed (the header), whatever tile shape or load path runs.  No atomics, no inline assembly.
+// The epilogue, the argument checks and the capped grid are those of conv1x1_common.h, shared with the fp32 library.
+#include "../csrc_backbone/conv1x1_common.h"
 #include "../../include/os2d_backbone_conv_bf16.h"
 #include "bf16x3_split.h"
 
@@ -36,76 +35,15 @@ constexpr int CB_THREADS = 256;
 constexpr int CB_TK = OS2D_BACKBONE_CONV_BF16_TILE_K;
 constexpr int CB_KO = CB_TK / 8;                      // 16-byte units of k per step
 constexpr int CB_PARTS = 3;
-constexpr long long CB_MAX_CHANNELS = 1ll << 20;
+constexpr ConvTiles CB_TILES = {OS2D_BACKBONE_CONV_BF16_TILE_M, OS2D_BACKBONE_CONV_BF16_TILE_N, OS2D_BACKBONE_CONV_BF16_SMALL_TILE_M,
+                                OS2D_BACKBONE_CONV_BF16_SMALL_TILE_N, CB_TK, OS2D_BACKBONE_CONV_BF16_MAX_GROUPS};
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-struct Conv {
-  const float *x, *s, *t, *r, *sr, *tr;
+struct Conv : ConvCall {
   const uint4* wp;
-  float* y;
-  int Cin, Cout, W, Wo, HWo, HW, stride, relu;
-  int ksteps;              // Kp / TILE_K
-  int kunits;              // Kp / 8
-  int mtiles;
-  long long pixels;        // N * Ho * Wo
-  long long tiles;
+  int kunits;              // Kp / 8, Kp = TILE_K * ksteps
 };
-
-// MODE 0: the fold alone, 1: + r, 2: + the fold of r
-template <int MODE>
-__device__ __forceinline__ float conv_out(float acc, float s, float t, float r, float sr, float tr, bool relu) {
-#pragma clang fp contract(off)
-  float v = bb_bn(acc, s, t);
-  if (MODE) {
-    const float d = MODE == 2 ? bb_bn(r, sr, tr) : r;
-    v = v + d;
-  }
-  return relu ? bb_relu_nan(v) : v;
-}
-
-// The epilogue of one wave's 64 x 64 outputs, as in csrc_backbone_conv/conv1x1.hip: register q of accumulator [a][b] is channel cbase +
-// 32 * a + (q & 3) + 8 * (q >> 2) at pixel pbase + 32 * b.  Every load is from a clamped, always valid address and has no branch around
-// it; only the stores are predicated.
-template <int MODE>
-__device__ __forceinline__ void conv_epilogue(const Conv& p, const f32x16 (&acc)[2][2], int cbase, long long pbase) {
-  const bool relu = p.relu != 0;
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-    float s[16], t[16], sr[16], tr[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int co = cbase + a * 32 + (q & 3) + 8 * (q >> 2);
-      const int cc = co < p.Cout ? co : p.Cout - 1;
-      s[q] = p.s[cc];
-      t[q] = p.t[cc];
-      sr[q] = MODE == 2 ? p.sr[cc] : 0.0f;
-      tr[q] = MODE == 2 ? p.tr[cc] : 0.0f;
-    }
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const long long pix = pbase + b * 32;
-      const bool pix_ok = pix < p.pixels;
-      const long long pc = pix_ok ? pix : p.pixels - 1;
-      const long long img = pc / p.HWo;
-      const long long at = img * p.Cout * p.HWo + (pc - img * p.HWo);
-      float r[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int co = cbase + a * 32 + (q & 3) + 8 * (q >> 2);
-        const int cc = co < p.Cout ? co : p.Cout - 1;
-        r[q] = MODE ? p.r[at + (long long)cc * p.HWo] : 0.0f;
-      }
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int co = cbase + a * 32 + (q & 3) + 8 * (q >> 2);
-        const float out = conv_out<MODE>(acc[a][b][q], s[q], t[q], r[q], sr[q], tr[q], relu);
-        if (pix_ok && co < p.Cout) p.y[at + (long long)co * p.HWo] = out;
-      }
-    }
-  }
-}
 
 // 8 consecutive k of one pixel -> its three 16-byte units.  The common case is branch-free, two values per conversion; a value at the top
 // of the range (NaN, Inf, or one that rounds to bf16's infinity) sends the 8 of them through the scalar rules of bf16x3_split_x, which
@@ -172,17 +110,7 @@ __global__ __launch_bounds__(CB_THREADS, 2) void conv1x1_bf16x3_kernel(const Con
 #pragma unroll
     for (int i = 0; i < BI; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const long long pix = n0 + 2 * (lane + 64 * i) + j;
-        xok[i][j] = pix < p.pixels;
-        xoff[i][j] = 0;
-        if (xok[i][j]) {
-          const long long img = pix / p.HWo;
-          const int at = (int)(pix - img * p.HWo);
-          const int src = p.stride == 1 ? at : (at / p.Wo) * 2 * p.W + (at % p.Wo) * 2;
-          xoff[i][j] = img * p.Cin * plane + src;
-        }
-      }
+      for (int j = 0; j < 2; ++j) xok[i][j] = conv_source(p, n0 + 2 * (lane + 64 * i) + j, xoff[i][j]);
 
     uint4 ra[AQ];
     float2 rb[BI][8];
@@ -233,12 +161,7 @@ __global__ __launch_bounds__(CB_THREADS, 2) void conv1x1_bf16x3_kernel(const Con
     };
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[a][b][q] = 0.0f;
+    conv_clear(acc);
 
     load(0);
     for (int kt = 0; kt < p.ksteps; ++kt) {
@@ -267,15 +190,7 @@ __global__ __launch_bounds__(CB_THREADS, 2) void conv1x1_bf16x3_kernel(const Con
       __syncthreads();                   // every wave has read its fragments: the image may be overwritten
     }
 
-    const int mode = p.r == nullptr ? 0 : (p.sr == nullptr ? 1 : 2);
-    const int cbase = m0 + wm * 64 + 4 * half;
-    const long long pbase = n0 + wn * 64 + l32;
-    if (mode == 0)
-      conv_epilogue<0>(p, acc, cbase, pbase);
-    else if (mode == 1)
-      conv_epilogue<1>(p, acc, cbase, pbase);
-    else
-      conv_epilogue<2>(p, acc, cbase, pbase);
+    conv_finish(p, acc, m0 + wm * 64, n0 + wn * 64, half, l32);
   }
 }
 
@@ -290,20 +205,7 @@ __global__ __launch_bounds__(CB_THREADS) void pack_kernel(const float* w, unsign
   }
 }
 
-// the limits of include/os2d_backbone.h on one tensor of N x C x plane
-bool too_large(int N, int C, long long plane) {
-  return (long long)N * C > BB_MAX_ROWS || plane > BB_MAX_PLANE || (long long)N * C * plane > BB_MAX_ELEMENTS;
-}
-
-bool channels_ok(int C) { return C >= 1 && C <= CB_MAX_CHANNELS; }
-
 long long padded_k(int Cin) { return ((long long)Cin + CB_TK - 1) / CB_TK * CB_TK; }
-
-// do [a, a + na) and [b, b + nb) bytes meet?
-bool bytes_meet(const void* a, size_t na, const void* b, size_t nb) {
-  const size_t pa = reinterpret_cast<size_t>(a), pb = reinterpret_cast<size_t>(b);
-  return pa < pb + nb && pb < pa + na;
-}
 
 }  // namespace
 
@@ -313,7 +215,7 @@ int os2d_backbone_conv_bf16_abi_version(void) { return OS2D_BACKBONE_CONV_BF16_A
 const char* os2d_backbone_conv_bf16_last_error(void) { return os2d_error_text; }
 
 size_t os2d_backbone_conv_bf16_packed_elems(int Cout, int Cin) {
-  if (!channels_ok(Cout) || !channels_ok(Cin)) return 0;
+  if (!conv_channels_ok(Cout) || !conv_channels_ok(Cin)) return 0;
   return (size_t)CB_PARTS * (size_t)padded_k(Cin) * (size_t)Cout;
 }
 
@@ -322,8 +224,8 @@ int os2d_backbone_conv_bf16_pack_weights(const float* w, unsigned short* wp, int
   if (bb_misaligned(w, 4)) return os2d_refuse("pack_weights: w not aligned (4 bytes)");
   if (bb_misaligned(wp, 16)) return os2d_refuse("pack_weights: wp not aligned (16 bytes)");
   if (Cout < 1 || Cin < 1) return os2d_refuse("pack_weights: bad shape (every size >= 1)");
-  if (!channels_ok(Cout) || !channels_ok(Cin)) return os2d_refuse("pack_weights: too large (Cin, Cout <= 2^20)");
-  if (bytes_meet(w, (size_t)Cout * Cin * sizeof(float), wp, os2d_backbone_conv_bf16_packed_elems(Cout, Cin) * sizeof(unsigned short)))
+  if (!conv_channels_ok(Cout) || !conv_channels_ok(Cin)) return os2d_refuse("pack_weights: too large (Cin, Cout <= 2^20)");
+  if (bb_bytes_meet(w, (size_t)Cout * Cin * sizeof(float), wp, os2d_backbone_conv_bf16_packed_elems(Cout, Cin) * sizeof(unsigned short)))
     return os2d_refuse("pack_weights: wp overlaps w");
   const long long Kp = padded_k(Cin), blocks = ((long long)Cout * Kp + CB_THREADS - 1) / CB_THREADS;
   const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096)), block(CB_THREADS);
@@ -333,51 +235,17 @@ int os2d_backbone_conv_bf16_pack_weights(const float* w, unsigned short* wp, int
 
 int os2d_backbone_conv1x1_bf16x3(const float* x, const unsigned short* wp, const float* s, const float* t, const float* r, const float* sr,
                                  const float* tr, float* y, int N, int Cin, int Cout, int H, int W, int stride, int relu, void* stream) {
-  if (!x || !wp || !s || !t || !y) return os2d_refuse("conv1x1_bf16x3: null pointer");
-  if ((sr == nullptr) != (tr == nullptr)) return os2d_refuse("conv1x1_bf16x3: sr and tr are both given or both NULL");
-  if (sr && !r) return os2d_refuse("conv1x1_bf16x3: sr and tr come only together with r");
-  if (bb_misaligned(x, 4) || bb_misaligned(s, 4) || bb_misaligned(t, 4) || bb_misaligned(r, 4) || bb_misaligned(sr, 4) || bb_misaligned(tr, 4) ||
-      bb_misaligned(y, 4))
-    return os2d_refuse("conv1x1_bf16x3: pointer not aligned (4 bytes)");
-  if (bb_misaligned(wp, 16)) return os2d_refuse("conv1x1_bf16x3: wp not aligned (16 bytes)");
-  if (N < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return os2d_refuse("conv1x1_bf16x3: bad shape (every size >= 1)");
-  if (stride != 1 && stride != 2) return os2d_refuse("conv1x1_bf16x3: stride is 1 or 2");
-  if (relu != 0 && relu != 1) return os2d_refuse("conv1x1_bf16x3: relu is 0 or 1");
-  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-  const long long HW = (long long)H * W, HWo = (long long)Ho * Wo;
-  if (Cin > CB_MAX_CHANNELS || Cout > CB_MAX_CHANNELS || too_large(N, Cin, HW) || too_large(N, Cout, HWo))
-    return os2d_refuse("conv1x1_bf16x3: too large (Cin, Cout <= 2^20; for x and y: N * C < 2^31, H * W <= 2^30, N * C * H * W <= 2^40)");
-  const long long ny = (long long)N * Cout * HWo;
-  const size_t ybytes = (size_t)ny * sizeof(float);
-  if (bytes_meet(y, ybytes, x, (size_t)N * Cin * HW * sizeof(float))) return os2d_refuse("conv1x1_bf16x3: y overlaps x");
-  if (bytes_meet(y, ybytes, wp, os2d_backbone_conv_bf16_packed_elems(Cout, Cin) * sizeof(unsigned short)))
-    return os2d_refuse("conv1x1_bf16x3: y overlaps wp");
-  if (r && bb_overlap(r, y, ny)) return os2d_refuse("conv1x1_bf16x3: y overlaps r");
-
   Conv p;
-  p.x = x; p.wp = reinterpret_cast<const uint4*>(wp); p.s = s; p.t = t; p.r = r; p.sr = sr; p.tr = tr; p.y = y;
-  p.Cin = Cin; p.Cout = Cout; p.W = W; p.Wo = Wo; p.HWo = (int)HWo; p.HW = (int)HW; p.stride = stride; p.relu = relu;
-  p.ksteps = (int)(padded_k(Cin) / CB_TK);
-  p.kunits = (int)(padded_k(Cin) / 8);
-  p.pixels = (long long)N * HWo;
-  const bool small = Cout <= OS2D_BACKBONE_CONV_BF16_SMALL_TILE_M;
-  const int tm = small ? OS2D_BACKBONE_CONV_BF16_SMALL_TILE_M : OS2D_BACKBONE_CONV_BF16_TILE_M;
-  const int tn = small ? OS2D_BACKBONE_CONV_BF16_SMALL_TILE_N : OS2D_BACKBONE_CONV_BF16_TILE_N;
-  p.mtiles = (Cout + tm - 1) / tm;
-  p.tiles = p.mtiles * ((p.pixels + tn - 1) / tn);
-  const bool vec = stride == 1 && HW % 2 == 0 && !bb_misaligned(x, 8);
-  const dim3 grid((unsigned)(p.tiles < OS2D_BACKBONE_CONV_BF16_MAX_GROUPS ? p.tiles : OS2D_BACKBONE_CONV_BF16_MAX_GROUPS)), block(CB_THREADS);
-  if (small) {
-    if (vec)
-      hipLaunchKernelGGL((conv1x1_bf16x3_kernel<1, true>), grid, block, 0, os2d_stream(stream), p);
-    else
-      hipLaunchKernelGGL((conv1x1_bf16x3_kernel<1, false>), grid, block, 0, os2d_stream(stream), p);
-  } else {
-    if (vec)
-      hipLaunchKernelGGL((conv1x1_bf16x3_kernel<2, true>), grid, block, 0, os2d_stream(stream), p);
-    else
-      hipLaunchKernelGGL((conv1x1_bf16x3_kernel<2, false>), grid, block, 0, os2d_stream(stream), p);
-  }
+  const ConvWeights weights = {wp, "wp", 16, os2d_backbone_conv_bf16_packed_elems(Cout, Cin) * sizeof(unsigned short)};
+  if (const int rc = conv_check("conv1x1_bf16x3", p, weights, x, s, t, r, sr, tr, y, N, Cin, Cout, H, W, stride, relu)) return rc;
+  p.wp = reinterpret_cast<const uint4*>(wp);
+  bool small;
+  const dim3 grid(conv_plan(p, CB_TILES, small)), block(CB_THREADS);
+  p.kunits = p.ksteps * CB_KO;
+  const bool vec = stride == 1 && p.HW % 2 == 0 && !bb_misaligned(x, 8);
+  const auto kernel = small ? (vec ? conv1x1_bf16x3_kernel<1, true> : conv1x1_bf16x3_kernel<1, false>)
+                            : (vec ? conv1x1_bf16x3_kernel<2, true> : conv1x1_bf16x3_kernel<2, false>);
+  hipLaunchKernelGGL(kernel, grid, block, 0, os2d_stream(stream), p);
   return os2d_launched("conv1x1_bf16x3_kernel");
 }
 

@@ -198,12 +198,9 @@ class FusedBackbone(object):
         y = torch.empty((n, cout, (h - 1) // stride + 1, (w - 1) // stride + 1), dtype=x.dtype, device=x.device)
         if r is not None and r.shape != y.shape:
             raise ValueError("residual of shape {} for a block output of shape {}".format(tuple(r.shape), tuple(y.shape)))
-        if wp is not None:
-            _backbone_conv_bf16_lib.call("os2d_backbone_conv1x1_bf16x3", x, wp, fold[0], fold[1], r, None, None, y, n, cin, cout, h, w,
-                                         stride, int(relu), STREAM)
-            return y
-        _backbone_conv_lib.call("os2d_backbone_conv1x1", x, conv.weight.detach(), fold[0], fold[1], r, None, None, y, n, cin, cout, h, w,
-                                stride, int(relu), STREAM)
+        lib, entry, weights = ((_backbone_conv_bf16_lib, "os2d_backbone_conv1x1_bf16x3", wp) if wp is not None else
+                               (_backbone_conv_lib, "os2d_backbone_conv1x1", conv.weight.detach()))
+        lib.call(entry, x, weights, fold[0], fold[1], r, None, None, y, n, cin, cout, h, w, stride, int(relu), STREAM)
         return y
 
     def forward_conv1x1(self, x):

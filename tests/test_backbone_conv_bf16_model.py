@@ -183,8 +183,9 @@ def test_library_flags_includes_and_stamp(tmp_path):
         for inc in build.local_includes(path):
             assert os.path.basename(inc) in names, (path, inc)
     source = open(os.path.join(rec.csrc, "conv1x1_bf16x3.hip")).read()
-    assert "bb_bn(" in source and "bb_relu_nan(" in source and "bb_overlap(" in source and "__builtin_amdgcn_mfma_f32_32x32x16_bf16" in source
-    assert "bf16x3_split(" in source and not re.search(r"\basm\b", source) and not re.search(r"atomic\w*\s*\(", source)
+    common = F.shared_conv_header(rec, source)                           # the fp32 GEMM's epilogue and contract: the same text, not a copy
+    assert "bb_bn(" in common and "bb_relu_nan(" in common and "bb_overlap(" in common and "__builtin_amdgcn_mfma_f32_32x32x16_bf16" in source
+    assert "bf16x3_split(" in source and not re.search(r"\basm\b", source + common) and not re.search(r"atomic\w*\s*\(", source + common)
     h0 = build.source_hash(rec)
     assert build.source_hash(rec._replace(flags=rec.flags + ["-DX"])) != h0
     (tmp_path / "new_header.h").write_text("// new\n")

@@ -16,6 +16,7 @@ import backbone_conv_model as C
 from os2d_amd import _backbone_conv_bf16_lib as L
 from os2d_amd import _backbone_conv_lib as L32
 from os2d_amd._native import STREAM
+from test_backbone_conv_stages_gpu import FORMS, draw
 from test_backbone_stages_gpu import fold_draw, frame_intact, framed, gen, shifted
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,6 @@ TM, TN, TK = L.TILE_M, L.TILE_N, L.TILE_K
 COUTS = [1, L.SMALL_TILE_M - 1, L.SMALL_TILE_M, L.SMALL_TILE_M + 1, TM - 1, TM, TM + 1, 2 * TM + 1]
 CINS = [1, 7, 8, 9, 15, 16, 17, TK - 1, TK, TK + 1, 2 * TK + 1]
 HWS = [1, 3, 4, 5, TN - 1, TN, TN + 1, L.SMALL_TILE_N - 1, L.SMALL_TILE_N, L.SMALL_TILE_N + 1]
-FORMS = ["fold", "residual", "residual_fold"]
 SENTINEL = 0x5A5A
 
 
@@ -38,16 +38,6 @@ def packed(w, device):
     assert wp.data_ptr() % 16 == 0
     L.call("os2d_backbone_conv_bf16_pack_weights", w.contiguous().to(device), wp, cout, cin, STREAM)
     return whole, wp
-
-
-def draw(N, Cin, Cout, H, W, stride, form, g):
-    """The operands of one call on the CPU: x, w, (s, t), r, (sr, tr)"""
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    x, w = torch.randn(N, Cin, H, W, generator=g), torch.randn(Cout, Cin, generator=g)
-    s, t = fold_draw(Cout, g)
-    r = torch.randn(N, Cout, Ho, Wo, generator=g) if form != "fold" else None
-    sr, tr = fold_draw(Cout, g) if form == "residual_fold" else (None, None)
-    return x, w, s, t, r, sr, tr
 
 
 def run(ops, stride, relu, device, shifts=(0, 0, 0), fp32=False):

@@ -203,6 +203,21 @@ def test_library_record_header_binding_and_exports_agree():
     assert len(L.SIGNATURES["os2d_backbone_conv1x1"][1]) == 16
 
 
+def shared_conv_header(rec, source):
+    """-> the text of csrc_backbone/conv1x1_common.h, after checking that the unit `source` of the record takes the epilogue and the
+    argument contract from it: the unit includes it and defines neither of them, the header is among the record's headers and holds them."""
+    from os2d_amd import build
+    path = os.path.join(build.BACKBONE_CSRC, "conv1x1_common.h")
+    assert "conv1x1_common.h" in [os.path.basename(inc) for inc in build.local_includes(os.path.join(rec.csrc, rec.sources[0]))]
+    assert all(path in build.headers(lib) for lib in (rec, build.BACKBONE, build.BACKBONE_CONV, build.BACKBONE_CONV_BF16))
+    assert [os.path.basename(inc) for inc in build.local_includes(path)] == ["backbone_common.h"]          # and no library's public header
+    common = open(path).read()
+    for name in ("conv_out", "conv_epilogue", "too_large"):
+        assert not re.search(r"\b\w*{}\s*[<(]".format(name), source), name
+        assert len(re.findall(r"^[\w \t]*\b\w*{}\(.*\) {{$".format(name), common, flags=re.M)) == 1, name
+    return common
+
+
 def test_library_flags_includes_and_stamp(tmp_path):
     from os2d_amd import build
     rec = build.BACKBONE_CONV
@@ -219,8 +234,10 @@ def test_library_flags_includes_and_stamp(tmp_path):
         for inc in build.local_includes(path):
             assert os.path.basename(inc) in names, (path, inc)
     source = open(os.path.join(rec.csrc, "conv1x1.hip")).read()
-    assert "bb_bn(" in source and "bb_relu_nan(" in source and "bb_overlap(" in source and "__builtin_amdgcn_mfma_f32_32x32x2f32" in source
-    assert not re.search(r"\basm\b", source)                              # no inline assembly
+    # the fold, the ReLU and the overlap predicate are those of conv1x1_common.h, which the unit includes and does not restate
+    common = shared_conv_header(rec, source)
+    assert "bb_bn(" in common and "bb_relu_nan(" in common and "bb_overlap(" in common and "__builtin_amdgcn_mfma_f32_32x32x2f32" in source
+    assert not re.search(r"\basm\b", source) and not re.search(r"\basm\b", common)              # no inline assembly
     h0 = build.source_hash(rec)
     assert build.source_hash(rec._replace(flags=rec.flags + ["-DX"])) != h0
     (tmp_path / "new_header.h").write_text("// new\n")
